@@ -9,7 +9,15 @@ resident in HBM.  Subframes shard across ranks with no data-path collective (wea
 the only collective is the RCCL broadcast of the parameter block from rank 0 (plus the
 barriers / max-reduction of the timing harness).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--batch 8192]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--batch 8192] [--full]
+                    [--dump-outputs DIR]
+
+A plain run sets up, settles the clocks, warms up, times the K steps and prints the result line.
+--full adds what takes runs of its own: the CPU baseline (`cpu_baseline`), the per-kernel HIP-event
+timings behind `roofline` and C5's `at_2048_subframes`; a plain run prints null for them.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32), a fixed
+seeded sample of the subframes / code blocks where the whole output is too large; the inputs are
+seeded, so two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import json
@@ -261,6 +269,10 @@ def bench_c5_chain(args, world, rank, dist, torch):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     its, _ = ub.results()
+    if args.dump_outputs:        # per transport block: the code blocks' decoded bytes, and their iteration counts
+        dump_rows(args, rank, world, "decoded_bytes", ub.d_c, n_sf, ub.C * ub.c_stride, np.uint8,
+                  trim=lambda a, rows: a.reshape(len(rows), ub.C, ub.c_stride)[:, :, :C5_K // 8])
+        dump_array(args, rank, world, "iterations", its)
     ub.close()
     value = n_sf * args.steps * world / elapsed
     per_launch_ms = elapsed * 1000.0 / args.steps
@@ -366,11 +378,14 @@ def bench_c5(args, world, rank, dist, torch):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     its, _ = dec.results()
+    if args.dump_outputs:        # per code block: the decoded bytes, and the iteration counts of all of them
+        dump_rows(args, rank, world, "decoded_bytes", dec.d_out, n_cb, C5_K // 8, np.uint8)
+        dump_array(args, rank, world, "iterations", its)
     dec.close()
     value = n_sf * args.steps * world / elapsed
     per_launch_ms = elapsed * 1000.0 / args.steps
     small = None
-    if n_sf != 2048 and rank == 0 and world == 1:
+    if args.full and n_sf != 2048 and rank == 0 and world == 1:
         # the figure at 2048 subframes per launch (2 waves per SIMD, one round), comparable with the
         # rounds before the batch grew: the same kernel on a smaller launch, 5 timed runs
         d2 = (oai.TurboDecoder8Batch if args.c5_bits == 8 else oai.TurboDecoderBatch)(C5_K, 2048 * C5_CB)
@@ -518,21 +533,28 @@ def bench_fep(args, world, rank, dist, torch):
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    # k_fep launch duration for the roofline: HIP events on the launch stream around each launch
-    sid = torch.cuda.current_stream().cuda_stream
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-           for _ in range(args.kernel_reps)]
-    for e0, e1 in evs:
-        e0.record()
-        fb.run(stream=sid)
-        e1.record()
-    torch.cuda.synchronize()
-    kern_ms = sum(e0.elapsed_time(e1) for e0, e1 in evs) / len(evs)
+    if args.dump_outputs:        # per subframe: the frequency-domain symbols [antenna x symbol x bin x (re, im)]
+        dump_rows(args, rank, world, "rxdataF", fb.d_rxF, n_sf, n_ant * nsym * N * 4, np.int16)
+    alg = n_sf * n_ant * nsym * N * 4 * 2                # DFT windows read + frequency symbols written
+    roofline = None              # the per-kernel timing is a run of its own: --full
+    if args.full:
+        # k_fep launch duration for the roofline: HIP events on the launch stream around each launch
+        sid = torch.cuda.current_stream().cuda_stream
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+               for _ in range(args.kernel_reps)]
+        for e0, e1 in evs:
+            e0.record()
+            fb.run(stream=sid)
+            e1.record()
+        torch.cuda.synchronize()
+        kern_ms = sum(e0.elapsed_time(e1) for e0, e1 in evs) / len(evs)
+        ach = alg / (kern_ms * 1e-3) / 1e9
+        roofline = {"bound": "hbm", "kernel": "k_fep<11>", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": ach / HBM_PEAK_GBS, "traffic": _traffic("FEP", "k_fep<11>", n_sf), "kernel_ms": kern_ms,
+                    "algorithmic_bytes_per_launch": alg}
     fb.close()
     value = n_sf * args.steps * world / elapsed
     per_launch_ms = elapsed * 1000.0 / args.steps       # one k_fep launch per step
-    alg = n_sf * n_ant * nsym * N * 4 * 2                # DFT windows read + frequency symbols written
-    ach = alg / (kern_ms * 1e-3) / 1e9
     cpu = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -571,9 +593,7 @@ def bench_fep(args, world, rank, dist, torch):
             "data": "synthetic int16 IQ, resident in HBM",
             "config": {"workload": "slot_fep 20 MHz normal CP, 2 RX antennas, 14 x dft2048 per antenna",
                        "config_id": "FEP", "subframes_per_gpu_per_step": n_sf, "parallelism": f"subframe-sharded x{world}"},
-            "roofline": {"bound": "hbm", "kernel": "k_fep<11>", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": ach / HBM_PEAK_GBS, "traffic": _traffic("FEP", "k_fep<11>", n_sf), "kernel_ms": kern_ms,
-                         "algorithmic_bytes_per_launch": alg},
+            "roofline": roofline,
             "cpu_baseline": cpu}), flush=True)
 
 
@@ -667,9 +687,15 @@ def bench_ue(args, world, rank, dist, torch):
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    # per-stage launch durations (HIP events on the launch stream)
+    if args.dump_outputs:        # per subframe: codeword 0's unscrambled LLRs (the row's unused tail cleared)
+        def used(a, rows):
+            for j, r in enumerate(rows):
+                a[j, rb.llr_count(int(r) % 10):] = 0
+            return a
+        dump_rows(args, rank, world, "llr", rb.d_llr, n_sf, rb.stride * 2, np.int16, trim=used)
+    # --full: per-stage launch durations (HIP events on the launch stream)
     kern_ms = {}
-    for name, fn in stages.items():
+    for name, fn in stages.items() if args.full else ():
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                for _ in range(args.kernel_reps)]
         for e0, e1 in evs:
@@ -696,8 +722,13 @@ def bench_ue(args, world, rank, dist, torch):
         cb.close()
     rb.close()
     value = n_sf * args.steps * world / elapsed
-    dom = max(kern_ms, key=kern_ms.get)
-    ach = alg[dom] / (kern_ms[dom] * 1e-3) / 1e9
+    roofline = None              # the per-stage timings are runs of their own: --full
+    if args.full:
+        dom = max(kern_ms, key=kern_ms.get)
+        ach = alg[dom] / (kern_ms[dom] * 1e-3) / 1e9
+        roofline = {"bound": "hbm", "kernel": dom, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": ach / HBM_PEAK_GBS, "traffic": _stage_traffic(args.config, dom, n_sf),
+                    "kernel_ms": kern_ms, "algorithmic_bytes_per_launch": alg}
     cpu = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = _ue_cpu_baseline(args, p, Qm, tm3)
@@ -721,9 +752,7 @@ def bench_ue(args, world, rank, dist, torch):
             "data": f"GPU-transmitted {'C3' if tm3 else 'C2'} subframes (synthetic payload), resident in HBM",
             "config": {"workload": wl, "config_id": args.config, "subframes_per_gpu_per_step": n_sf,
                        "parallelism": f"subframe-sharded x{world}"},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": ach / HBM_PEAK_GBS, "traffic": _stage_traffic(args.config, dom, n_sf),
-                         "kernel_ms": kern_ms, "algorithmic_bytes_per_launch": alg},
+            "roofline": roofline,
             "end_to_end_algorithmic_GBps": sum(alg.values()) / (elapsed / args.steps) / 1e9,
             "cpu_baseline": cpu}), flush=True)
 
@@ -786,6 +815,42 @@ def clock_settle(run, sync, ms):
             sync()
     sync()
     return n
+
+
+DUMP_BUDGET = 48 << 20        # bytes of float32 samples per run of --dump-outputs (its limit: 64 MB in all)
+
+
+def dump_rows(args, rank, world, name, d_ptr, n_rows, row_bytes, dtype, budget=DUMP_BUDGET, trim=None):
+    """--dump-outputs: rows of a device array the timed path wrote (row = one subframe / code block),
+    all of them where they fit `budget`, else a fixed seeded sample, as DIR/<name>.npy (float32,
+    [rows][elements of `dtype`]) with the row numbers in DIR/<name>_rows.npy (float64).  Only the
+    sampled rows cross to the host; trim(array, rows) cuts or clears a row's padding, which the
+    kernels leave unwritten."""
+    import ctypes
+    import numpy as np
+    import openair4g_amd as oai
+    L = oai.lib()
+    n_el = row_bytes // np.dtype(dtype).itemsize
+    k = max(1, min(n_rows, budget // (n_el * 4 + 8)))
+    rows = np.sort(np.random.default_rng(0xD0).choice(n_rows, size=k, replace=False))
+    out = np.empty((k, n_el), dtype=dtype)
+    if L.oai4g_sync() != 0:
+        raise oai.OAI4GError(L.oai4g_last_error().decode())
+    for j, r in enumerate(rows):
+        if L.oai4g_memcpy_d2h(ctypes.c_void_p(out[j].ctypes.data), d_ptr + int(r) * row_bytes, row_bytes) != 0:
+            raise oai.OAI4GError(L.oai4g_last_error().decode())
+    dump_array(args, rank, world, name, out if trim is None else trim(out, rows))
+    dump_array(args, rank, world, name + "_rows", rows.astype(np.float64))
+
+
+def dump_array(args, rank, world, name, a):
+    """--dump-outputs: one host array as DIR/<name>.npy (float32; float64 where it is one already);
+    with more than one rank, rank r writes <name>.rank<r>.npy."""
+    import numpy as np
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    a = np.asarray(a)
+    np.save(os.path.join(args.dump_outputs, name + (f".rank{rank}" if world > 1 else "") + ".npy"),
+            a if a.dtype == np.float64 else a.astype(np.float32))
 
 
 def launch_ranks(n, argv):
@@ -935,9 +1000,17 @@ def main():
     ap.add_argument("--full-grid", action="store_true",
                     help="transmit configurations: the eNB's whole grid (PDSCH + CRS + PCFICH/PDCCH + PSS/SSS/PBCH + "
                          "PHICH) over subframe indices 0..9 instead of the PDSCH of --subframe")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--kernel-reps", type=int, default=5, help="serial runs timed per kernel for the roofline")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the CPU baseline, the per-kernel roofline timing and C5's "
+                         "2048-subframe side run (runs of their own after the timed steps; a plain run skips them "
+                         "and prints null in their places)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left on the device as DIR/<name>.npy "
+                         "(float32; a fixed seeded sample of rows where the whole output exceeds the size budget)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: seconds per CPU baseline leg")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--kernel-reps", type=int, default=5,
+                    help="--full: serial runs timed per kernel for the roofline")
     ap.add_argument("--c5-mode", default="8it", choices=["8it", "snr", "chain"],
                     help="C5 decoder inputs; chain = from the e soft bits through RM-rx + deinterleaving")
     ap.add_argument("--c5-bits", type=int, default=16, choices=[16, 8], help="C5 decoder: 16-bit or 8-bit")
@@ -950,6 +1023,10 @@ def main():
         args.batch = {"C3": 8192, "C4": 1024, "FEP": 8192, "UE": 4096, "UE3": 2048, "C5": C5_BATCH}.get(args.config, 2048)
     if args.cpu_stub:
         args.backend = "gloo"
+        if args.dump_outputs:
+            sys.exit("bench: --cpu-stub computes no output to dump")
+    if not args.full:
+        args.no_cpu_baseline = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -1050,10 +1127,13 @@ def bench_tx(args, world, rank, host):
     host.barrier()
     elapsed = time.perf_counter() - t0
 
-    # per-kernel launch durations for the roofline: the same batch run serially, HIP events on the
-    # launch stream around each kernel (outside the timed region)
+    if args.dump_outputs:        # the last timed step's time-domain IQ: [subframe][antenna x sample x (re, im)]
+        dump_rows(args, rank, world, "iq", pipe.d_iq, args.batch, pipe.n_ant * pipe.spt * 4, np.int16)
+
+    # --full: per-kernel launch durations for the roofline: the same batch run serially, HIP events on
+    # the launch stream around each kernel (outside the timed region)
     kern = [[], []]
-    for _ in range(args.kernel_reps):
+    for _ in range(args.kernel_reps if args.full else 0):
         a, b = pipe.run_timed()
         kern[0].append(a)
         kern[1].append(b)
@@ -1068,20 +1148,36 @@ def bench_tx(args, world, rank, host):
     sfs = range(10) if args.full_grid else [args.subframe]
     G = [sum(pipe.G(cw, sf) for sf in sfs) / len(sfs) for cw in range(params.n_cw)]      # mean over the batch
     ebits_b = sum((g + 7) / 8 for g in G)
-    enc_ms = float(np.median(kern[0]))
-    mod_ms = float(np.median(kern[1]))
-    per_kernel = {            # bytes = the kernel's own boundary (payload -> e words -> IQ), a diagnostic
-        "encode_rm_scramble": {"ms": enc_ms, "bytes": args.batch * (payload_b + ebits_b)},
-        "modulate_idft_cp": {"ms": mod_ms, "bytes": args.batch * (ebits_b + iq_b)},
-    }
-    dom = max(per_kernel, key=lambda k: per_kernel[k]["ms"])
-    # roofline.achieved: SURVEY 8(d)'s algorithmic bytes per subframe (payload read + IQ written)
-    # x the subframes one launch processes, over the dominant kernel's launch time (HIP events)
-    alg_launch = args.batch * (payload_b + iq_b)
-    ach = alg_launch / (per_kernel[dom]["ms"] * 1e-3) / 1e9
-    ptag = args.config + ("_full" if args.full_grid else "")     # profiles/traffic_<tag>.json
-    traffic = _traffic(ptag, dom, args.batch)
-    prof_ms = _traffic(ptag + "_ms", dom, args.batch)           # rocprofv3 average of the same command
+    roofline = None            # the per-kernel timings are runs of their own: --full
+    if args.full:
+        enc_ms = float(np.median(kern[0]))
+        mod_ms = float(np.median(kern[1]))
+        per_kernel = {            # bytes = the kernel's own boundary (payload -> e words -> IQ), a diagnostic
+            "encode_rm_scramble": {"ms": enc_ms, "bytes": args.batch * (payload_b + ebits_b)},
+            "modulate_idft_cp": {"ms": mod_ms, "bytes": args.batch * (ebits_b + iq_b)},
+        }
+        dom = max(per_kernel, key=lambda k: per_kernel[k]["ms"])
+        # roofline.achieved: SURVEY 8(d)'s algorithmic bytes per subframe (payload read + IQ written)
+        # x the subframes one launch processes, over the dominant kernel's launch time (HIP events)
+        alg_launch = args.batch * (payload_b + iq_b)
+        ach = alg_launch / (per_kernel[dom]["ms"] * 1e-3) / 1e9
+        ptag = args.config + ("_full" if args.full_grid else "")     # profiles/traffic_<tag>.json
+        traffic = _traffic(ptag, dom, args.batch)
+        prof_ms = _traffic(ptag + "_ms", dom, args.batch)           # rocprofv3 average of the same command
+        roofline = {"bound": "hbm", "kernel": dom, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": ach / HBM_PEAK_GBS, "traffic": traffic,
+                    "algorithmic_bytes_per_launch": alg_launch,
+                    "bytes_basis": f"SURVEY 8(d): payload + IQ = {payload_b + iq_b} B per subframe x "
+                                   f"{args.batch} subframes per launch",
+                    "timing": f"HIP events around each kernel on its launch stream, median of "
+                              f"{args.kernel_reps} serial runs of the batch (outside the timed region)",
+                    "kernel_ms": {k: v["ms"] for k, v in per_kernel.items()},
+                    "profiler_ms": prof_ms,
+                    "frac_profiler": (alg_launch / (prof_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if prof_ms else None,
+                    "valu_issue_frac": _valu_busy(ptag, args.batch),
+                    "kernel_boundary_bytes_per_launch": {k: v["bytes"] for k, v in per_kernel.items()},
+                    "kernel_boundary_frac": {k: v["bytes"] / (v["ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS
+                                             for k, v in per_kernel.items()}}
 
     cpu = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
@@ -1115,20 +1211,7 @@ def bench_tx(args, world, rank, host):
                        "full_grid": bool(args.full_grid),
                        "TBS": [params.TBS[cw] for cw in range(params.n_cw)], "G": G,
                        "parallelism": f"subframe-sharded x{world}"},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": ach / HBM_PEAK_GBS, "traffic": traffic,
-                         "algorithmic_bytes_per_launch": alg_launch,
-                         "bytes_basis": f"SURVEY 8(d): payload + IQ = {payload_b + iq_b} B per subframe x "
-                                        f"{args.batch} subframes per launch",
-                         "timing": f"HIP events around each kernel on its launch stream, median of "
-                                   f"{args.kernel_reps} serial runs of the batch (outside the timed region)",
-                         "kernel_ms": {k: v["ms"] for k, v in per_kernel.items()},
-                         "profiler_ms": prof_ms,
-                         "frac_profiler": (alg_launch / (prof_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if prof_ms else None,
-                         "valu_issue_frac": _valu_busy(ptag, args.batch),
-                         "kernel_boundary_bytes_per_launch": {k: v["bytes"] for k, v in per_kernel.items()},
-                         "kernel_boundary_frac": {k: v["bytes"] / (v["ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS
-                                                  for k, v in per_kernel.items()}},
+            "roofline": roofline,
             "end_to_end_algorithmic_GBps": value * (payload_b + iq_b) / 1e9,
             "per_rank_subframes_per_s": [args.batch * args.steps / e for e in rank_elapsed],
             # value over the sum of the ranks' own rates: 1.0 when every shard takes the same time (the

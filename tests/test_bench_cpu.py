@@ -18,6 +18,10 @@ def _bench(*args, timeout=240):
                           timeout=timeout, env=env, cwd=ROOT)
 
 
+def _line(r):
+    return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+
+
 def test_bench_spawns_ranks_gloo_stub():
     r = _bench("--gpus", "2", "--cpu-stub", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--batch", "64")
     assert r.returncode == 0, r.stderr
@@ -31,6 +35,24 @@ def test_bench_spawns_ranks_gloo_stub():
     assert out["value"] > 0 and out["ms_per_step"] > 0
     assert len(out["per_rank_subframes_per_s"]) == 2 and min(out["per_rank_subframes_per_s"]) > 0
     assert 0 < out["rank_efficiency"] <= 1.0 + 1e-9
+
+
+def test_bench_side_runs_only_with_full(tmp_path):
+    """A plain run times its steps and prints the line; the per-kernel roofline runs (and the CPU
+    baseline, tests/test_gpu_bench_dump.py) belong to --full.  The stub computes nothing to dump."""
+    plain = _bench("--gpus", "1", "--cpu-stub", "--steps", "3", "--warmup", "1", "--batch", "64")
+    assert plain.returncode == 0, plain.stderr
+    out = _line(plain)
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert out["unit"] == "subframes/s" and out["higher_is_better"] is True and out["dtype"] == "int16"
+    assert out["metric"] == "DL subframes/sec (20 MHz, 2x2, 64-QAM)"
+    assert out["roofline"] is None and out["cpu_baseline"] is None
+    full = _bench("--gpus", "1", "--cpu-stub", "--steps", "3", "--warmup", "1", "--batch", "64", "--full",
+                  "--no-cpu-baseline", "--kernel-reps", "2")
+    assert full.returncode == 0, full.stderr
+    assert set(_line(full)["roofline"]["kernel_ms"]) == {"encode_rm_scramble", "modulate_idft_cp"}
+    r = _bench("--gpus", "1", "--cpu-stub", "--steps", "1", "--dump-outputs", str(tmp_path / "d"))
+    assert r.returncode != 0 and not (tmp_path / "d").exists()
 
 
 def test_bench_failing_rank_fails_the_job():

@@ -15,6 +15,7 @@ for lib in variants/*/libopenair4g_amd.so; do
     || { echo "FAILED tests with $lib"; grep -E "FAILED|Error" gpurun_out/${TAG}_tests_*.log | head; exit 1; }
   echo "$lib: $(tail -1 gpurun_out/${TAG}_tests_$(basename $(dirname $lib)).log)"
 done
+set -- --full "$@"   # the lines below read roofline.kernel_ms
 for rep in $(seq $REPS); do
   for lib in openair4g_amd/lib/libopenair4g_amd.so variants/*/libopenair4g_amd.so; do
     [ -f "$lib" ] || continue

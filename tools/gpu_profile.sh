@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 mkdir -p gpurun_out/prof
 TAG=${TAG:-r01}
-CMD="python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --kernel-reps 2 --config ${CONFIG:-C3}"
+CMD="python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --kernel-reps 2 --config ${CONFIG:-C3}"
 # counter passes serialise every dispatch: no clock-settle runs there (durations come from the trace pass)
 CMDP="$CMD --settle-ms 0"
 run() {

@@ -22,6 +22,7 @@ TAG=${TAG:-round}
 fail() { echo "STEP FAILED: $1"; exit 1; }
 bench_line() {   # $1 = name, rest = bench.py args
   local name=$1; shift
+  set -- --full "$@"   # the recorded lines carry the roofline and the CPU baseline
   timeout -k 10 400 python bench.py "$@" > gpurun_out/bench_${TAG}_${name}.json.log 2>&1 \
     || { tail -5 gpurun_out/bench_${TAG}_${name}.json.log; fail "bench $*"; }
   echo "bench [$*]: $(grep -o '"value": [0-9.]*' gpurun_out/bench_${TAG}_${name}.json.log | head -1)"

@@ -58,7 +58,7 @@ def main(prof_dir, tag, config, out_dir):
                                             "VGPR_Count", "SGPR_Count")})
     traffic = {}
     lines = [f"# rocprofv3 summary {tag} — config {config}", "",
-             "Command: `rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline`"
+             "Command: `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline`"
              f" (+ separate `--pmc FETCH_SIZE` and `--pmc WRITE_SIZE` passes)", "",
              "| kernel | calls | avg µs | min µs | max µs | % |", "|---|---|---|---|---|---|"]
     for s in stats:

@@ -643,9 +643,11 @@ int oai4g_tx_encode(const oai4g_tx_config_t *cfg, int n_sf, const uint8_t *d_pay
 /* Stage entry: run only the modulator kernel (packed scrambled e bits in d_work, as oai4g_tx_encode
  * leaves them -> QAM / RE map / precoding / IDFT / CP -> d_iq). */
 int oai4g_tx_modulate(const oai4g_tx_config_t *cfg, int n_sf, const void *d_work, int32_t *d_iq, void *stream);
-/* 1 when the configuration's range check admits the modulator's fused IDFT levels (2048-point
- * two-antenna LARGE_CDD whose largest QAM level keeps every 256- / 1024-level value inside int16;
- * DESIGN.md), 0 otherwise. */
+/* 1 when the configuration's range check admits the modulator's no-saturation IDFT forms, 0
+ * otherwise.  It can pass for every 2048-point normal-prefix transmit mode (TM1, ALAMOUTI, two- and
+ * four-antenna LARGE_CDD): it does when the largest level among the QAM / QPSK tables, the CRS and
+ * the static REs of oai4g_tx_config_set_control / _set_common keeps every value of the leaf, 64-,
+ * 256-, 1024- and 2048-levels inside int16 with a margin; those calls re-check it. */
 int oai4g_tx_mod_nosat(const oai4g_tx_config_t *cfg);
 
 /* Diagnostics: average ms of the encoder kernel stopped after phase `stop_phase`

@@ -728,11 +728,12 @@ struct oai4g_tx_config {
   cfg_dev_t *d = nullptr;           /* device copy */
   uint16_t *d_remap = nullptr;
   std::vector<uint16_t> h_remap;
-  uint32_t *d_crs = nullptr;
   uint32_t *d_gold = nullptr;           /* [10][n_cw][ebits_words] scrambling words */
-  std::vector<uint32_t> h_crs;          /* [10][4][200] packed CRS IQ */
-  uint32_t *d_ctl = nullptr;            /* static RE values [10][14][2][N] (set_control / set_common) */
-  std::vector<uint32_t> h_ctl;          /* host copy of d_ctl's table (empty when no control REs) */
+  /* build_stat_tm's inputs (host only) */
+  std::vector<uint32_t> h_crs;          /* [10][6][200] packed CRS IQ of pilot entry i, index m (empty without CRS) */
+  std::vector<uint32_t> h_ctl;          /* [10][14][ctl_planes][N] packed IQ of the static REs of set_control /
+                                           set_common per antenna (empty without them) */
+  uint32_t ctl_planes = 2;              /* 2, or the TX antennas when there are more */
   uint32_t *d_stat = nullptr;           /* cfg_dev_t::stat_tm */
   int ctl_vmax = 0;                     /* largest I / Q magnitude in the static-RE table (mod_nosat_ok) */
   std::vector<oai4g_dci_alloc_t> dci;   /* oai4g_tx_config_set_control's DCI set */
@@ -1159,10 +1160,12 @@ static int derive_cfg(oai4g_tx_config *cfg, const oai4g_tx_params_t *p, const ui
   return rm_fail ? -2 : 0;
 }
 
-/* cfg_dev_t::stat_tm from the RE map, the CRS values and the control table: for kernel antenna `ant`
- * (TM1: the one transform) the value the modulator's static-RE step used to produce per RE
- * (pilots.c:43-168: port p's pilot on antenna p, every port's in the single TM1 transform; the
- * control REs of generate_dci_top on antennas 0 / 1 only), in remap_tm's thread-major order */
+/* cfg_dev_t::stat_tm from the RE map, the CRS values (h_crs) and the static-RE table (h_ctl): the
+ * packed IQ that kernel antenna `ant` (TM1: the one transform) carries at every RE that is not a
+ * data RE, in remap_tm's thread-major order.  A CRS RE holds port p's pilot on antenna p and 0 on
+ * the others, every port's in the single TM1 transform (pilots.c:43-168); a static RE holds the
+ * table's value for that antenna (generate_dci_top, the PBCH and the PHICH write antennas 0 / 1, the
+ * PSS and SSS every antenna).  k_modofdm ORs the plane over its data path. */
 static int build_stat_tm(oai4g_tx_config *cfg)
 {
   if (cfg->d_stat) hipFree(cfg->d_stat);
@@ -1184,7 +1187,7 @@ static int build_stat_tm(oai4g_tx_config *cfg)
           const uint32_t ci = (cd >> 9) & 7u, m = cd & 0xFFu, port = ((cd >> 8) & 1u) | (ci >= 4 ? 2u : 0u);
           if (!cfg->h_crs.empty() && (planes == 1 || ant == port)) v = cfg->h_crs[(sf * 6 + ci) * 200 + m];
         } else if ((cd & 0xE000u) == OAI4G_CTL_CODE) {
-          if (!cfg->h_ctl.empty() && ant < 2) v = cfg->h_ctl[(sl * 2 + ant) * N + pos];
+          if (!cfg->h_ctl.empty() && ant < cfg->ctl_planes) v = cfg->h_ctl[(sl * cfg->ctl_planes + ant) * N + pos];
         }
         st[(sl * planes + ant) * N + t * 16 + k] = v;
       }
@@ -1202,31 +1205,23 @@ static int upload_remap(oai4g_tx_config *cfg)
   if (cfg->d_remap) hipFree(cfg->d_remap);
   cfg->d_remap = nullptr;
   if (!cfg->h_remap.empty()) {
-    /* natural layout followed by the thread-major copy the fused kernel reads */
+    /* the natural layout k_modulate_bytes reads, then k_modofdm's thread-major copy */
     const size_t n = cfg->h_remap.size(), N = cfg->h.N, T = N >> 4;
-#if OAI4G_MOD_STAGE
-    /* k_modofdm stages 4 entries per quad of data REs below a sentinel at 3N/4 */
     for (int sf = 0; sf < 10; sf++)
       for (int l = 0; l < 14; l++)
-        if (cfg->h.symnre[sf][l] + 3u > (3u * N) / 4u) { set_err("too many data REs per symbol for the modulator"); return -1; }
-#endif
-    /* natural, thread-major, thread-major with the non-data codes on the zero sentinel */
-    std::vector<uint16_t> both(3 * n);
+        if (!oai4g_mod_nre_fits(cfg->h.symnre[sf][l], (uint32_t)N)) { set_err("too many data REs per symbol for the modulator"); return -1; }
+    std::vector<uint16_t> both(2 * n);
     std::copy(cfg->h_remap.begin(), cfg->h_remap.end(), both.begin());
-    /* staged entries: 2-byte QAM-table addresses, or (OAI4G_MOD_PRE, the 2048-point kernels) 8-byte
-     * (y0, d) pairs of two-antenna LARGE_CDD / 4-byte QAM words of TM1 */
-    const bool pre = OAI4G_MOD_STAGE && OAI4G_MOD_PRE && cfg->h.mimo_mode == OAI4G_LARGE_CDD && cfg->h.n_ant == 2 &&
-                     cfg->h.log2N == 11;
-    const bool pre1 = OAI4G_MOD_STAGE && OAI4G_MOD_PRE && cfg->h.mimo_mode == OAI4G_SISO && cfg->h.log2N == 11;
-    const uint32_t esh = pre ? 3u : pre1 ? 2u : 1u;
-    const uint16_t sentinel = (uint16_t)(((3u * (uint32_t)N) / 4u) << esh);   /* modofdm_geom::SENT, bytes */
+    /* k_modofdm's staged entries (oai4g_internal.h): 2-byte QAM-table addresses, or in the 2048-point
+     * kernels 8-byte (y0, d) pairs of two-antenna LARGE_CDD / 4-byte QAM words of TM1 */
+    const uint32_t esh = oai4g_mod_entry_shift(cfg->h.mimo_mode, cfg->h.n_ant, cfg->h.log2N);
+    const bool pre = esh == 3, pre1 = esh == 2;
+    const uint16_t sentinel = (uint16_t)(oai4g_mod_sentinel((uint32_t)N) << esh);
     for (size_t sl = 0; sl < n / N; sl++)
       for (size_t t = 0; t < T; t++)
         for (size_t k = 0; k < 16; k++) {
           uint16_t code = cfg->h_remap[sl * N + t + T * k];
-#if OAI4G_MOD_STAGE
-          /* data RE (idx | parity << 15, idx < 3N/4): the byte offset of its staged entry (2 idx, or 8 idx
-           * for the precoded pairs: < 8 * 1536 < 2^15) */
+          /* data RE (idx | parity << 15, idx below the sentinel): the byte offset of its staged entry */
           if (code < OAI4G_CTL_CODE) {
             /* the precoded pairs carry the CDD sign already: the staging step stores -d for an odd
              * data index.  The reference alternates the sign per RE within each RB
@@ -1237,23 +1232,13 @@ static int upload_remap(oai4g_tx_config *cfg)
             if (pre && par != (idx & 1u)) { set_err("LARGE_CDD: CDD parity differs from the RE index parity"); return -1; }
             code = (uint16_t)(((pre || pre1 ? 0u : par) << 15) | (idx << esh));
           }
-#endif
-          both[n + sl * N + t * 16 + k] = code;
-#if OAI4G_MOD_STAGE
-          both[2 * n + sl * N + t * 16 + k] = code < OAI4G_CTL_CODE ? code : sentinel;
-#else
-          /* the unstaged modulator tests code < OAI4G_CTL_CODE itself: keep the non-data codes */
-          (void)sentinel;
-          both[2 * n + sl * N + t * 16 + k] = code;
-#endif
+          both[n + sl * N + t * 16 + k] = code < OAI4G_CTL_CODE ? code : sentinel;
         }
     HCK(hipMalloc(&cfg->d_remap, both.size() * 2), -1);
     HCK(hipMemcpy(cfg->d_remap, both.data(), both.size() * 2, hipMemcpyHostToDevice), -1);
     cfg->h.remap_tm = cfg->d_remap + n;
-    cfg->h.remap_tm0 = cfg->d_remap + 2 * n;
   } else {
     cfg->h.remap_tm = nullptr;
-    cfg->h.remap_tm0 = nullptr;
   }
   if (build_stat_tm(cfg) != 0) return -1;
   cfg->h.remap = cfg->d_remap;
@@ -1297,12 +1282,7 @@ static int upload_cfg(oai4g_tx_config *cfg)
 {
   if (upload_remap(cfg) != 0) return -1;
   if (upload_gold(cfg) != 0) return -1;
-  if (!cfg->h_crs.empty()) {
-    HCK(hipMalloc(&cfg->d_crs, cfg->h_crs.size() * 4), -1);
-    HCK(hipMemcpy(cfg->d_crs, cfg->h_crs.data(), cfg->h_crs.size() * 4, hipMemcpyHostToDevice), -1);
-  }
-  cfg->h.crs_tab = cfg->d_crs;
-  cfg->h.with_crs = cfg->d_crs ? 1u : 0u;
+  cfg->h.with_crs = !cfg->h_crs.empty();
   cfg->h.mod_nosat = mod_nosat_ok(cfg->h, std::max(packed_iq_max(cfg->h_crs), cfg->ctl_vmax));
   cfg->h.n_cu = (uint32_t)g_n_cu;
   cfg->h.gold_x1 = g_gx1;
@@ -1323,14 +1303,10 @@ static void release_cfg(oai4g_tx_config *cfg)
   cfg->ev_done = nullptr;
   if (cfg->d) hipFree(cfg->d);
   if (cfg->d_remap) hipFree(cfg->d_remap);
-  if (cfg->d_crs) hipFree(cfg->d_crs);
-  if (cfg->d_ctl) hipFree(cfg->d_ctl);
   if (cfg->d_stat) hipFree(cfg->d_stat);
   if (cfg->d_gold) hipFree(cfg->d_gold);
   cfg->d_stat = nullptr;
   cfg->d_gold = nullptr;
-  cfg->d_crs = nullptr;
-  cfg->d_ctl = nullptr;
   cfg->d = nullptr;
   cfg->d_remap = nullptr;
 }
@@ -3051,8 +3027,8 @@ extern "C" uint8_t oai4g_generate_dci_top(uint8_t num_ue_spec_dci, uint8_t num_c
 /* Batched static REs: generate_dci_top's PCFICH + PDCCH (set_control) and the PSS / SSS, PBCH and
  * PHICH of the common signal procedures (set_common, phy_procedures_lte_eNb.c:1529-1760, 2585)
  * for every subframe index, computed on the GPU by the drop-in kernels into one subframe grid per
- * subframe index, gathered into a [10][14][2][N] table, marked in the RE map with OAI4G_CTL_CODE
- * and merged by the modulator. */
+ * subframe index, gathered into the host table h_ctl, marked in the RE map with OAI4G_CTL_CODE and
+ * folded into cfg_dev_t::stat_tm (upload_remap -> build_stat_tm), which the modulator merges. */
 static void sync_args(const oai4g_frame_parms_t *fp, int16_t amp, bool pss, uint16_t slot_offset, sync_args_t &a);
 static void pbch_args(const oai4g_frame_parms_t *fp, int amp, const uint8_t *pdu, uint8_t frame_mod4, pbch_args_t &a);
 static int phich_item(const oai4g_frame_parms_t *fp, uint8_t nseq, uint8_t ngroup, uint8_t HI, uint8_t subframe,
@@ -3066,16 +3042,14 @@ static int rebuild_static(oai4g_tx_config_t *cfg)
     if ((c & 0xE000u) == OAI4G_CTL_CODE) c = 0xFFFF;
   memset(cfg->h.ctlmask, 0, sizeof(cfg->h.ctlmask));
   cfg->h.ctl_on = 0;
-  if (cfg->d_ctl) hipFree(cfg->d_ctl);
-  cfg->d_ctl = nullptr;
-  cfg->h.ctl_tab = nullptr;
   cfg->h_ctl.clear();
   cfg->ctl_vmax = 0;
   const bool dci_on = (uint32_t)cfg->n_ue_dci + cfg->n_common_dci > 0;
   if (dci_on || cfg->common_on) {
     if (cfg->h_remap.empty()) { set_err("static REs: configuration has no RE map"); return -1; }
     const oai4g_frame_parms_t &fp = cfg->fp;
-    std::vector<uint32_t> tab((size_t)10 * 14 * 2 * N, 0);
+    const uint32_t n_tab = cfg->ctl_planes = n_ant > 2 ? n_ant : 2;
+    std::vector<uint32_t> tab((size_t)10 * 14 * n_tab * N, 0);
     const size_t gbytes = (size_t)14 * N * 4, gpad = (gbytes + 255) & ~(size_t)255;
     const size_t mcap = (size_t)4 * 1024;    /* >= 4 nquad REs for every geometry */
     const size_t accb = (size_t)4 * 4 * N * 4;   /* PHICH accumulators / PBCH encode grid (4 antennas x 4 symbols) */
@@ -3089,7 +3063,7 @@ static int rebuild_static(oai4g_tx_config_t *cfg)
     std::vector<uint32_t> g((size_t)14 * N);
     for (uint32_t sf = 0; sf < 10; sf++) {
       HCK(hipMemsetAsync(buf, 0, 4 * gpad, g_scr.s), -1);
-      uint32_t n_out = n_ant > 2 ? 2 : n_ant;          /* antennas whose values the table keeps */
+      uint32_t n_out = n_ant > 2 ? 2 : n_ant;          /* antennas that can carry a static RE */
       if (dci_on) {
         dci_args_t a;
         std::vector<uint32_t> map;
@@ -3165,14 +3139,14 @@ static int rebuild_static(oai4g_tx_config_t *cfg)
         }
         if (cm.pbch || cm.pss_sss) n_out = n_ant;
       }
-      for (uint32_t ant = 0; ant < n_out && ant < 2; ant++) {
+      for (uint32_t ant = 0; ant < n_out; ant++) {
         HCK(hipMemcpyAsync(g.data(), dg[ant], gbytes, hipMemcpyDeviceToHost, g_scr.s), -1);
         HCK(hipStreamSynchronize(g_scr.s), -1);
         for (uint32_t l = 0; l < nsymb; l++)
           for (uint32_t k = 0; k < N; k++) {
             const uint32_t v = g[(size_t)l * N + k];
             if (!v) continue;
-            tab[(((size_t)sf * 14 + l) * 2 + ant) * N + k] = v;
+            tab[(((size_t)sf * 14 + l) * n_tab + ant) * N + k] = v;
             uint16_t &code = cfg->h_remap[((size_t)sf * 14 + l) * N + k];
             if (code != 0xFFFF && code != OAI4G_CTL_CODE) {
               set_err("static REs: subframe %u symbol %u RE %u collides with a PDSCH / CRS RE", sf, l, k);
@@ -3183,12 +3157,9 @@ static int rebuild_static(oai4g_tx_config_t *cfg)
           }
       }
     }
-    HCK(hipMalloc(&cfg->d_ctl, tab.size() * 4), -1);
-    HCK(hipMemcpy(cfg->d_ctl, tab.data(), tab.size() * 4, hipMemcpyHostToDevice), -1);
-    cfg->h.ctl_tab = cfg->d_ctl;
     cfg->h.ctl_on = 1;
-    cfg->h_ctl = tab;
     cfg->ctl_vmax = packed_iq_max(tab);
+    cfg->h_ctl = std::move(tab);
   }
   cfg->h.mod_nosat = mod_nosat_ok(cfg->h, std::max(packed_iq_max(cfg->h_crs), cfg->ctl_vmax));
   if (upload_remap(cfg) != 0) return -1;

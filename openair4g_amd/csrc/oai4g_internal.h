@@ -24,15 +24,22 @@
 #define OAI4G_CRS_CODE 0xE000u               /* remap codes >= this (and != 0xFFFF) are CRS REs:
                                                 CRS_CODE | pilot entry i << 9 | port & 1 << 8 | m */
 #define OAI4G_CTL_CODE 0xC000u               /* remap code of a control-region RE (generate_dci_top) */
-#ifndef OAI4G_MOD_STAGE
-#define OAI4G_MOD_STAGE 1   /* k_modofdm stages a QAM-table address per data RE (remap_tm data codes
-                               2 idx | parity << 15); 0 = per-RE bit extraction from staged e words */
-#endif
-#ifndef OAI4G_MOD_PRE
-#define OAI4G_MOD_PRE 1     /* 2048-point LARGE_CDD (C3): the staging step also does the QAM lookups and the
-                               CDD sums of both codewords, one (y0, d) pair of words per data RE; the RE
-                               codes of that kernel are 8 idx | parity << 15 (oai4g_mod_pre) */
-#endif
+/* k_modofdm's staged layout, one definition for the kernel and for upload_remap, which writes the RE
+ * codes the kernel reads.  Per symbol the kernel stages one LDS entry per data RE, entry idx at byte
+ * idx << shift, below a zero sentinel entry at index 3N/4 that every non-data RE addresses; the
+ * thread-major RE code of data RE idx is that byte offset.  Entries are 2-byte QAM-table addresses
+ * (shift 1; bit 15 of the code carries the CDD parity), except in the 2048-point kernels that stage
+ * looked-up values: 4-byte QAM words for TM1 (shift 2) and 8-byte precoded (y0, d) pairs, sign
+ * included, for two-antenna LARGE_CDD (shift 3; 8 * 3N/4 < 2^15). */
+static constexpr uint32_t oai4g_mod_entry_shift(uint32_t mimo_mode, uint32_t n_ant, uint32_t log2N)
+{
+  return log2N != 11 ? 1u : mimo_mode == OAI4G_LARGE_CDD && n_ant == 2 ? 3u : mimo_mode == OAI4G_SISO ? 2u : 1u;
+}
+/* the bits of an RE code that address its entry */
+static constexpr uint32_t oai4g_mod_addr_mask(uint32_t shift) { return 0x7FFFu & ~((1u << shift) - 1u); }
+static constexpr uint32_t oai4g_mod_sentinel(uint32_t N) { return (3u * N) / 4u; }
+/* a symbol's data REs are staged in quads: the last quad must end below the sentinel */
+static constexpr bool oai4g_mod_nre_fits(uint32_t nre, uint32_t N) { return nre + 3u <= oai4g_mod_sentinel(N); }
 #define OAI4G_ENC_CRC_TABLE_WORDS (256 + 256) /* byte tables A/B (the combine multipliers stay in global memory;
                                                   slice-by-4 tables, 2048 words, cost one workgroup per CU: slower) */
 #define OAI4G_GOLD_LANES 256
@@ -160,29 +167,26 @@ struct cfg_dev_t {
   uint32_t symnre[10][14];      /* data REs in symbol l (32-bit: the modulator reads it with a scalar load) */
   uint32_t n_cu;                /* compute units of the device (persistent grids) */
   const uint16_t *remap;        /* [10][14][N] data-RE index | parity<<15; OAI4G_CRS_CODE | pilot
-                                   symbol<<9 | port<<8 | m for a CRS RE; 0xFFFF = none */
-  const uint16_t *remap_tm;     /* the same codes thread-major: per (sf, l), [t][n] = remap[t + (N/16) n],
-                                   so each modofdm thread fetches its 16 codes with two 16-B loads */
-  const uint16_t *remap_tm0;    /* remap_tm with every non-data code replaced by the staged zero
-                                   sentinel's byte offset (2 * 3N/4): the kernels without CRS or control
-                                   REs then address the sentinel without a clamp */
-  uint32_t with_crs;
+                                   symbol<<9 | port<<8 | m for a CRS RE; OAI4G_CTL_CODE for a static RE of
+                                   set_control / set_common; 0xFFFF = none (k_modulate_bytes reads it) */
+  const uint16_t *remap_tm;     /* k_modofdm's copy, thread-major: per (sf, l), [t][n] is the RE at t + (N/16) n,
+                                   so each thread fetches its 16 codes with two 16-B loads.  A data RE's code
+                                   is the byte offset of its staged entry (oai4g_mod_entry_shift; | parity<<15
+                                   with 2-byte entries), every other RE's the zero sentinel's */
+  uint32_t with_crs;            /* the grid carries CRS */
   uint32_t pilmask;             /* bit l: symbol l carries CRS (QAM levels scaled by rho_B) */
-  const uint32_t *crs_tab;      /* [10][6][200] packed CRS IQ of pilot symbol i (l = 0, 4, 7, 11; 1, 8 for
-                                   ports 2/3 with 4 TX antennas), index m */
-  const uint32_t *ctl_tab;      /* [10][14][2][N] packed IQ of the static REs (PCFICH, PDCCH, PHICH, PSS, SSS, PBCH; antennas
-                                   0 / 1) per subframe index; REs with code OAI4G_CTL_CODE take it */
-  uint32_t ctlmask[10];         /* bit l: symbol l of subframe index sf carries control REs */
-  uint32_t ctl_on;
+  uint32_t ctlmask[10];         /* bit l: symbol l of subframe index sf carries static REs of set_control /
+                                   set_common (PCFICH, PDCCH, PHICH, PSS, SSS, PBCH) */
+  uint32_t ctl_on;              /* any of them */
   const uint32_t *gold_tab;     /* [10][n_cw][ebits_words] scrambling words (dlsch_scrambling.c:51-97) per
                                    subframe index and codeword: c_init depends on nothing else */
   const uint32_t *gold_x1;      /* [256]     x1 state after 50+16l word steps */
   const uint32_t *gold_x2j;     /* [256][32] columns of M2^(50+16l) */
   const uint32_t *tw;           /* 2 x OAI4G_TW_TOTAL packed twiddles t, then (-t.im, t.re) */
   const uint32_t *stat_tm;      /* [10][14][stat_planes][N] thread-major like remap_tm: the packed IQ each
-                                   kernel antenna takes at a CRS or control RE, 0 elsewhere (CRS / control
-                                   configurations; k_modofdm ORs it over the data path, which reads the
-                                   zero sentinel there) */
+                                   kernel antenna takes at a CRS or static RE, 0 elsewhere (null without
+                                   either; k_modofdm ORs it over the data path, which reads the zero
+                                   sentinel there; built by build_stat_tm) */
   uint32_t stat_planes;         /* 1 (TM1: one transform) or the TX antennas */
   uint32_t pad2;
 };

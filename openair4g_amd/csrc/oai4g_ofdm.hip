@@ -94,9 +94,6 @@ static __device__ __forceinline__ twp_t tw_use(s16x2 t, uint32_t dep)
   return {t, u2c(tn)};
 }
 
-#ifndef OAI4G_MOD_W0
-#define OAI4G_MOD_W0 1   /* NS leaf: the W^0 products as x - (x > 0) (0: the dot2 form) */
-#endif
 /* x * conj(W^0) with W^0 = (32767, 0), packed like cmulc16: each lane floor(32767 x / 2^15), which is
  * x - 1 for x > 0 and x for x <= 0 when |x| < 2^15 (NS: no leaf value is -32768).  The lane's x > 0 is
  * the sign bit of -x; the 32-bit subtraction of the two 0/1 flags cannot borrow across lanes (the low
@@ -121,7 +118,7 @@ static __device__ __forceinline__ void idft16_reg(s16x2 *x, const twp_t *w16 /* 
   for (int k = 0; k < 4; k++) {
     /* NS: row 0 multiplies by W^0 = (32767, 0) (companion (0, 32767)), lane by lane floor(32767 x / 2^15)
      * = x - (x > 0) for |x| < 2^15 (w0mul_ns) */
-    const bool w0 = NS && OAI4G_MOD_W0 && k == 0;
+    const bool w0 = NS && k == 0;
     s16x2 b1 = w0 ? w0mul_ns(S[k][1]) : cmulc16u(S[k][1], w16[k1[k]]);
     s16x2 b2 = w0 ? w0mul_ns(S[k][2]) : cmulc16u(S[k][2], w16[k2[k]]);
     s16x2 b3 = w0 ? w0mul_ns(S[k][3]) : cmulc16u(S[k][3], w16[k3[k]]);
@@ -335,9 +332,61 @@ struct idft2048_tw_t {
 
 typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 
+/* --------------------------------------------------------------------------------------
+ * k_modofdm's build-time knobs, all in one place.  The numeric tunables are what an A/B varies
+ * (build.py --variant NAME -DOAI4G_MOD_GROUP=2 ...); the diagnostics cut the shipped path for
+ * timing only and give wrong output.  Everything else about the kernel is fixed: the settled
+ * questions are listed in DESIGN.md ("measured and settled").
+ * ------------------------------------------------------------------------------------ */
+#ifndef OAI4G_MODOFDM_WAVES
+/* waves per SIMD, 0 = per size: 2048 points 4 (round 5: SGPR twiddle operands, affine LDS addresses and
+ * companions rebuilt at use bring the kernel to <= 124 VGPRs, and the LDS alias to 19.0 KB per
+ * workgroup: 8 workgroups per CU); smaller transforms 3 (24 KB of LDS per workgroup) */
+#define OAI4G_MODOFDM_WAVES 0
+#endif
+#ifndef OAI4G_MOD_GROUP
+#define OAI4G_MOD_GROUP 4   /* REs whose LDS round trips are issued together (register budget) */
+#endif
+#ifndef OAI4G_MOD_GROUPZ
+#define OAI4G_MOD_GROUPZ 5   /* the same where the guard band is skipped (ZB), when it divides the REs left */
+#endif
+#ifndef OAI4G_MOD_PRIO
+/* wave priority 2 from the item's start to a point of the transform, 0 after it: the arbiter issues
+ * the latency-bound staging / RE lookups (LDS round trips, little VALU) and the passes that follow
+ * ahead of the other waves' pass-C VALU streams (profiles/mod_prio_r06.txt).  Lowered: 1 after the RE
+ * lookups (-1.2 %), 5 after the radix-16 leaf (-2.5 %), 6 after the pass-B loads, 7 at pass C, 9 after
+ * the first pass-C loads (kept: -4 %), 4 after the staging barrier (slower); 8 = 7 with the leaf and
+ * pass B at 1; 2: 1 + the pass-B / pass-C loads at 1; 3: 1 at priority 3 */
+#define OAI4G_MOD_PRIO 9
+#endif
+#ifndef OAI4G_DIAG_MODOFDM
+#define OAI4G_DIAG_MODOFDM 0   /* timing diagnostic only: 1 = no IQ stores */
+#endif
 #ifndef OAI4G_DIAG_NOSYNC
 #define OAI4G_DIAG_NOSYNC 0   /* timing diagnostic only: 1 = the idft2048 exchanges skip their barriers (wrong output) */
 #endif
+#ifndef OAI4G_DIAG_MODCUT
+#define OAI4G_DIAG_MODCUT 0   /* timing diagnostic only (wrong output): the unit stops after phase 1 = prologue
+                                 (QAM / RE map / precoding), 2 = leaf IDFT16, 3 = pass A + B (the 64- and 256-levels
+                                 and the E2 stores), 4 = pass C without its IQ stores; the cut values are kept
+                                 alive by empty asm operands (no instruction), so the earlier phases still run */
+#endif
+#ifndef OAI4G_DIAG_PASSA
+#define OAI4G_DIAG_PASSA 0   /* timing diagnostic only: 1 = pass-A stores at bank-distinct (wrong) words */
+#endif
+#ifndef OAI4G_DIAG_QTAB
+#define OAI4G_DIAG_QTAB 0    /* timing diagnostic only: 1 = QAM-table reads at lane-distinct banks (wrong values) */
+#endif
+/* settled and removed: a build that still passes one of these would silently get the default */
+#if defined(OAI4G_MOD_STAGE) || defined(OAI4G_MOD_PRE) || defined(OAI4G_MOD_ALIAS) || defined(OAI4G_MOD_STATTM) || \
+    defined(OAI4G_MOD_STATEARLY) || defined(OAI4G_MOD_ENDSYNC) || defined(OAI4G_MOD_ZBAND) || \
+    defined(OAI4G_MOD_ZB_OPAQUE) || defined(OAI4G_MOD_W0) || defined(OAI4G_PASSC_TWONCE)
+#error "retired k_modofdm switch: OAI4G_MOD_STAGE / _PRE / _ALIAS / _STATTM / _STATEARLY / _ENDSYNC / _ZBAND / _ZB_OPAQUE / _W0 and OAI4G_PASSC_TWONCE no longer exist (DESIGN.md, measured and settled)"
+#endif
+#if OAI4G_DIAG_MODOFDM != 0 && OAI4G_DIAG_MODOFDM != 1
+#error "OAI4G_DIAG_MODOFDM: only 1 (no IQ stores) remains"
+#endif
+
 #if OAI4G_DIAG_NOSYNC
 #define IDFT_SYNC() do { } while (0)
 #else
@@ -356,12 +405,6 @@ static __device__ __forceinline__ void idft2048_unit(uint32_t *lds, int t, bool 
 {
   constexpr int X1W = idft2048_tw_t::X1W, E2S = idft2048_tw_t::E2S;
   static_assert(7 * E2S + 256 <= X1W, "E2 must fit the exchange");
-#ifndef OAI4G_DIAG_MODCUT
-#define OAI4G_DIAG_MODCUT 0   /* timing diagnostic only (wrong output): the unit stops after phase 1 = prologue
-                                 (QAM / RE map / precoding), 2 = leaf IDFT16, 3 = pass A + B (the 64- and 256-levels
-                                 and the E2 stores), 4 = pass C without its IQ stores; the cut values are kept
-                                 alive by empty asm operands (no instruction), so the earlier phases still run */
-#endif
   auto sink = [&](const s16x2 (&v)[16]) {
 #pragma unroll
     for (int k = 0; k < 16; k++) asm volatile("" ::"v"(c2u(v[k])));
@@ -370,15 +413,6 @@ static __device__ __forceinline__ void idft2048_unit(uint32_t *lds, int t, bool 
   /* pass A: leaves */
   if (active) {
     prod(x);
-#ifndef OAI4G_MOD_PRIO
-/* wave priority 2 from the item's start to a point of the transform, 0 after it: the arbiter issues
- * the latency-bound staging / RE lookups (LDS round trips, little VALU) and the passes that follow
- * ahead of the other waves' pass-C VALU streams (profiles/mod_prio_r06.txt).  Lowered: 1 after the RE
- * lookups (-1.2 %), 5 after the radix-16 leaf (-2.5 %), 6 after the pass-B loads, 7 at pass C, 9 after
- * the first pass-C loads (kept: -4 %), 4 after the staging barrier (slower); 8 = 7 with the leaf and
- * pass B at 1; 2: 1 + the pass-B / pass-C loads at 1; 3: 1 at priority 3 */
-#define OAI4G_MOD_PRIO 9
-#endif
     if constexpr (OAI4G_MOD_PRIO >= 1 && OAI4G_MOD_PRIO <= 3) __builtin_amdgcn_s_setprio(0);
     if constexpr (OAI4G_MOD_PRIO == 8) __builtin_amdgcn_s_setprio(1);
     if constexpr (OAI4G_DIAG_MODCUT == 1) {
@@ -399,9 +433,6 @@ static __device__ __forceinline__ void idft2048_unit(uint32_t *lds, int t, bool 
   if constexpr (OAI4G_DIAG_MODCUT == 1 || OAI4G_DIAG_MODCUT == 2) return;
   if constexpr (PSYNC) IDFT_SYNC();
   if (active) {
-#ifndef OAI4G_DIAG_PASSA
-#define OAI4G_DIAG_PASSA 0   /* timing diagnostic only: 1 = pass-A stores at bank-distinct (wrong) words */
-#endif
     const uint32_t wo = OAI4G_DIAG_PASSA ? (uint32_t)t : 2u * (t & 31) + ((t >> 5) & 1) + 64u * (t >> 6);
 #pragma unroll
     for (int a = 0; a < NA; a++) {
@@ -473,23 +504,16 @@ static __device__ __forceinline__ void idft2048_unit(uint32_t *lds, int t, bool 
   if constexpr (OAI4G_MOD_PRIO == 2) __builtin_amdgcn_s_setprio(1);
   if constexpr (OAI4G_MOD_PRIO == 7 || OAI4G_MOD_PRIO == 8) __builtin_amdgcn_s_setprio(0);
   if (active) {
-#ifndef OAI4G_PASSC_TWONCE
-#define OAI4G_PASSC_TWONCE 1   /* 1: the pass-C companions are built once for both antennas (0: per antenna) */
-#endif
-    twp_t wc[2][3], wc2[2][4];
-    auto build_wc = [&]() {
+    twp_t wc[2][3], wc2[2][4];   /* the pass-C companions, built once for both antennas */
 #pragma unroll
-      for (int h = 0; h < 2; h++) {
+    for (int h = 0; h < 2; h++) {
 #pragma unroll
-        for (int r = 0; r < 3; r++) wc[h][r] = tw_use(tw.c1024[h][r], dep);
+      for (int r = 0; r < 3; r++) wc[h][r] = tw_use(tw.c1024[h][r], dep);
 #pragma unroll
-        for (int m1 = 0; m1 < 4; m1++) wc2[h][m1] = tw_use(tw.c2048[h + 2 * m1], dep);
-      }
-    };
-    if (OAI4G_PASSC_TWONCE) build_wc();
+      for (int m1 = 0; m1 < 4; m1++) wc2[h][m1] = tw_use(tw.c2048[h + 2 * m1], dep);
+    }
 #pragma unroll
     for (int a = 0; a < NA; a++) {
-      if (!OAI4G_PASSC_TWONCE) build_wc();
       s16x2 v[2][8];   /* [h][j] */
 #pragma unroll
       for (int jj = 0; jj < 8; jj++) {
@@ -806,16 +830,18 @@ static __device__ __forceinline__ s16x2 half_signed(s16x2 x, bool neg)
 template <int LOG2N>
 struct modofdm_geom {
   static constexpr int N = 1 << LOG2N, T = N >> 4, UNITS = 128 / T, LDSW = idft_sel<LOG2N>::XW;
-  /* staged e-bit words per codeword: up to 12 N_RB <= 0.71 N data REs (15 PRB in 256) of 6 bits */
-  static constexpr int EW = (6 * ((N * 3) / 4)) / 32 + 4;
-  /* OAI4G_MOD_STAGE: per codeword one 16-bit QAM-table address per data RE (12 N_RB + 3 <= 3N/4
-   * entries, host-checked), two sentinel entries at SENT; quad q = 4 REs, QPT quads per thread */
-  static constexpr int SENT = (N * 3) / 4, SW = SENT + 4, QPT = 3, QROW = 64;
+  /* staged entries per codeword: one per data RE (at most 12 N_RB, rounded up to quads: the host checks
+   * oai4g_mod_nre_fits), then the sentinel entries at SENT; quad q = 4 REs, QPT quads per thread */
+  static constexpr int SENT = oai4g_mod_sentinel(N), SW = SENT + 4, QPT = 3, QROW = 64;
   /* guard band: leaf inputs t + T n with n in [ZLO, ZHI] fall between subcarrier 6 N_RB_DL and
    * first_carrier_offset = N - 6 N_RB_DL for every thread t (N_RB_DL 6/25/50/100: n = 5..10;
    * 15: n = 6..9; host-checked), where the reference's grid is zero */
   static constexpr int ZLO = LOG2N == 8 ? 6 : 5, ZHI = LOG2N == 8 ? 9 : 10;
 };
+/* the guard-band leaf inputs are the constant 0: no code, LDS or QAM work for them.  In every kernel
+ * but the plain two-antenna LARGE_CDD one (C3 without CRS / control: measured 1.7 % slower with it,
+ * while the full grid gains 0.9 % and C4 4-6 %, profiles/mod_ab_r03_zband.txt) */
+static constexpr bool modofdm_zband(int MODE, bool CRS) { return CRS || MODE != 2; }
 
 /* 4 bytes from any byte address of global memory (unaligned dword load) */
 typedef uint32_t __attribute__((aligned(1))) u32_a1_t;
@@ -824,36 +850,11 @@ static __device__ __forceinline__ uint32_t ld_u32_any(const uint8_t *p)
   return *(const __attribute__((address_space(1))) u32_a1_t *)p;
 }
 
-#ifndef OAI4G_DIAG_MODOFDM
-#define OAI4G_DIAG_MODOFDM 0   /* timing diagnostics only: 1 = no IQ stores, 2 = no e-bit staging, 3 = no QAM lookups,
-                                  4 = QAM table reads without bank conflicts */
-#endif
-#ifndef OAI4G_MOD_ENDSYNC
-/* the barrier at the end of an item is not needed: the next item's LDS writes (staging, then the
- * leaves) are separated from this item's last reads (prologue, pass C) by the staging barrier */
-#define OAI4G_MOD_ENDSYNC 0
-#endif
-#ifndef OAI4G_MOD_ZBAND
-/* the guard-band leaf inputs are the constant 0: no code, LDS or QAM work for them.  1 = in every
- * kernel but the plain LARGE_CDD one (C3 without CRS / control: measured 1.7 % slower with it, while
- * the full grid gains 0.9 % and C4 4-6 %, profiles/mod_ab_r03_zband.txt); 2 = everywhere; 0 = off */
-#define OAI4G_MOD_ZBAND 1
-#endif
-#ifndef OAI4G_MODOFDM_WAVES
-/* waves per SIMD: 2048 points 4 (round 5: SGPR twiddle operands, affine LDS addresses and
- * companions rebuilt at use bring the kernel to <= 124 VGPRs, and the LDS alias to 19.0 KB per
- * workgroup: 8 workgroups per CU); smaller transforms 3 (24 KB of LDS per workgroup) */
-#define OAI4G_MODOFDM_WAVES 0
-#endif
-#ifndef OAI4G_MOD_ALIAS
-/* 2048-point symbols: the staged QAM addresses share LDS with the IDFT exchange (two more barriers
- * per item), 19.0 KB per workgroup instead of 25.0 KB */
-#define OAI4G_MOD_ALIAS 1
-#endif
 #define MODOFDM_WAVES_OF(L) (OAI4G_MODOFDM_WAVES > 0 ? OAI4G_MODOFDM_WAVES : ((L) == 11 ? 4 : 3))
 #define MODOFDM_ATTR __attribute__((amdgpu_waves_per_eu(MODOFDM_WAVES_OF(LOG2N))))
 /* MODE: 0 = TM1 (one transform stored to every antenna), 1 = ALAMOUTI, 2 = LARGE_CDD, 3 = 4-port
  * LARGE_CDD (C4: two items per symbol, each transforming one antenna pair) */
+/* CRS: the grid has static REs (CRS, or the control / common signals of set_control / set_common) */
 /* NS: the fused ibfly4 + shr1 levels (ibfly4_shr1_ns); the host sets it only for configurations whose
  * range check passed (mod_nosat_ok) */
 template <int LOG2N, int MODE, bool CRS, bool ECP, bool NS = false>
@@ -862,50 +863,44 @@ __global__ void __launch_bounds__(128) MODOFDM_ATTR k_modofdm(const cfg_dev_t *_
                                                  uint32_t sf0)
 {
   using G = modofdm_geom<LOG2N>;
-  constexpr int N = G::N, T = G::T, UNITS = G::UNITS, LDSW = G::LDSW, EW = G::EW;
-  (void)EW;
+  constexpr int N = G::N, T = G::T, UNITS = G::UNITS, LDSW = G::LDSW;
   constexpr int NA = MODE == 0 ? 1 : 2;
   constexpr bool CW2 = MODE == 2 || MODE == 3;
   constexpr uint32_t IPS = MODE == 3 ? 2u : 1u;   /* items per (subframe, symbol) */
   __shared__ __attribute__((aligned(16))) uint32_t lds_data[UNITS * NA * LDSW];
-#ifndef OAI4G_MOD_STATTM
-#define OAI4G_MOD_STATTM 1   /* CRS / control kernels (staged builds): the static REs come from cfg stat_tm, ORed
-                                over a data path that reads the zero sentinel there (0: per-RE code tests) */
-#endif
-  constexpr bool STATTM = OAI4G_MOD_STATTM && OAI4G_MOD_STAGE && CRS;
-#ifndef OAI4G_MOD_STATEARLY
-#define OAI4G_MOD_STATEARLY 1   /* STATTM: the static words are read before the staging barrier (0: in the prologue) */
-#endif
-  /* not in the two-antenna 2048-point kernels: 32 more live VGPRs there spill (20-100 bytes per lane) */
-  constexpr bool SEARLY = STATTM && OAI4G_MOD_STATEARLY && (NA == 1 || LOG2N < 11);
-#if OAI4G_MOD_STAGE
+  /* a static symbol's words (cfg stat_tm) are read before the staging barrier, not in the prologue.
+   * Not in the two-antenna 2048-point kernels: 32 more live VGPRs there spill (20-100 bytes per lane) */
+  constexpr bool SEARLY = CRS && (NA == 1 || LOG2N < 11);
   /* per codeword, the qtab byte address of every data RE's QAM word: entries 4q..4q+3 staged from
    * quad q's 4 Qm bits; entries SENT, SENT + 1 address the zero word that non-data REs read */
   constexpr int SW = G::SW, SENT = G::SENT, QPT = G::QPT, QROW = G::QROW;
   constexpr uint32_t QZERO = 4u * 4u * QROW;     /* byte address of the zero word behind the 4 rows */
-  constexpr bool ALIAS = OAI4G_MOD_ALIAS && LOG2N == 11;
+  /* 2048-point symbols: the staged entries share LDS with the IDFT exchange (two more barriers per
+   * item), 19.0 KB per workgroup instead of 25.0 KB; smaller transforms keep them in lds_s_own */
+  constexpr bool ALIAS = LOG2N == 11;
   static_assert(!ALIAS || (UNITS == 1 && 2 * SW <= 2 * NA * LDSW), "staged addresses must fit the exchange");
   __shared__ __attribute__((aligned(16))) uint16_t lds_s_own[ALIAS ? 1 : UNITS][2][SW];
   uint16_t(*lds_s)[2][SW] = ALIAS ? (uint16_t(*)[2][SW])lds_data : lds_s_own;
   /* row cw * 2 + pilot symbol: 64 packed IQ words, 256 bytes, so a row base ORs into an entry's byte
    * offset (bits 8-9 against 2-7); then the zero word */
   __shared__ uint32_t qtab[4 * QROW + 1];
-  /* OAI4G_MOD_PRE (C3's kernel): the staging step looks the QAM words of both codewords up and stores
+  /* bytes per staged entry as a shift, and the bits of an RE code that address one: the layout
+   * upload_remap wrote the codes for (oai4g_internal.h) */
+  constexpr uint32_t ESH = oai4g_mod_entry_shift(MODE == 0 ? OAI4G_SISO : MODE == 1 ? OAI4G_ALAMOUTI : OAI4G_LARGE_CDD,
+                                                 MODE == 3 ? 4 : 2, LOG2N);
+  constexpr uint32_t EMASK = oai4g_mod_addr_mask(ESH);
+  /* PRE (C3's kernel): the staging step looks the QAM words of both codewords up and stores
    * their CDD sums per data RE, (y0, d) = ((x0 + x1) >> 1, (x0 - x1) >> 1) lane by lane: the RE step is
    * then one 8-byte LDS read and the sign of y1 = s d, instead of two dependent LDS round trips per
    * codeword and the sums */
-  constexpr bool PRE = OAI4G_MOD_PRE && MODE == 2 && ALIAS;
-  static_assert(!PRE || SW * 8 <= NA * LDSW * 4, "the precoded pairs must fit the exchange");
+  constexpr bool PRE = ESH == 3;
+  static_assert(!PRE || (MODE == 2 && ALIAS && SW * 8 <= NA * LDSW * 4), "the precoded pairs must fit the exchange");
   u32x2_t *lds_p = (u32x2_t *)lds_data;
   /* the same for TM1 (one codeword, one transform): the staging step stores each data RE's QAM word,
-   * the RE step reads it with one 4-byte LDS read (codes 4 idx) */
-  constexpr bool PRE1 = OAI4G_MOD_PRE && MODE == 0 && ALIAS;
-  static_assert(!PRE1 || SW * 4 <= NA * LDSW * 4, "the staged QAM words must fit the exchange");
+   * the RE step reads it with one 4-byte LDS read */
+  constexpr bool PRE1 = ESH == 2;
+  static_assert(!PRE1 || (MODE == 0 && ALIAS && SW * 4 <= NA * LDSW * 4), "the staged QAM words must fit the exchange");
   uint32_t *lds_w = (uint32_t *)lds_data;
-#else
-  __shared__ uint32_t lds_e[UNITS][2][EW];
-  __shared__ uint32_t qtab[2][2][64];          /* [cw][pilot symbol][Qm bits] -> packed IQ */
-#endif
   const int unit = threadIdx.x / T, t = threadIdx.x % T;
   typename idft_sel<LOG2N>::tw_t twr;
   twr.load(c->tw, t);
@@ -914,7 +909,6 @@ __global__ void __launch_bounds__(128) MODOFDM_ATTR k_modofdm(const cfg_dev_t *_
   const uint32_t n_ant = c->n_ant;
   constexpr uint32_t nsymb = ECP ? 12u : 14u;
   constexpr uint32_t sps = ECP ? 6 : 7;
-#if OAI4G_MOD_STAGE
   for (uint32_t i = threadIdx.x; i < 4 * QROW + 1; i += blockDim.x) {
     const uint32_t row = i / QROW, bits = i - row * QROW, cw = row >> 1, pil = row & 1;
     uint32_t v = 0;
@@ -931,41 +925,20 @@ __global__ void __launch_bounds__(128) MODOFDM_ATTR k_modofdm(const cfg_dev_t *_
   }
   if (!ALIAS)
     for (uint32_t i = threadIdx.x; i < UNITS * 4; i += blockDim.x) lds_s[i >> 2][(i >> 1) & 1][SENT + (i & 1)] = QZERO;
-#else
-  for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x) {
-    const uint32_t cw = i >> 7, pil = (i >> 6) & 1, bits = i & 63;
-    if constexpr (MODE == 1) {          /* one codeword: [0] = TA, [1] = TB */
-      const cw_dev_t &w = c->cw[0];
-      qtab[cw][pil][bits] = c2u(cw ? alm_tb(bits, w, pil) : alm_ta(bits, w, pil));
-    } else {
-      const cw_dev_t &w = c->cw[cw];
-      qtab[cw][pil][bits] = c2u(qam_map(bits, w.Qm, pil ? w.qam_b : w.qam_a, pil ? w.qpsk_b : w.qpsk_a));
-    }
-  }
-#endif
   const uint32_t Qm0 = c->cw[0].Qm, Qm1 = c->cw[1].Qm;
   const uint32_t mask0 = (1u << Qm0) - 1u, mask1 = (1u << Qm1) - 1u;
   /* 4 Qm t: the lane part of a quad's bit offset (loop-invariant) */
   const uint32_t qt0 = 4u * Qm0 * (uint32_t)t, qt1 = 4u * Qm1 * (uint32_t)t;
-  (void)qt0;
-  (void)qt1;
   __syncthreads();
 
-  /* software pipeline: the RE codes and e-bit words of a unit's next item are loaded while the
+  /* software pipeline: the RE codes and e-bit bytes of a unit's next item are loaded while the
    * current item is transformed, so no item starts with an exposed HBM round trip */
-#if !OAI4G_MOD_STAGE
-  constexpr int EPT = (EW + T - 1) / T;          /* staged e words per thread and codeword */
-#endif
   /* wave-uniform by construction: an SGPR, so the loop control never waits on the vector load of
    * the dispatch packet (a VGPR copy made every iteration wait for all the IQ stores in flight) */
   const int stride = __builtin_amdgcn_readfirstlane(gridDim.x * UNITS);
   struct pf_t {
     u32x4_t ra, rb;
-#if OAI4G_MOD_STAGE
     uint32_t x0[QPT], x1[QPT];   /* quad q = t + k T: the 4 bytes holding its 4 Qm bits */
-#else
-    uint32_t e0[EPT], e1[EPT];
-#endif
   } pf;
   /* the configuration through the constant address space: its uniform fields become scalar loads
    * (lgkmcnt) instead of vector loads the IQ stores would otherwise order behind (shared vmcnt) */
@@ -984,10 +957,9 @@ __global__ void __launch_bounds__(128) MODOFDM_ATTR k_modofdm(const cfg_dev_t *_
     const uint32_t sfi = (cc->first_sf + (sf0 + sf) * cc->sf_step) % 10;
     const uint32_t nre_u = cc->symnre[sfi][l], re0 = cc->symbase[sfi][l];   /* uniform: scalar loads */
     const uint32_t nre = act ? nre_u : 0u;
-    const gu128_t *rsrc = (const gu128_t *)((CRS && !STATTM ? cc->remap_tm : cc->remap_tm0) + ((size_t)sfi * 14 + l) * N + (size_t)t * 16);
+    const gu128_t *rsrc = (const gu128_t *)(cc->remap_tm + ((size_t)sfi * 14 + l) * N + (size_t)t * 16);
     pf.ra = rsrc[0];
     pf.rb = rsrc[1];
-#if OAI4G_MOD_STAGE
     if (act && nre) {
       const uint8_t *esf = (const uint8_t *)(ebits + (size_t)(sf * cc->n_cw) * cc->ebits_words);
       const uint32_t nq = (nre + 3) >> 2;
@@ -1001,21 +973,6 @@ __global__ void __launch_bounds__(128) MODOFDM_ATTR k_modofdm(const cfg_dev_t *_
           pf.x1[k] = ld_u32_any(esf + (size_t)4 * cc->ebits_words + ((b1 + min(qt1 + (uint32_t)(4 * T * k) * Qm1, lim1)) >> 3));
       }
     }
-#else
-    if (act && nre && OAI4G_DIAG_MODOFDM != 2) {
-      gu32_t *esf = (gu32_t *)(ebits + (size_t)(sf * cc->n_cw) * cc->ebits_words);
-      const uint32_t wlo0 = (re0 * Qm0) >> 5, cnt0 = min((uint32_t)EW, (((re0 + nre) * Qm0 + 31) >> 5) - wlo0 + 1);
-#pragma unroll
-      for (int k = 0; k < EPT; k++)
-        if (t + k * T < (int)cnt0) pf.e0[k] = esf[wlo0 + t + k * T];
-      if constexpr (CW2) {
-        const uint32_t wlo1 = (re0 * Qm1) >> 5, cnt1 = min((uint32_t)EW, (((re0 + nre) * Qm1 + 31) >> 5) - wlo1 + 1);
-#pragma unroll
-        for (int k = 0; k < EPT; k++)
-          if (t + k * T < (int)cnt1) pf.e1[k] = esf[cc->ebits_words + wlo1 + t + k * T];
-      }
-    }
-#endif
   };
   fetch(blockIdx.x * UNITS);
   /* no vector load crosses into the item loop: at the loop header the compiler merges the entry
@@ -1057,7 +1014,6 @@ __global__ void __launch_bounds__(128) MODOFDM_ATTR k_modofdm(const cfg_dev_t *_
     /* this thread's 16 RE codes (thread-major copy, prefetched) */
     const uint32_t rw[8] = {pf.ra.x, pf.ra.y, pf.ra.z, pf.ra.w, pf.rb.x, pf.rb.y, pf.rb.z, pf.rb.w};
     if constexpr (OAI4G_MOD_PRIO >= 1) __builtin_amdgcn_s_setprio(OAI4G_MOD_PRIO == 3 ? 3 : 2);
-#if OAI4G_MOD_STAGE
     /* stage, per codeword, the QAM-table address of every data RE of this symbol: quad q's 4 Qm
      * bits from its prefetched bytes -> 4 entries (ALAMOUTI: even entries TA rows, odd TB rows) */
     if (PRE) {
@@ -1134,23 +1090,7 @@ __global__ void __launch_bounds__(128) MODOFDM_ATTR k_modofdm(const cfg_dev_t *_
         }
       }
     }
-#else
-    /* stage this symbol's e bits of each codeword (prefetched words, coalesced) */
-    const uint32_t wlo0 = (re0 * Qm0) >> 5, wlo1 = (re0 * Qm1) >> 5;
-    if (active && nre && OAI4G_DIAG_MODOFDM != 2) {
-      const uint32_t cnt0 = min((uint32_t)EW, (((re0 + nre) * Qm0 + 31) >> 5) - wlo0 + 1);
-#pragma unroll
-      for (int k = 0; k < EPT; k++)
-        if (t + k * T < (int)cnt0) lds_e[unit][0][t + k * T] = pf.e0[k];
-      if constexpr (CW2) {
-        const uint32_t cnt1 = min((uint32_t)EW, (((re0 + nre) * Qm1 + 31) >> 5) - wlo1 + 1);
-#pragma unroll
-        for (int k = 0; k < EPT; k++)
-          if (t + k * T < (int)cnt1) lds_e[unit][1][t + k * T] = pf.e1[k];
-      }
-    }
-#endif
-    /* a CRS / control symbol's static words (STATTM) are read here, ahead of the staging barrier: their L2
+    /* a CRS / control symbol's static words are read here, ahead of the staging barrier: their L2
      * round trip overlaps the barrier and the next item's prefetch instead of stalling the prologue */
     u32x4_t stw[NA][4];
     if constexpr (SEARLY) {
@@ -1169,60 +1109,34 @@ __global__ void __launch_bounds__(128) MODOFDM_ATTR k_modofdm(const cfg_dev_t *_
     if constexpr (OAI4G_MOD_PRIO == 4) __builtin_amdgcn_s_setprio(0);
     fetch(base + stride);
 
-    gu32_t *crs_tab = (gu32_t *)cc->crs_tab;
     const bool crs = CRS && stat_sym;
-    gu32_t *ctl_tab = (gu32_t *)cc->ctl_tab;
-#if OAI4G_MOD_STAGE
     const char *sb0 = (const char *)lds_s[unit][0], *sb1 = (const char *)lds_s[unit][1], *qb = (const char *)qtab;
-#else
-    const uint32_t *e0 = lds_e[unit][0], *e1 = lds_e[unit][1];
-    const uint32_t *q0 = qtab[0][pil], *q1 = qtab[1][pil];
-    /* bit position of data RE idx within the staged words: idx * Qm + (re0 * Qm - 32 wlo) */
-    const uint32_t b0 = re0 * Qm0 - 32 * wlo0, b1 = re0 * Qm1 - 32 * wlo1;
-#endif
-#if OAI4G_MOD_STAGE
-    constexpr bool PSYNC = ALIAS;
-#else
-    constexpr bool PSYNC = false;
-#endif
+    constexpr bool PSYNC = ALIAS;   /* the prologue reads LDS the exchange aliases */
     idft_any2<LOG2N, NA, PSYNC, NS>(
         lds_data + unit * NA * LDSW, t, active, twr,
         [&](s16x2 (*x)[16]) {
           /* branch-free and staged in groups of GR REs so each LDS round trip is issued for the
-           * whole group before the first wait: codes -> bit offsets -> e words -> QAM words.  An RE
-           * outside the allocation reads data RE 0 (inside the staged words), zeroed by the select */
-#ifndef OAI4G_MOD_GROUP
-#define OAI4G_MOD_GROUP 4   /* REs whose LDS round trips are issued together (register budget) */
-#endif
+           * whole group before the first wait: codes -> staged entries -> QAM words.  A non-data RE's
+           * code addresses the zero sentinel */
           constexpr int GR = OAI4G_MOD_GROUP;
-#if OAI4G_MOD_STAGE
-          /* remap_tm data codes are 2 idx | parity << 15 (ALAMOUTI: 2 (2i + role)): the byte
-           * offset of entry idx; any non-data code (>= 0xC000) clamps to the zero sentinel (in
-           * remap_tm0 it already is the sentinel) */
-          constexpr uint32_t AM = MODE == 1 ? 0x7FFCu : 0x7FFEu;
-          constexpr bool ZB = OAI4G_MOD_ZBAND == 2 || (OAI4G_MOD_ZBAND == 1 && (CRS || MODE != 2));
+          /* a data RE's code is the byte offset of its staged entry, idx << ESH (2-byte entries: | parity
+           * << 15; ALAMOUTI: idx = 2i + role, and the pair's TA / TB entries are read from 4i) */
+          constexpr uint32_t AM = MODE == 1 ? EMASK & ~2u : EMASK;
+          constexpr bool ZB = modofdm_zband(MODE, CRS);
           auto zb = [&](int n) { return ZB && n >= G::ZLO && n <= G::ZHI; };   /* constant after unrolling */
           /* the NZ leaf inputs outside the guard band, visited in groups of GZ (the i-th is act(i)) */
           constexpr int NZ = ZB ? 16 - (G::ZHI - G::ZLO + 1) : 16;
-#ifndef OAI4G_MOD_GROUPZ
-#define OAI4G_MOD_GROUPZ 5
-#endif
           constexpr int GZ = ZB ? (NZ % OAI4G_MOD_GROUPZ == 0 ? OAI4G_MOD_GROUPZ : 4) : GR;
           auto act = [&](int i) { return (ZB && i >= G::ZLO) ? i + (G::ZHI - G::ZLO + 1) : i; };
-#ifndef OAI4G_MOD_ZB_OPAQUE
-#define OAI4G_MOD_ZB_OPAQUE 0   /* 1: the guard-band zeros come from a v_mov the compiler cannot fold (A/B of the leaf folding) */
-#endif
 #pragma unroll
           for (int n = 0; n < 16; n++)
             if (zb(n)) {
-              uint32_t z = 0;
-              if (OAI4G_MOD_ZB_OPAQUE) asm("v_mov_b32 %0, 0" : "=v"(z));
 #pragma unroll
-              for (int a = 0; a < NA; a++) x[a][n] = u2c(z);
+              for (int a = 0; a < NA; a++) x[a][n] = (s16x2){0, 0};
             }
           if constexpr (PRE) {
-            /* one 8-byte read per RE: the pair staged for its data index, CDD sign included (codes
-             * 8 idx; every non-data code addresses the zero pair, clamped when CRS / control codes occur) */
+            /* one 8-byte read per RE: the pair staged for its data index, CDD sign included (every
+             * non-data code addresses the zero pair) */
             const char *pb = (const char *)lds_p;
 #pragma unroll
             for (int g = 0; g < NZ; g += GZ) {
@@ -1232,8 +1146,7 @@ __global__ void __launch_bounds__(128) MODOFDM_ATTR k_modofdm(const cfg_dev_t *_
               for (int n = 0; n < GZ; n++) {
                 const int i = act(g + n);
                 code[n] = (rw[i >> 1] >> (16 * (i & 1))) & 0xFFFFu;
-                const uint32_t a = CRS && !STATTM ? min(code[n] & 0x7FF8u, 8u * SENT) : code[n] & 0x7FF8u;
-                v[n] = *(const u32x2_t *)(pb + a);
+                v[n] = *(const u32x2_t *)(pb + (code[n] & EMASK));
               }
 #pragma unroll
               for (int n = 0; n < GZ; n++) {
@@ -1243,7 +1156,7 @@ __global__ void __launch_bounds__(128) MODOFDM_ATTR k_modofdm(const cfg_dev_t *_
               }
             }
           } else if constexpr (PRE1) {
-            /* one 4-byte read per RE: the QAM word staged for its data index (codes 4 idx) */
+            /* one 4-byte read per RE: the QAM word staged for its data index */
             const char *pb = (const char *)lds_w;
 #pragma unroll
             for (int g = 0; g < NZ; g += GZ) {
@@ -1252,8 +1165,7 @@ __global__ void __launch_bounds__(128) MODOFDM_ATTR k_modofdm(const cfg_dev_t *_
               for (int n = 0; n < GZ; n++) {
                 const int i = act(g + n);
                 const uint32_t code = (rw[i >> 1] >> (16 * (i & 1))) & 0xFFFFu;
-                const uint32_t a = CRS && !STATTM ? min(code & 0x7FFCu, 4u * SENT) : code & 0x7FFCu;
-                v[n] = *(const uint32_t *)(pb + a);
+                v[n] = *(const uint32_t *)(pb + (code & EMASK));
               }
 #pragma unroll
               for (int n = 0; n < GZ; n++) x[0][act(g + n)] = u2c(v[n]);
@@ -1266,15 +1178,11 @@ __global__ void __launch_bounds__(128) MODOFDM_ATTR k_modofdm(const cfg_dev_t *_
             for (int n = 0; n < GZ; n++) {
               const int i = act(g + n);
               code[n] = (rw[i >> 1] >> (16 * (i & 1))) & 0xFFFFu;
-              /* without CRS / control REs every non-data code is already the sentinel (remap_tm0) */
-              const uint32_t a = CRS && !STATTM ? min(code[n] & AM, 2u * SENT) : code[n] & AM;
+              const uint32_t a = code[n] & AM;
               v0[n] = *(const uint16_t *)(sb0 + a);
               if constexpr (MODE == 1) v1[n] = *(const uint16_t *)(sb0 + a + 2);
               if constexpr (CW2) v1[n] = *(const uint16_t *)(sb1 + a);
             }
-#ifndef OAI4G_DIAG_QTAB
-#define OAI4G_DIAG_QTAB 0    /* timing diagnostic only: 1 = QAM-table reads at lane-distinct banks (wrong values) */
-#endif
 #if OAI4G_DIAG_QTAB
             const uint32_t qkeep = cc->with_crs ? 0xFFFFFFFFu : 0u, qlane = ((uint32_t)threadIdx.x & 31u) << 2;
 #define QADDR(x) (((x) & qkeep) | (qlane & ~qkeep))
@@ -1307,77 +1215,9 @@ __global__ void __launch_bounds__(128) MODOFDM_ATTR k_modofdm(const cfg_dev_t *_
               }
             }
           }
-#else
-#if OAI4G_DIAG_MODOFDM == 3
-#pragma unroll
-          for (int n = 0; n < 16; n++)
-#pragma unroll
-            for (int a = 0; a < NA; a++) x[a][n] = u2c(rw[n >> 1] + (uint32_t)(a + n));
-          if (0)
-#endif
-#pragma unroll
-          for (int g = 0; g < 16; g += GR) {
-            uint32_t code[GR], p[GR], lo[GR], hi[GR], v0[GR], v1[GR];
-            /* ALAMOUTI codes are 2i | role: both symbols of pair i start at bit 2i Qm */
-            constexpr uint32_t IDXM = MODE == 1 ? 0x7FFEu : 0x7FFFu;
-#pragma unroll
-            for (int n = 0; n < GR; n++) {
-              code[n] = (rw[(g + n) >> 1] >> (16 * ((g + n) & 1))) & 0xFFFFu;
-              p[n] = __umul24(code[n] < OAI4G_CTL_CODE ? (code[n] & IDXM) : 0u, Qm0) + b0;
-            }
-#pragma unroll
-            for (int n = 0; n < GR; n++) { lo[n] = e0[p[n] >> 5]; hi[n] = e0[(p[n] >> 5) + 1]; }
-#if OAI4G_DIAG_MODOFDM == 4   /* timing diagnostic: QAM table reads at lane-unique words (no bank conflicts) */
-            const uint32_t dkeep = cc->with_crs ? 0xFFFFFFFFu : 0u, dlane = (uint32_t)threadIdx.x & 31u;
-#define QIDX(x) (((x) & dkeep) | (dlane & ~dkeep))
-#else
-#define QIDX(x) (x)
-#endif
-            if constexpr (MODE == 1) {
-#pragma unroll
-              for (int n = 0; n < GR; n++) {
-                const uint32_t wv = __builtin_amdgcn_alignbit(hi[n], lo[n], p[n] & 31);
-                v0[n] = q0[wv & mask0];
-                v1[n] = q1[(wv >> Qm0) & mask0];
-              }
-            } else {
-#pragma unroll
-              for (int n = 0; n < GR; n++) v0[n] = q0[QIDX(__builtin_amdgcn_alignbit(hi[n], lo[n], p[n] & 31) & mask0)];
-            }
-            if constexpr (CW2) {
-#pragma unroll
-              for (int n = 0; n < GR; n++) {
-                p[n] = __umul24(code[n] < OAI4G_CTL_CODE ? (code[n] & 0x7FFFu) : 0u, Qm1) + b1;
-                lo[n] = e1[p[n] >> 5];
-                hi[n] = e1[(p[n] >> 5) + 1];
-              }
-#pragma unroll
-              for (int n = 0; n < GR; n++) v1[n] = q1[QIDX(__builtin_amdgcn_alignbit(hi[n], lo[n], p[n] & 31) & mask1)];
-            }
-#pragma unroll
-            for (int n = 0; n < GR; n++) {
-              const bool valid = code[n] < OAI4G_CTL_CODE;         /* a PDSCH data RE */
-              const s16x2 x0 = u2c(valid ? v0[n] : 0u);
-              if constexpr (MODE == 1) {
-                alm_pair(x0, u2c(valid ? v1[n] : 0u), code[n] & 1u, x[0][g + n], x[1][g + n]);
-              } else if constexpr (MODE == 3) {
-                const s16x2 x1 = u2c(valid ? v1[n] : 0u);
-                const uint32_t sel = ((re0 + (code[n] & 0x7FFFu)) & 7u) * 4u + 2u * pair;   /* (i mod 8, p) */
-#pragma unroll
-                for (int a = 0; a < 2; a++)
-                  x[a][g + n] = half_signed(((CDD4_QSEL >> (sel + a)) & 1u) ? x1 : x0, (CDD4_NEG >> (sel + a)) & 1u);
-              } else if constexpr (NA == 2) {
-                const s16x2 x1 = CW2 ? u2c(valid ? v1[n] : 0u) : (s16x2){0, 0};
-                cdd_pair(x0, x1, code[n] >> 15 & 1u, x[0][g + n], x[1][g + n]);
-              } else {
-                x[0][g + n] = x0;                                   /* TM1: SISO precoder */
-              }
-            }
-          }
-#endif
-          if constexpr (CRS && STATTM) {
+          if constexpr (CRS) {
             if (crs) {
-              /* CRS / control symbol: the data path read the zero sentinel at every static RE (remap_tm0),
+              /* CRS / control symbol: the data path read the zero sentinel at every static RE (remap_tm),
                * so the antenna's static values (0 at data REs) are ORed over it: 16 consecutive words per
                * thread and antenna, four 16-byte loads, no per-RE tests */
 #pragma unroll
@@ -1397,33 +1237,6 @@ __global__ void __launch_bounds__(128) MODOFDM_ATTR k_modofdm(const cfg_dev_t *_
                 for (int n = 0; n < 16; n++) {
                   if (zb(n)) continue;   /* no CRS or control RE in the guard band */
                   x[a][n] = u2c(c2u(x[a][n]) | w[n >> 2][n & 3]);
-                }
-              }
-            }
-          } else if constexpr (CRS) {
-            if (crs) {
-              /* cell-specific RS (pilots.c:43-168): overwrite the antenna carrying port p */
-#pragma unroll
-              for (int n = 0; n < 16; n++) {
-#if OAI4G_MOD_STAGE
-                if (zb(n)) continue;   /* no CRS or control RE in the guard band */
-#endif
-                const uint32_t cd = (rw[n >> 1] >> (16 * (n & 1))) & 0xFFFFu;
-                const bool pil_re = cd >= OAI4G_CRS_CODE && cd != 0xFFFFu;
-                const uint32_t ci = (cd >> 9) & 7u, m = cd & 0xFFu, port = ((cd >> 8) & 1u) | (ci >= 4 ? 2u : 0u);
-                const uint32_t pv = pil_re ? crs_tab[(sfi * 6 + ci) * 200 + m] : 0u;
-#pragma unroll
-                for (int a = 0; a < NA; a++)
-                  if (pil_re) x[a][n] = (NA == 1 || (uint32_t)a + 2 * pair == port) ? u2c(pv) : (s16x2){0, 0};
-                /* control region (generate_dci_top writes antennas 0 and 1 only, dci.c:2260-2336) */
-                const bool ctl_re = (cd & 0xE000u) == OAI4G_CTL_CODE;
-                if (ctl_re) {
-                  const size_t cb = ((size_t)(sfi * 14 + l) * 2) * N + (uint32_t)t + (uint32_t)(N / 16) * (uint32_t)n;
-#pragma unroll
-                  for (int a = 0; a < NA; a++) {
-                    const uint32_t ant = NA == 1 ? 0u : (uint32_t)a + 2 * pair;
-                    x[a][n] = ant < 2 ? u2c(ctl_tab[cb + ant * N]) : (s16x2){0, 0};
-                  }
                 }
               }
             }
@@ -1472,7 +1285,9 @@ __global__ void __launch_bounds__(128) MODOFDM_ATTR k_modofdm(const cfg_dev_t *_
           }
         },
         1, it);
-    if (OAI4G_MOD_ENDSYNC || PSYNC) __syncthreads();   /* PSYNC: the next item stages into the exchange */
+    /* no barrier at the end of an item otherwise: the next item's LDS writes (staging, then the leaves)
+     * are separated from this item's last reads (prologue, pass C) by the staging barrier */
+    if (PSYNC) __syncthreads();   /* the next item stages into the exchange */
   }
 }
 
@@ -1553,7 +1368,7 @@ hipError_t oai4g_launch_modofdm(const cfg_dev_t *d_cfg, const cfg_dev_t *h_cfg, 
   if (h_cfg->mimo_mode != OAI4G_SISO && h_cfg->n_ant != 2 && !(h_cfg->mimo_mode == OAI4G_LARGE_CDD && h_cfg->n_ant == 4))
     return hipErrorInvalidValue;
   if (h_cfg->mimo_mode == OAI4G_LARGE_CDD && h_cfg->n_cw != 2) return hipErrorInvalidValue;
-  if (OAI4G_MOD_ZBAND && h_cfg->log2N >= 7 && h_cfg->log2N <= 11) {
+  if (h_cfg->log2N >= 7 && h_cfg->log2N <= 11) {
     /* the guard-band leaf inputs must be zero subcarriers: T ZLO > 6 N_RB_DL, T (ZHI + 1) <= first_carrier */
     const uint32_t T = h_cfg->N >> 4, zlo = h_cfg->log2N == 8 ? 6u : 5u, zhi = h_cfg->log2N == 8 ? 9u : 10u;
     if (h_cfg->first_carrier != h_cfg->N - 6 * h_cfg->N_RB_DL || T * zlo <= 6 * h_cfg->N_RB_DL ||

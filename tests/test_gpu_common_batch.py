@@ -42,7 +42,7 @@ def _oracle_iq(p, sf, pay, items, n_common, pdu, fm4, phich, pbch_state):
 
 
 @pytest.mark.parametrize("name,nid,fm4,dci", [("C3", 0, 0, True), ("C3", 13, 2, True), ("C2", 7, 1, False),
-                                               ("TM2", 41, 3, True), ("C1", 2, 0, True)])
+                                               ("TM2", 41, 3, True), ("C1", 2, 0, True), ("C4", 8, 1, True)])
 def test_batch_full_grid(gpu, name, nid, fm4, dci):
     p = gpu.make_params(name, subframe=0, subframe_step=1, Nid_cell=nid, with_crs=1)
     n_ant = p.nb_antennas_tx

@@ -139,6 +139,12 @@ oai4g_dlsch_t *oai4g_new_dlsch(uint8_t Kmimo, uint8_t Mdlharq, uint8_t N_RB_DL);
 void oai4g_free_dlsch(oai4g_dlsch_t *dlsch);
 /* lte_gold_generic (PHY/LTE_REFSIG/lte_gold.c:151): scalar 32-bit LFSR helper, host-side */
 uint32_t oai4g_lte_gold_generic(uint32_t *x1, uint32_t *x2, uint8_t reset);
+/* The encoder's 32-fold of the QPP interleaver, host-side.  With Q = K/32, a code-block size K takes
+ * it when 1024 | K and Pi(k + Q) = Pi(k) + s Q (mod K) with s odd holds for every k < K (verified
+ * step by step, not from a closed form).  Returns 1 and writes s and the K/32 entries
+ * tab[k] = (Pi(k) mod Q) << 7 | (s^-1 (Pi(k) div Q) mod 32); 0 (outputs untouched) for a size that
+ * keeps the quarter fold; < 0 when K is not a turbo block size. */
+int oai4g_qpp_fold32(uint32_t K, uint32_t *s, uint16_t *tab);
 
 /* ---------------- drop-in entry points (GPU compute on host buffers) ---------------- */
 /* crc24a / crc24b (PHY/CODING/crc_byte.c:117 / :135): returns crc << 8 */

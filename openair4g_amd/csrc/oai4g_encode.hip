@@ -813,7 +813,55 @@ static __device__ void encode_codeword(const cfg_dev_t *__restrict__ c, uint32_t
    * per 32 positions with byte permutes.  A block's planes (K / 32 words) live in its first parity
    * stream's slot, which the turbo encoder writes only in phase 3b: region A holds just the
    * interleaved words. */
+  /* Block sizes with 1024 | K whose QPP folds 32 ways (cw.qpp_f32, oai4g_qpp_fold32) skip all of
+   * that: with Q = K/32, Pi(k + Q j) = x' + Q ((j0 + s j) mod 32) for k < Q, x' = Pi(k) mod Q,
+   * j0 = Pi(k) div Q.  So with the block as the 32 x Q bit matrix T[x] (bit j = c[x + Q (s j mod 32)]),
+   * output word k (bit j = c'[k + Q j]) is T[x'] rotated right by s^-1 j0: a column gather and a
+   * rotate.  A half-wave transposes a 32 x 32 tile of the systematic words into T (lane j loads
+   * word t + (Q/32) (s j mod 32): the multiply-by-s row order costs nothing), T lives where the
+   * planes would (K/32 words in the first parity slot); after the barrier a half-wave gathers and
+   * rotates an output tile through the 16-bit table entries, transposes back and stores whole
+   * interleaved words: no atomics, no byte stores, no zeroing.  The tiles of all such blocks are
+   * flattened over the half-waves; the transposes need every lane, so the loops are wave-uniform
+   * and a half-wave past the end repeats the last tile (the same words, stored again). */
+  const uint32_t fw0 = __builtin_amdgcn_readfirstlane(cw.qpp_f32[0]), fw1 = __builtin_amdgcn_readfirstlane(cw.qpp_f32[1]);
+  const bool f32a = n0 != 0 && fw0 != 0, f32b = fw1 != 0;
+  const uint32_t ft0 = f32a ? n0 * (kw0 >> 5) : 0u, ftn = ft0 + (f32b ? (C - n0) * (kw1 >> 5) : 0u);   /* tiles */
+  const uint32_t fm0 = fw0 >> 5, fm1 = fw1 >> 5;
+  /* the table entries of each such size, staged once per workgroup (K/32 <= 192 of them) in the
+   * second parity slot of the size's first block, free like the first until phase 3b: the gather
+   * then chains two LDS reads instead of a global load and an LDS read per tile.  Loaded here,
+   * stored behind the forward transposes. */
+  uint32_t *etab0 = strm + 2 * sw, *etab1 = strm + (n0 * 3 + 2) * sw;
+  uint32_t te0 = 0, te1 = 0;
+  if (f32a && tid < kw0) te0 = ((const uint16_t *)cw.qpp_tab[0])[tid];
+  if (f32b && tid < kw1) te1 = ((const uint16_t *)cw.qpp_tab[1])[tid];
+  /* flattened tile -> block, tile of the block, block size index */
+  auto tile_of = [&](uint32_t i, uint32_t &r, uint32_t &t, uint32_t &nt, uint32_t &ki) {
+    ki = i >= ft0 ? 1u : 0u;
+    const uint32_t ii = ki ? i - ft0 : i;
+    nt = (ki ? kw1 : kw0) >> 5;
+    const uint32_t rr = __umul24(ii, ki ? fm1 : fm0) >> 20;
+    t = ii - __umul24(rr, nt);
+    r = ki ? n0 + rr : rr;
+  };
+  if (ftn) {
+    const tp_lane_t tpl = tp_lane(tid & 31);
+    const uint32_t l32 = tid & 31u;
+    const uint32_t sa = fw0 & 31u, sb = fw1 & 31u;
+    for (uint32_t base = 0; base < ftn; base += nth >> 5) {
+      uint32_t r, t, nt, ki;
+      tile_of(min(base + (tid >> 5), ftn - 1), r, t, nt, ki);
+      uint32_t *sys = strm + r * 3 * sw;
+      const uint32_t v = sys[t + nt * (((ki ? sb : sa) * l32) & 31u)];
+      sys[sw + 32 * t + l32] = transpose32_t<0>(v, tpl);
+    }
+    /* one entry per thread: the workgroup's 256 threads cover K/32 <= OAI4G_MAX_CHUNKS */
+    if (f32a && tid < kw0) etab0[tid] = te0;
+    if (f32b && tid < kw1) etab1[tid] = te1;
+  }
   for (uint32_t r = 0; r < C; r++) {
+    if (r < n0 ? f32a : f32b) continue;
     const uint32_t K = r < n0 ? kk0 : kk1, Kw = (K + 31) >> 5, Q = K >> 2, io = r < n0 ? r * kw0 : u0 + (r - n0) * kw1;
     const uint32_t *sys = strm + r * 3 * sw;
     for (uint32_t w = tid; w < Kw; w += nth) ilv[io + w] = 0u;
@@ -837,11 +885,30 @@ static __device__ void encode_codeword(const cfg_dev_t *__restrict__ c, uint32_t
     }
   }
   __syncthreads();
+  if (ftn) {
+    /* 32-fold blocks: lane x of output tile t reads T[Pi(k) mod Q] for k = 32t + x, rotates it, and
+     * after the transpose lane j holds interleaved word t + (Q/32) j */
+    const tp_lane_t tpl = tp_lane(tid & 31);
+    const uint32_t l32 = tid & 31u;
+    for (uint32_t base = 0; base < ftn; base += nth >> 5) {
+      uint32_t r, t, nt, ki;
+      tile_of(min(base + (tid >> 5), ftn - 1), r, t, nt, ki);
+      /* entry: rotate in bits 0-4 (alignbit reads only those), T word in bits 7-14: its byte offset
+       * is one field extract, as in the quarter fold's entries */
+      const uint32_t e = (ki ? etab1 : etab0)[32 * t + l32];
+      const uint32_t *T = strm + (r * 3 + 1) * sw;
+      const uint32_t D = *(const uint32_t *)((const uint8_t *)T + __builtin_amdgcn_ubfe(e, 5, 10));
+      const uint32_t io = r < n0 ? r * kw0 : u0 + (r - n0) * kw1;
+      ilv[io + t + nt * l32] = transpose32_t<0>(__builtin_amdgcn_alignbit(D, D, e), tpl);
+    }
+  }
   {
     /* 8-step units: unit j of block r walks k = 8j .. 8j+7 (< Q) through the host table and
-     * yields one byte of each quarter; ceil(K/32) units per block, indexed like the interleaved words */
+     * yields one byte of each quarter; ceil(K/32) units per block, indexed like the interleaved words
+     * (the units of quarter-fold blocks only: blocks of size kk0 come first, u0 words of them) */
     const bool s3a = __builtin_amdgcn_readfirstlane(cw.qpp_s3[0]) != 0, s3b = __builtin_amdgcn_readfirstlane(cw.qpp_s3[1]) != 0;
-    for (uint32_t i = tid; i < nw; i += nth) {
+    const uint32_t ulo = f32a ? u0 : 0u, uhi = f32b ? u0 : nw;
+    for (uint32_t i = ulo + tid; i < uhi; i += nth) {
       uint32_t r, j, K, ki;
       unit_of(i, r, j, K, ki);
       const uint32_t Q = K >> 2;
@@ -1117,7 +1184,10 @@ static __device__ void encode_codeword(const cfg_dev_t *__restrict__ c, uint32_t
   }
 }
 
-__global__ void __launch_bounds__(256) k_encode(const cfg_dev_t *__restrict__ c, const uint8_t *__restrict__ payload,
+/* Held to 80 SGPRs (the compiler meets it without spills): at 83, the next allocation step, the
+ * same 8 workgroups per CU ran measurably slower: phase 0 of C3 29.8 -> 33.6 us per 8192 subframes,
+ * C2 -3.5 % (profiles/qppfold_ab.md) */
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) k_encode(const cfg_dev_t *__restrict__ c, const uint8_t *__restrict__ payload,
                                                 uint32_t *__restrict__ ebits, int stop_phase, uint32_t sf0)
 {
   extern __shared__ uint32_t lds_dyn[];

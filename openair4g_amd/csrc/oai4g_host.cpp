@@ -809,6 +809,32 @@ static void rm_plan(cw_dev_t &c, int ki)
   if (getenv("OAI4G_ENC_GENERAL_RM")) c.rm_wrapt[ki] = ~1u;
 }
 
+/* k_encode phase 3a's 32-fold: predicate and table for block size K (include/oai4g.h).  Plain host
+ * arithmetic, no device. */
+extern "C" int oai4g_qpp_fold32(uint32_t K, uint32_t *s_out, uint16_t *tab)
+{
+  const int qi = oai4g_qpp_index(K);
+  if (qi < 0 || oai4g_qpp_table[qi].K != K) return -1;
+  if (K & 1023u) return 0;                 /* rows of a 32 x 32 tile must be aligned words: 32 | Q */
+  const uint64_t f1 = oai4g_qpp_table[qi].f1, f2 = oai4g_qpp_table[qi].f2;
+  const uint32_t Q = K >> 5;
+  auto pi = [&](uint64_t k) { return (uint32_t)((f1 * k + f2 * k * k) % K); };
+  const uint32_t d = (pi(Q) + K - pi(0)) % K;
+  if (d % Q) return 0;
+  const uint32_t s = d / Q;
+  if (!(s & 1u)) return 0;
+  for (uint32_t k = 0; k < K; k++)
+    if ((pi(k + Q) + K - pi(k)) % K != d) return 0;
+  uint32_t si = 1;                          /* s^-1 mod 32 */
+  while (((si * s) & 31u) != 1u) si += 2;
+  *s_out = s;
+  for (uint32_t k = 0; k < Q; k++) {
+    const uint32_t x = pi(k);
+    tab[k] = (uint16_t)(((x % Q) << 7) | ((si * (x / Q)) & 31u));
+  }
+  return 1;
+}
+
 static int derive_cfg(oai4g_tx_config *cfg, const oai4g_tx_params_t *p, const uint8_t Nl[2], bool need_remap,
                       int only_sf)
 {
@@ -919,7 +945,6 @@ static int derive_cfg(oai4g_tx_config *cfg, const oai4g_tx_params_t *p, const ui
         uint32_t pi = (uint32_t)((f1 * k + f2 * k * k) % K), pi1 = (uint32_t)((f1 * (k + 1) + f2 * (k + 1) * (k + 1)) % K);
         c.qpp0[ki][j] = pi | (((pi1 + K - pi) % K) << 16);
       }
-      c.qpp_d2[ki] = (uint32_t)((2 * f2) % K);
       memset(c.qpp_tab[ki], 0, sizeof(c.qpp_tab[ki]));
       /* entry k: plane word xp/8 (bits 7-14) and the rotate (bits 0-4) that lands bit (8u + xp%8) of
        * it at bit k%8 of each byte (the walk's step index is folded into the rotate, so the kernel
@@ -930,6 +955,16 @@ static int derive_cfg(oai4g_tx_config *cfg, const oai4g_tx_params_t *p, const ui
         c.qpp_tab[ki][k >> 1] |= (((xp >> 3) << 7) | rot) << (16 * (k & 1));
       }
       c.qpp_s3[ki] = (uint32_t)((f1 * (K / 4)) % K) == K / 4 ? 0u : 1u;
+      /* the 32-fold where the size admits it: its K/32 uint16 entries replace the quarter fold's in
+       * qpp_tab (the kernel takes one path or the other per block size) */
+      static_assert(sizeof(c.qpp_tab[0]) >= OAI4G_MAX_CHUNKS * sizeof(uint16_t), "32-fold entries fit qpp_tab");
+      uint32_t s32 = 0;
+      uint16_t t32[OAI4G_MAX_CHUNKS];
+      if (oai4g_qpp_fold32(K, &s32, t32) == 1) {
+        memset(c.qpp_tab[ki], 0, sizeof(c.qpp_tab[ki]));
+        memcpy(c.qpp_tab[ki], t32, (K / 32) * sizeof(uint16_t));
+        c.qpp_f32[ki] = s32 | ((((1u << 20) + K / 1024 - 1) / (K / 1024)) << 5);
+      }
     }
     {
       uint32_t o = 0;

@@ -86,14 +86,17 @@ struct cw_dev_t {
   uint16_t tasks[OAI4G_MAX_TASKS];    /* block | kind << 4 (0: v0 rows, 1: v1/v2 rows) | tile << 5 */
   uint32_t ilv_off[OAI4G_MAX_CB + 1]; /* LDS word offset of block r's QPP-interleaved input words */
   /* QPP interleaver walk per 8-step unit j of the quarter fold (kidx list): Pi(8j) | (Pi(8j+1) -
-   * Pi(8j) mod K) << 16, j < K/32, and the second difference 2 f2 mod K (3gpplte.c:50-74 restated
-   * incrementally) */
+   * Pi(8j) mod K) << 16, j < K/32 (3gpplte.c:50-74 restated incrementally) */
   uint32_t qpp0[2][OAI4G_MAX_CHUNKS];
   /* the quarter fold's walk as a table: entry k < K/4 (two uint16 per word) = word index of
    * x' = Pi(k) mod K/4 in the byte-interleaved planes (x' >> 3) | shift (8 (Pi(k) div K/4) +
    * (x' & 7)) << 11 */
   alignas(16) uint32_t qpp_tab[2][OAI4G_MAX_CHUNKS * 4];
-  uint32_t qpp_d2[2];
+  /* 32-fold (oai4g_qpp_fold32; sizes with 1024 | K): with Q = K/32, Pi(k + Q) = Pi(k) + s Q mod K.
+   * qpp_f32 = 0 for a size that keeps the quarter fold, else s (odd, bits 0-4) | ceil(2^20 / (Q/32))
+   * << 5 (tile index -> block), and then qpp_tab holds, as uint16 entries k < Q, the word index
+   * x' = Pi(k) mod Q (bits 7-14) and the rotate s^-1 (Pi(k) div Q) mod 32 (bits 0-4) */
+  uint32_t qpp_f32[2];
   /* quarter folding: Pi(k + K/4) = Pi(k) + c4 mod K with c4 = f1 K/4 mod K in {K/4, 3K/4}
    * (f2 even, 8 | K); qpp_s3 = (c4 == 3K/4) */
   uint32_t qpp_s3[2];

@@ -145,6 +145,21 @@ uint32_t oai4g_lte_gold_generic(uint32_t *x1, uint32_t *x2, uint8_t reset);
  * tab[k] = (Pi(k) mod Q) << 7 | (s^-1 (Pi(k) div Q) mod 32); 0 (outputs untouched) for a size that
  * keeps the quarter fold; < 0 when K is not a turbo block size. */
 int oai4g_qpp_fold32(uint32_t K, uint32_t *s, uint16_t *tab);
+/* The lane scan of the encoder's turbo phase for block sizes with 32 | K, host-side: with q = 1, 2 or
+ * 3 chunks of 32 bits per lane, rows[d] is the constituent encoder's zero-input state propagation over
+ * 32 q 2^d steps (d = 0..5), the image of state s in bits 4s..4s+2.  Returns 0, or -1 for another q. */
+int oai4g_rsc_scan_rows(uint32_t q, uint32_t rows[6]);
+/* The tile-pair schedule of the encoder's rate-matching phase, host-side.  A codeword of C blocks, the
+ * first n0 of block size index 0 and the rest of index 1, with nt[i] plan tiles per block of size i
+ * (1..20; ceil(R/32) + ceil(R/16)) and wrapt[i] the tile whose run straddles the circular buffer's end
+ * (or ~0 / ~1: none / the general placement path).  A block of size i runs ceil(nt[i] / 2) pairs of
+ * tiles (2p, 2p + 1).  Writes pair0[r] = index of block r's first pair (pair0[C] = all pairs, also the
+ * return value) and one descriptor per pair in block order: bit 0 = the pair holds the wrap tile,
+ * bit 1 = i, bits 2-5 = r, bits 16-28 = byte offset of the pair's first row in the plan tables
+ * (4 (21 * 32 i + 32 * 2p)).  pairs holds up to 10 C entries, pair0 C + 1.  Returns < 0 for arguments
+ * out of range. */
+int oai4g_rm_pair_schedule(uint32_t C, uint32_t n0, const uint32_t nt[2], const uint32_t wrapt[2],
+                           uint32_t *pairs, uint32_t *pair0);
 
 /* ---------------- drop-in entry points (GPU compute on host buffers) ---------------- */
 /* crc24a / crc24b (PHY/CODING/crc_byte.c:117 / :135): returns crc << 8 */

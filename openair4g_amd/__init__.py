@@ -334,6 +334,10 @@ _SIGS = {
     "oai4g_sync": (ctypes.c_int, []),
     "oai4g_fill_payload": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p]),
     "oai4g_qpp_fold32": (ctypes.c_int, [ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p]),
+    "oai4g_rsc_scan_rows": (ctypes.c_int, [ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
+    "oai4g_rm_pair_schedule": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32),
+                                              ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
+                                              ctypes.POINTER(ctypes.c_uint32)]),
 }
 
 

@@ -411,7 +411,11 @@ static __device__ __forceinline__ void turbo_segment(const uint32_t *in, uint32_
 #pragma unroll
   for (int d = 0; d < 6; d++) {
     uint32_t other = __shfl_up(S, 1u << d, 64);
-    if (lane >= (1u << d)) S ^= tb->apow[lq + d][other];
+    /* a lane below 2^d looks up state 0, which propagates to 0: a select, no exec-masked region, and
+     * the lane test kept in vcc (hoisted out of the segment loop the six masks hold 12 SGPRs) */
+    uint32_t ln = lane;
+    asm volatile("" : "+v"(ln));
+    S ^= tb->apow[lq + d][ln >= (1u << d) ? other : 0u];
   }
   uint32_t s = __shfl_up(S, 1, 64);
   if (lane == 0) s = 0;
@@ -440,6 +444,93 @@ static __device__ __forceinline__ void turbo_segment(const uint32_t *in, uint32_
       }
     }
   }
+}
+
+/* zero-input propagation of the 3-bit state by n steps, every state's image packed in one word (state
+ * s at bits 4s..4s+2): a lookup is a shift and a field extract, no LDS read.  The feedback polynomial
+ * is primitive, so the map has period 7 and n counts mod 7. */
+static constexpr uint32_t rsc_prop_packed(uint32_t n)
+{
+  uint32_t w = 0;
+  for (uint32_t s = 0; s < 8; s++) {
+    uint8_t st = (uint8_t)s;
+    for (uint32_t i = 0; i < n % 7; i++) {
+      uint8_t o = 0;
+      st = rsc_step_c(0, st, &o);
+    }
+    w |= (uint32_t)st << (4 * s);
+  }
+  return w;
+}
+static_assert(rsc_prop_packed(7) == 0x76543210u && rsc_prop_packed(1) != 0x76543210u, "RSC zero-input period");
+
+static __device__ __forceinline__ uint32_t rsc_prop(uint32_t packed, uint32_t s) { return (packed >> (4 * s)) & 7u; }
+
+/* the scan rows of turbo_segment32<Q>, as the kernel uses them (CPU tests read them back) */
+extern "C" int oai4g_rsc_scan_rows(uint32_t q, uint32_t rows[6])
+{
+  if (q < 1 || q > 3) return -1;
+  for (uint32_t d = 0; d < 6; d++) rows[d] = rsc_prop_packed((32 * q) << d);
+  return 0;
+}
+
+/* turbo_segment for block sizes with 32 | K (nch = K / 32 full chunks, no partial chunk): lane l owns
+ * the Q = ceil(nch / 64) consecutive chunks from Q l on, Q a compile-time 1, 2 or 3, so K = 6144 runs
+ * 64 lanes x 3 chunks.  No exec-masked region but the stores: lanes past the block read its last
+ * chunk (their states feed nobody), the scan selects state 0 (which propagates to 0) for a lane below
+ * 2^d instead of masking it, the propagation rows are packed constants (rsc_prop), the entry state
+ * comes back out of the inclusive one through the inverse row instead of a second shuffle, and the
+ * chunks a part-filled last lane does not own are stored as zeros into the stream's tail and
+ * read-ahead words (nch, nch + 1 < stream_words: zero until the tail bits are ORed in behind the
+ * barrier). */
+template <int Q>
+static __device__ __forceinline__ void turbo_segment32(const uint32_t *in, uint32_t *par_out, uint32_t nch,
+                                                       uint32_t *tail_out, const enc_tabs_t *tb)
+{
+  constexpr uint32_t A1 = rsc_prop_packed(32), AQinv = rsc_prop_packed(7 - (32 * Q) % 7);
+  const uint32_t lane = threadIdx.x & 63, j0 = lane * Q, last = nch - 1;
+  uint32_t v[Q], S = 0;
+#pragma unroll
+  for (int t = 0; t < Q; t++) {
+    v[t] = rsc_feedback_word(in[min(j0 + t, last)]);
+    S = (t ? rsc_prop(A1, S) : 0u) ^ (v[t] >> 29);
+  }
+  const uint32_t Sloc = S;
+  /* inclusive scan over lanes: S_l ^= A^(32 Q 2^d) S_(l - 2^d) */
+#pragma unroll
+  for (int d = 0; d < 6; d++) {
+    const uint32_t o = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((lane - (1u << d)) << 2), (int)S);
+    /* the lane test stays here, in vcc: hoisted out of the segment loop, the six lane masks take 12
+     * SGPRs and k_encode no longer fits its 80 */
+    uint32_t ln = lane;
+    asm volatile("" : "+v"(ln));
+    S ^= rsc_prop(rsc_prop_packed((32u * Q) << d), ln >= (1u << d) ? o : 0u);
+  }
+  /* S_l = A^(32 Q) s_l ^ Sloc_l with s_l the lane's entry state */
+  uint32_t s = rsc_prop(AQinv, S ^ Sloc), fin = 0;
+  uint32_t par[Q];
+#pragma unroll
+  for (int t = 0; t < Q; t++) {
+    const uint32_t j = j0 + t;
+    const uint32_t p = rsc_parity_of_feedback(v[t]) ^ tb->zs[s];
+    s = rsc_prop(A1, s) ^ (v[t] >> 29);
+    par[t] = (t == 0 || j < nch) ? p : 0u;
+    fin = j == last ? s : fin;
+  }
+  /* trellis termination (3gpplte_sse.c:104-109, 440-471): (x, z) per step, in every lane; the lane
+   * that owns the last chunk stores it */
+  uint32_t tbits = 0;
+#pragma unroll
+  for (int stp = 0; stp < 3; stp++) {
+    const uint32_t z = ((fin >> 2) ^ fin) & 1u, x = (fin ^ (fin >> 1)) & 1u;
+    fin >>= 1;
+    tbits |= (x << (2 * stp)) | (z << (2 * stp + 1));
+  }
+  if (j0 < nch) {
+#pragma unroll
+    for (int t = 0; t < Q; t++) par_out[j0 + t] = par[t];
+  }
+  if (last - j0 < (uint32_t)Q) *tail_out = tbits;
 }
 
 /* tail bit m (0..11) of block r: t[0..5] from encoder 1, t[6..11] from encoder 2 */
@@ -954,7 +1045,14 @@ static __device__ void encode_codeword(const cfg_dev_t *__restrict__ c, uint32_t
     const uint32_t r = seg >> 1, e = seg & 1u;
     uint32_t *blk = strm + r * 3 * sw;
     const uint32_t io = r < n0 ? r * kw0 : u0 + (r - n0) * kw1;
-    turbo_segment(e ? ilv + io : blk, blk + (1 + e) * sw, r < n0 ? kk0 : kk1, &tails[2 * r + e], tabs);
+    const uint32_t *in = e ? ilv + io : blk;
+    uint32_t *par = blk + (1 + e) * sw, *tail = &tails[2 * r + e];
+    const uint32_t K = r < n0 ? kk0 : kk1, nch = K >> 5;
+    /* scalar dispatch: the lane-exact forms for 32 | K by chunks per lane, the generic one otherwise */
+    if (K & 31u) turbo_segment(in, par, K, tail, tabs);
+    else if (nch > 128) turbo_segment32<3>(in, par, nch, tail, tabs);
+    else if (nch > 64) turbo_segment32<2>(in, par, nch, tail, tabs);
+    else turbo_segment32<1>(in, par, nch, tail, tabs);
   }
   __syncthreads();
   if (stop_phase <= 3) return;
@@ -1027,27 +1125,22 @@ static __device__ void encode_codeword(const cfg_dev_t *__restrict__ c, uint32_t
   {
     const tp_lane_t tpl = tp_lane(tid & 31);
     const uint32_t sw3 = __builtin_amdgcn_readfirstlane(3 * sw);
-    const uint32_t nt0 = __builtin_amdgcn_readfirstlane(cw.ntk[0]), nt1 = __builtin_amdgcn_readfirstlane(cw.ntk[1]);
     const uint32_t Nnn0 = __builtin_amdgcn_readfirstlane(cw.Nnnk[0]), Nnn1 = __builtin_amdgcn_readfirstlane(cw.Nnnk[1]);
-    const uint32_t es = __builtin_amdgcn_readfirstlane(cw.esplit[sfi]);
-    const uint32_t Elo = __builtin_amdgcn_readfirstlane(cw.E[sfi][0]), Ehi = __builtin_amdgcn_readfirstlane(cw.E[sfi][C - 1]);
-    const uint32_t wrapt0 = __builtin_amdgcn_readfirstlane(cw.rm_wrapt[0]), wrapt1 = __builtin_amdgcn_readfirstlane(cw.rm_wrapt[1]);
     /* no repetition (E <= Nnn for every block): a run lands once at most */
-    const bool once = Ehi <= min(Nnn0, Nnn1) && Elo <= min(Nnn0, Nnn1) && wrapt0 != ~1u && wrapt1 != ~1u;
-    const uint32_t pp0 = (nt0 + 1) >> 1, pp1 = (nt1 + 1) >> 1;            /* tile pairs per block */
-    const uint32_t psplit = n0 * pp0;
-    const uint32_t pm0 = ((1u << 20) + pp0 - 1) / pp0, pm1 = ((1u << 20) + pp1 - 1) / pp1;
-    auto ro_of = [&](uint32_t r) { return r >= es ? es * Elo + (r - es) * Ehi : r * Elo; };   /* e bit offset of block r */
-    auto pair0 = [&](uint32_t r) { return r < n0 ? r * pp0 : psplit + (r - n0) * pp1; };      /* first tile pair of block r */
-    /* tile pair P -> (block size, block, first tile); the pair's plan rows are contiguous, so a
-     * lane's plan words sit at a wave-uniform base + 4 lane.  Loaded one pair ahead. */
-    auto decode = [&](uint32_t P, uint32_t &ki, uint32_t &r, uint32_t &t0) {
-      ki = P >= psplit ? 1u : 0u;
-      const uint32_t PP = ki ? P - psplit : P, pp = ki ? pp1 : pp0;
-      const uint32_t rr = (PP * (ki ? pm1 : pm0)) >> 20, rem = PP - rr * pp;
-      r = ki ? n0 + rr : rr;
-      t0 = 2 * rem;
-    };
+    bool once;
+    {
+      const uint32_t Elo = __builtin_amdgcn_readfirstlane(cw.E[sfi][0]), Ehi = __builtin_amdgcn_readfirstlane(cw.E[sfi][C - 1]);
+      const uint32_t wrapt0 = __builtin_amdgcn_readfirstlane(cw.rm_wrapt[0]), wrapt1 = __builtin_amdgcn_readfirstlane(cw.rm_wrapt[1]);
+      once = Ehi <= min(Nnn0, Nnn1) && Elo <= min(Nnn0, Nnn1) && wrapt0 != ~1u && wrapt1 != ~1u;
+    }
+    /* The tile pairs come from the host's schedule (cw.rm_pairs, oai4g_rm_pair_schedule): one
+     * descriptor per pair, and per block E and the e-bit offset from the subframe index's tables, all
+     * read with scalar loads through the constant address space: nothing is stepped or decoded here.
+     * (E and the offset staged in LDS and read by block index next to the stream words instead:
+     * measured, the kernel 12 % slower.) */
+    typedef const __attribute__((address_space(4))) uint32_t cu32_t;
+    cu32_t *pdesc = (cu32_t *)cw.rm_pairs, *ppair0 = (cu32_t *)cw.rm_pair0;
+    cu32_t *pE = (cu32_t *)cw.E[sfi], *proff = (cu32_t *)cw.roff[sfi];
     gu32_t *gold = (gu32_t *)(c->gold_tab + (size_t)(sfi * c->n_cw + cwi) * c->ebits_words);
     uint32_t *eout = DEBUG ? nullptr : ebits + (size_t)(sf * c->n_cw + cwi) * c->ebits_words;
     uint32_t *ebuf = DEBUG ? dbg_ebuf : lds_base;
@@ -1055,67 +1148,42 @@ static __device__ void encode_codeword(const cfg_dev_t *__restrict__ c, uint32_t
     uint32_t carry = 0;                          /* the boundary word of the first half */
     for (uint32_t h = 0; h < nhalf; h++) {
       const uint32_t rb0 = h ? hb : 0, rb1 = h ? C : hb;
-      const uint32_t eb0 = ro_of(rb0), eb1 = rb1 < C ? ro_of(rb1) : G;   /* e bits [eb0, eb1) */
+      const uint32_t eb0 = proff[rb0], eb1 = rb1 < C ? proff[rb1] : G;   /* e bits [eb0, eb1) */
       const uint32_t w0 = eb0 >> 5, nwh = ((eb1 + 31) >> 5) - w0;       /* staged words */
       /* nwh + 1 words: or_bits2 always writes word bit / 32 + 1 as well, so the word past the half's last
        * is zeroed too; the host reserves it (derive_cfg: lds_a_words >= w1, w2 = staged words + 1; the
        * debug kernel's dbg_ebuf holds the whole codeword + 1) */
       for (uint32_t i = tid; i < nwh + 1; i += nth) ebuf[i] = (i == 0 && h) ? carry : 0u;
       __syncthreads();
-      const uint32_t pb = pair0(rb0), pe = pair0(rb1), bit0 = 32 * w0;
-      /* plan rows of pair (ki, t0): a wave-uniform word offset (scalar) from the plan base, so the
-       * loads take an SGPR base and the lane offset, with no vector address arithmetic */
-      const uint32_t *rsrc0 = &cw.rm_src[0][0][0], *rdst0 = &cw.rm_dst[0][0][0];
-      auto row_of = [&](uint32_t ki, uint32_t t0) {
-        return __builtin_amdgcn_readfirstlane(ki * ((OAI4G_RM_TILES + 1) * 32) + t0 * 32);
-      };
-      /* round-robin pairs P = pb + wave + k nwaves, stepped rather than decoded: the next pair is
-       * nwaves pairs on (2 nwaves tiles), carried over block ends; a block's scalars change only
-       * there.  Plan words loaded one pair ahead. */
-      /* The pair loop, versioned on `once` (wave-uniform, loop-invariant) so that neither version
-       * tests it per pair; a block's scalars (stream offset, E, e offset, Nnn, wrap tile) are
-       * refreshed only when the walk enters the next block. */
+      const uint32_t pb = ppair0[rb0], pe = ppair0[rb1], bit0 = 32 * w0;
+      /* plan rows of a pair: the descriptor's byte offset (scalar) and 4 lane from the plan bases */
+      const char *rsrc0 = (const char *)&cw.rm_src[0][0][0], *rdst0 = (const char *)&cw.rm_dst[0][0][0];
+      /* The pair loop: round-robin pairs P = pb + wave + k nwaves of the schedule, versioned on `once`
+       * (wave-uniform, loop-invariant) so that neither version tests it per pair.  The descriptor is
+       * fetched two pairs ahead, and with it, one pair ahead, the block's E and e-bit offset and the
+       * lane's plan words; past the wave's last pair the fetches repeat the half's last pair (unused).
+       * (Two pairs in flight per wave, the two transposes interleaved: measured, the kernel 2.5 %
+       * slower.) */
       auto pair_loop = [&](auto ONCE) {
         uint32_t P = pb + wave;
-        uint32_t ki = 0, r = 0, t0 = 0;
-        uint32_t nsrc = 1u << 5, ndst = 0;
-        if (P < pe) {
-          decode(P, ki, r, t0);
-          const uint32_t ro = row_of(ki, t0);
-          nsrc = (rsrc0 + ro)[lane];
-          ndst = (rdst0 + ro)[lane];
-        }
-        uint32_t bbo = 0, E = 0, rob = 0, Nnn = 0, wtc = 0, tpb = 0, rowb = 0;
-        auto enter = [&](uint32_t rr, uint32_t kk) {
-          bbo = __builtin_amdgcn_readfirstlane(rr * sw3);
-          E = rr >= es ? Ehi : Elo;
-          rob = ro_of(rr) - bit0;
-          Nnn = kk ? Nnn1 : Nnn0;
-          wtc = kk ? wrapt1 : wrapt0;
-          tpb = 2 * (kk ? pp1 : pp0);                                        /* tiles per block (pairs x 2) */
-          rowb = kk * ((OAI4G_RM_TILES + 1) * 32);                           /* the block size's plan rows */
+        if (P >= pe) return;
+        const uint32_t plast = pe - 1;
+        uint32_t d = pdesc[P], dn = pdesc[min(P + nwaves, plast)];
+        uint32_t E, ro, nsrc, ndst;
+        auto fetch = [&]() {
+          E = pE[(d >> 2) & 15u];
+          ro = proff[(d >> 2) & 15u];
+          nsrc = *(const uint32_t *)(rsrc0 + ((d >> 16) + 4 * lane));
+          ndst = *(const uint32_t *)(rdst0 + ((d >> 16) + 4 * lane));
         };
-        enter(r, ki);
-        for (; P < pe; P += nwaves) {    /* scalar loop: wave is an SGPR */
-          const uint32_t src = nsrc, dst = ndst;
-          /* the next pair of this wave (crossing into later blocks only at a block end) */
-          uint32_t k2 = ki, r2 = r, t2 = t0 + 2 * nwaves, rowb2 = rowb;
-          if (t2 >= tpb) {
-            uint32_t tpb2 = tpb;
-            do {
-              t2 -= tpb2;
-              r2++;
-              k2 = r2 >= n0 ? 1u : 0u;
-              tpb2 = 2 * (k2 ? pp1 : pp0);
-            } while (t2 >= tpb2);
-            rowb2 = k2 * ((OAI4G_RM_TILES + 1) * 32);
-          }
-          if (P + nwaves < pe) {
-            const uint32_t ro = __builtin_amdgcn_readfirstlane(rowb2 + t2 * 32);
-            nsrc = (rsrc0 + ro)[lane];
-            ndst = (rdst0 + ro)[lane];
-          }
-          const uint32_t *bb = strm + bbo - 1;                               /* block streams - 1 word (scalar offset) */
+        fetch();
+        for (;;) {    /* scalar loop: wave is an SGPR */
+          const uint32_t src = nsrc, dst = ndst, dc = d, Ec = E, rob = ro - bit0;   /* rob: relative to the staged words */
+          d = dn;
+          dn = pdesc[min(P + 2 * nwaves, plast)];
+          fetch();
+          /* block streams - 1 word: (block << 2) x words per block = its byte offset (scalar) */
+          const uint32_t *bb = (const uint32_t *)((const char *)strm + (dc & 0x3cu) * sw3) - 1;
           const uint32_t *wp = bb + ((src >> 5) & 0x7fffu);
           uint32_t y = __builtin_amdgcn_alignbit(wp[1], wp[0], src);          /* bits before 0 are NULLs */
           /* the RM_SRC_LAST lane (row R - 1 of y2, j = Kpi - 1 reads y^(2)_0 at bit 31) needs no
@@ -1124,37 +1192,38 @@ static __device__ void encode_codeword(const cfg_dev_t *__restrict__ c, uint32_t
           y = transpose32_t<0>(y, tpl);
           y >>= (dst >> 16) & 31u;                                           /* leading NULLs z */
           const uint32_t o = dst & 0xffffu, m = __builtin_amdgcn_ubfe(dst, 21, 6);
-          const uint32_t ro = rob;                                           /* relative to the staged words */
           if constexpr (decltype(ONCE)::value) {
             /* no repetition (E <= Nnn): the run's part below E, then (the one run that straddles
-             * the circular buffer's end: a block's wrap tile, scalar test first) its wrapped part at 0 */
-            const int l = min((int)m, (int)E - (int)o);
-            if (l > 0) or_bits2(ebuf, ro + o, y & (0xffffffffu >> (32 - l)));
-            if (wtc - t0 < 2u) {                                             /* t0 or t0 + 1 is the wrap tile */
+             * the circular buffer's end, in a block's wrap tile: the descriptor's flag, a scalar
+             * test, first) its wrapped part at 0.  A run that lands nothing is masked off, not
+             * placed as zeros: ORing zeros costs the LDS atomics of every such lane (a third of
+             * them at C3), measured slower than the exec-masked region. */
+            const int l = min((int)m, (int)Ec - (int)o);
+            if (l > 0) or_bits2(ebuf, rob + o, y & (0xffffffffu >> (32 - l)));
+            if (dc & 1u) {
               asm volatile("" ::: "memory");   /* keeps the lane test below behind the scalar one */
               if (dst & OAI4G_RM_DST_WRAP) {
-                const uint32_t ma = Nnn - o;                                 /* 1 .. m - 1 */
-                const uint32_t l2 = min(m - ma, E);
-                or_bits2(ebuf, ro, (y >> ma) & (0xffffffffu >> (32 - l2)));
+                const uint32_t ma = ((dc & 2u) ? Nnn1 : Nnn0) - o;           /* 1 .. m - 1 */
+                const uint32_t l2 = min(m - ma, Ec);
+                or_bits2(ebuf, rob, (y >> ma) & (0xffffffffu >> (32 - l2)));
               }
             }
           } else if (m) {
+            const uint32_t Nnn = (dc & 2u) ? Nnn1 : Nnn0;
             y &= 0xffffffffu >> (32 - m);
             /* the run may straddle the wrap back to k0c; E > Nnn repeats the buffer */
             const uint32_t ma = min(m, Nnn - o);
             for (uint32_t part = 0; part < 2; part++) {
               const uint32_t len = part ? m - ma : ma, os = part ? 0u : o;
               const uint32_t v = part ? (ma < 32 ? y >> ma : 0u) : (ma < 32 ? y & ((1u << ma) - 1u) : y);
-              for (uint32_t x = os; len && x < E; x += Nnn) {                   /* repetition rounds */
-                const uint32_t l = min(len, E - x);
-                or_bits(ebuf, ro + x, v & (0xffffffffu >> (32 - l)));
+              for (uint32_t x = os; len && x < Ec; x += Nnn) {                  /* repetition rounds */
+                const uint32_t l = min(len, Ec - x);
+                or_bits(ebuf, rob + x, v & (0xffffffffu >> (32 - l)));
               }
             }
           }
-          if (r2 != r) enter(r2, k2);
-          ki = k2;
-          r = r2;
-          t0 = t2;
+          P += nwaves;
+          if (P >= pe) break;
         }
       };
       if (once) pair_loop(std::true_type{});

@@ -809,6 +809,27 @@ static void rm_plan(cw_dev_t &c, int ki)
   if (getenv("OAI4G_ENC_GENERAL_RM")) c.rm_wrapt[ki] = ~1u;
 }
 
+/* k_encode phase 4's tile-pair schedule (include/oai4g.h).  Plain host arithmetic, no device. */
+extern "C" int oai4g_rm_pair_schedule(uint32_t C, uint32_t n0, const uint32_t nt[2], const uint32_t wrapt[2],
+                                      uint32_t *pairs, uint32_t *pair0)
+{
+  if (C < 1 || C > OAI4G_MAX_CB || n0 > C) return -1;
+  for (uint32_t ki = 0; ki < 2; ki++)
+    if ((ki ? n0 < C : n0 > 0) && (nt[ki] < 1 || nt[ki] > OAI4G_RM_TILES)) return -1;
+  uint32_t n = 0;
+  for (uint32_t r = 0; r < C; r++) {
+    const uint32_t ki = r >= n0 ? 1u : 0u, pp = (nt[ki] + 1) / 2;
+    pair0[r] = n;
+    for (uint32_t p = 0; p < pp; p++) {
+      const uint32_t t0 = 2 * p, row = ki * ((OAI4G_RM_TILES + 1) * 32) + t0 * 32;   /* plan-row word offset */
+      const uint32_t wrap = wrapt[ki] - t0 < 2u ? 1u : 0u;                           /* t0 or t0 + 1 (not ~0, ~1) */
+      pairs[n++] = wrap | (ki << 1) | (r << 2) | ((4 * row) << 16);
+    }
+  }
+  pair0[C] = n;
+  return (int)n;
+}
+
 /* k_encode phase 3a's 32-fold: predicate and table for block size K (include/oai4g.h).  Plain host
  * arithmetic, no device. */
 extern "C" int oai4g_qpp_fold32(uint32_t K, uint32_t *s_out, uint16_t *tab)
@@ -1065,6 +1086,10 @@ static int derive_cfg(oai4g_tx_config *cfg, const oai4g_tx_params_t *p, const ui
       c.ntmag[ki] = ((1u << 20) + c.ntk[ki] - 1) / c.ntk[ki];
       if (c.ntk[ki] > OAI4G_RM_TILES) { set_err("rate-matching plan: %u tiles", c.ntk[ki]); return -1; }
       rm_plan(c, ki);
+    }
+    if (oai4g_rm_pair_schedule(C, c.n0, c.ntk, c.rm_wrapt, c.rm_pairs, c.rm_pair0) < 0) {
+      set_err("rate-matching pair schedule");
+      return -1;
     }
     max_w = wwords > max_w ? wwords : max_w;
     uint32_t tbw = (c.A_bytes + 3 + 3) / 4 + 1;

@@ -149,6 +149,13 @@ struct cw_dev_t {
    *           o + m > Nnn. */
   uint32_t rm_src[2][OAI4G_RM_TILES + 1][32];   /* + one idle tile: a pair's second tile may be past nt */
   uint32_t rm_dst[2][OAI4G_RM_TILES + 1][32];
+  /* the tile pairs of every block in order (oai4g_rm_pair_schedule): a wave of phase 4 takes pairs
+   * i = first + wave, + nwaves, ... of a half of the blocks, [rm_pair0[first block], rm_pair0[end block]),
+   * and reads one descriptor per pair with a scalar load: bit 0 = the pair holds the block size's wrap
+   * tile, bit 1 = block size index, bits 2-5 = block, bits 16-28 = byte offset of the pair's rows in
+   * rm_src / rm_dst.  E and the e-bit offset of the block come from E[sfi] / roff[sfi]. */
+  uint32_t rm_pair0[OAI4G_MAX_CB + 1];
+  uint32_t rm_pairs[OAI4G_MAX_CB * ((OAI4G_RM_TILES + 1) / 2)];
 };
 
 struct cfg_dev_t {

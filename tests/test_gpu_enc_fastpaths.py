@@ -13,7 +13,9 @@ The one-antenna 20 MHz configuration (C2) with TBS overridden so that segmentati
   TBS = 12152           K- = 6080 and K+ = 6144 in one codeword, no filler
   TBS = 6208            K- = 3136 and K+ = 3200 with F = 56 filler bits
   TBS = 75376           13 blocks of 5824
-and the flagship shape itself (C3: 6 blocks of 6144 on both codewords)."""
+and the flagship shape itself (C3: 6 blocks of 6144 on both codewords).
+
+The exhaustive form (all 188 block sizes, every K- / K+ pair) is tests/test_gpu_enc_sweep.py."""
 import pytest
 
 import numpy as np

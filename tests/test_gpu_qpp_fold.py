@@ -7,7 +7,9 @@ yields exactly the block sizes under test:
   TBS = K - 24          one block of K (B = K, no CRC-24B)
   TBS = 2K - 72         two blocks of K (B' = 2K, no filler)
   TBS = 12152           K- = 6080 (quarter fold) and K+ = 6144 (32-fold) in one codeword, no filler
-and the flagship shape itself (C3: 6 blocks of 6144 on both codewords)."""
+and the flagship shape itself (C3: 6 blocks of 6144 on both codewords).
+
+The exhaustive form (all 188 block sizes, every K- / K+ pair) is tests/test_gpu_enc_sweep.py."""
 import numpy as np
 import pytest
 

@@ -160,6 +160,18 @@ int oai4g_rsc_scan_rows(uint32_t q, uint32_t rows[6]);
  * out of range. */
 int oai4g_rm_pair_schedule(uint32_t C, uint32_t n0, const uint32_t nt[2], const uint32_t wrapt[2],
                            uint32_t *pairs, uint32_t *pair0);
+/* The fused modulator's item map, host-side.  Its persistent workgroups walk a flat item space that is
+ * dense over the symbols lz .. lz + per - 1 of every subframe (the lz leading symbols that carry nothing
+ * at any subframe index are no items), ips items per symbol (2 with four antennas: one per antenna
+ * pair): item -> sf = item / ips / per, l = lz + item / ips % per, pair = item % ips.  Workgroup b of a
+ * grid of g takes items (b + k g) u .. + u - 1 for k = 0, 1, ... (u = 2048 / N transforms per
+ * workgroup).  Returns 1 when the item also zero-fills symbols 0 .. lz - 1 of its subframe (l == lz > 0),
+ * else 0; < 0 for arguments out of range (ips 1 or 2, lz <= 4, per >= 1). */
+int oai4g_mod_item_map(uint32_t item, uint32_t ips, uint32_t lz, uint32_t per, uint32_t *sf, uint32_t *l,
+                       uint32_t *pair);
+/* Test hook: at most n_workgroups in the fused modulator's grid, so that small batches run many rounds
+ * per workgroup and a ragged last round; 0 restores the default (workgroups per CU x CUs). */
+void oai4g_set_modofdm_grid_cap(int n_workgroups);
 
 /* ---------------- drop-in entry points (GPU compute on host buffers) ---------------- */
 /* crc24a / crc24b (PHY/CODING/crc_byte.c:117 / :135): returns crc << 8 */
@@ -670,6 +682,9 @@ int oai4g_tx_modulate(const oai4g_tx_config_t *cfg, int n_sf, const void *d_work
  * the static REs of oai4g_tx_config_set_control / _set_common keeps every value of the leaf, 64-,
  * 256-, 1024- and 2048-levels inside int16 with a margin; those calls re-check it. */
 int oai4g_tx_mod_nosat(const oai4g_tx_config_t *cfg);
+/* The configuration's lz of oai4g_mod_item_map: its leading symbols without data REs, CRS or static REs at
+ * every subframe index (0 with CRS or a control region; set_control / set_common re-derive it). */
+int oai4g_tx_mod_lz(const oai4g_tx_config_t *cfg);
 
 /* Diagnostics: average ms of the encoder kernel stopped after phase `stop_phase`
  * (0 load+Gold, 1 CRC, 2 segmentation, 3 turbo, 4 w build, 99 = complete).  Outputs invalid. */

@@ -338,6 +338,11 @@ _SIGS = {
     "oai4g_rm_pair_schedule": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32),
                                               ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
                                               ctypes.POINTER(ctypes.c_uint32)]),
+    "oai4g_mod_item_map": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                          ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
+                                          ctypes.POINTER(ctypes.c_uint32)]),
+    "oai4g_set_modofdm_grid_cap": (None, [ctypes.c_int]),
+    "oai4g_tx_mod_lz": (ctypes.c_int, [ctypes.c_void_p]),
 }
 
 
@@ -1463,6 +1468,11 @@ class TxPipeline:
     @property
     def mod_nosat(self):
         return bool(self.L.oai4g_tx_mod_nosat(self.cfg))
+
+    @property
+    def mod_lz(self):
+        """Leading symbols the modulator's item space skips (oai4g_mod_item_map)."""
+        return self.L.oai4g_tx_mod_lz(self.cfg)
 
     def sync(self):
         _check(self.L.oai4g_sync() == 0)

@@ -611,6 +611,40 @@ static int packed_iq_max(const std::vector<uint32_t> &t)
   return v;
 }
 
+/* k_modofdm's dense item space (oai4g_internal.h oai4g_mod_item): mod_lz = the leading symbols that are
+ * empty at every subframe index: no data REs, in a grid without static REs.  With CRS (symbol 0 carries
+ * it) or the static REs of set_control / set_common (a PCFICH sits in symbol 0) it is 0, and the kernels
+ * for such grids are compiled for that; re-run wherever those change. */
+static void mod_items_setup(cfg_dev_t &h)
+{
+  uint32_t lz = 0;
+  if (!h.with_crs && !h.ctl_on)
+    for (; lz < OAI4G_MOD_LZ_MAX && lz + 1 < h.nsymb / 2; lz++) {
+      bool empty = true;
+      for (int sf = 0; sf < 10 && empty; sf++) empty = h.symnre[sf][lz] == 0;
+      if (!empty) break;
+    }
+  h.mod_lz = lz;
+  h.mod_per = h.nsymb - lz;
+  h.mod_permag = oai4g_mod_permag(h.mod_per);
+}
+
+/* the item map as k_modofdm and its launch use it (include/oai4g.h).  Plain host arithmetic, no device. */
+extern "C" int oai4g_mod_item_map(uint32_t item, uint32_t ips, uint32_t lz, uint32_t per, uint32_t *sf, uint32_t *l,
+                                  uint32_t *pair)
+{
+  if (ips < 1 || ips > 2 || per < 1 || lz > OAI4G_MOD_LZ_MAX) return -1;
+  const oai4g_mod_item_t m = oai4g_mod_item(item, ips, lz, per, oai4g_mod_permag(per));
+  *sf = m.sf;
+  *l = m.l;
+  *pair = m.pair;
+  return m.l == lz && lz > 0 ? 1 : 0;
+}
+
+/* test hook: at most n workgroups in k_modofdm's persistent grid (0: the occupancy default) */
+int g_modofdm_grid_cap = 0;
+extern "C" void oai4g_set_modofdm_grid_cap(int n_workgroups) { g_modofdm_grid_cap = n_workgroups > 0 ? n_workgroups : 0; }
+
 /* ------------------------------------------------------------------------------------------
  * RE map: restatement of dlsch_modulation's control flow (dlsch_modulation.c:1258-1493 and
  * allocate_REs_in_RB :139-249, 745-748) producing, per symbol, the data-RE order.
@@ -1344,6 +1378,7 @@ static int upload_cfg(oai4g_tx_config *cfg)
   if (upload_gold(cfg) != 0) return -1;
   cfg->h.with_crs = !cfg->h_crs.empty();
   cfg->h.mod_nosat = mod_nosat_ok(cfg->h, std::max(packed_iq_max(cfg->h_crs), cfg->ctl_vmax));
+  mod_items_setup(cfg->h);
   cfg->h.n_cu = (uint32_t)g_n_cu;
   cfg->h.gold_x1 = g_gx1;
   cfg->h.gold_x2j = g_gx2j;
@@ -1498,6 +1533,7 @@ extern "C" int oai4g_tx_modulate(const oai4g_tx_config_t *cfg, int n_sf, const v
 }
 
 extern "C" int oai4g_tx_mod_nosat(const oai4g_tx_config_t *cfg) { return cfg ? (int)cfg->h.mod_nosat : 0; }
+extern "C" int oai4g_tx_mod_lz(const oai4g_tx_config_t *cfg) { return cfg ? (int)cfg->h.mod_lz : -1; }
 
 /* Diagnostics: time the encoder with an early exit after phase `stop_phase`
  * (0 load/Gold, 1 CRC, 2 segmentation, 3 turbo, 4 w build, 99 full). Outputs are invalid. */
@@ -3222,6 +3258,7 @@ static int rebuild_static(oai4g_tx_config_t *cfg)
     cfg->h_ctl = std::move(tab);
   }
   cfg->h.mod_nosat = mod_nosat_ok(cfg->h, std::max(packed_iq_max(cfg->h_crs), cfg->ctl_vmax));
+  mod_items_setup(cfg->h);
   if (upload_remap(cfg) != 0) return -1;
   HCK(hipMemcpy(cfg->d, &cfg->h, sizeof(cfg_dev_t), hipMemcpyHostToDevice), -1);
   return 0;

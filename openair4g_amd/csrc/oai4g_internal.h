@@ -40,6 +40,26 @@ static constexpr uint32_t oai4g_mod_addr_mask(uint32_t shift) { return 0x7FFFu &
 static constexpr uint32_t oai4g_mod_sentinel(uint32_t N) { return (3u * N) / 4u; }
 /* a symbol's data REs are staged in quads: the last quad must end below the sentinel */
 static constexpr bool oai4g_mod_nre_fits(uint32_t nre, uint32_t N) { return nre + 3u <= oai4g_mod_sentinel(N); }
+/* k_modofdm's item space is dense over the symbols that can carry anything: the lz leading symbols that
+ * are empty at every subframe index (the control region of a grid without CRS or control signals) are
+ * no items.  Item -> (subframe, symbol, antenna pair): ips items per symbol (2 in the 4-port kernel),
+ * per = nsymb - lz symbols per subframe, permag = ceil(2^32 / per) (oai4g_mod_permag): the quotient is
+ * exact while n_sf per^2 <= 2^32 (launch-checked).  The item with l == lz also zero-fills symbols
+ * 0 .. lz - 1 of its subframe (its antenna pair's planes with ips = 2, else every antenna's). */
+struct oai4g_mod_item_t {
+  uint32_t sf, l, pair;
+};
+static constexpr uint32_t oai4g_mod_permag(uint32_t per) { return (uint32_t)(((1ull << 32) + per - 1) / per); }
+static inline __host__ __device__ oai4g_mod_item_t oai4g_mod_item(uint32_t item, uint32_t ips, uint32_t lz, uint32_t per,
+                                                                  uint32_t permag)
+{
+  const uint32_t it = item / ips;
+  const uint32_t sf = (uint32_t)(((uint64_t)it * permag) >> 32);
+  return {sf, lz + it - sf * per, item - it * ips};
+}
+/* leading symbols that may be skipped at most: the fill region [0, body of symbol lz - CP) of an antenna
+ * plane stays inside slot 0 for either prefix type */
+#define OAI4G_MOD_LZ_MAX 4u
 #define OAI4G_ENC_CRC_TABLE_WORDS (256 + 256) /* byte tables A/B (the combine multipliers stay in global memory;
                                                   slice-by-4 tables, 2048 words, cost one workgroup per CU: slower) */
 #define OAI4G_GOLD_LANES 256
@@ -170,8 +190,10 @@ struct cfg_dev_t {
   uint32_t lds_a_words;         /* region A: TB + CRC tables (0-2) | interleaved words (3) | packed w (4) */
   uint32_t lds_b_words;         /* region B: constituent streams */
   uint32_t mod_nosat;            /* 1: k_modofdm may take the fused IDFT levels (oai4g_host.cpp mod_nosat_ok) */
-  uint32_t pad;
-  uint32_t crctab[2][256];      /* CRC byte tables (crc_byte.c:98-105): [0] CRC-24A, [1] CRC-24B */
+  /* k_modofdm's dense item space (oai4g_mod_item): leading symbols that are no items, nsymb - mod_lz,
+   * ceil(2^32 / mod_per); set by oai4g_host.cpp mod_items_setup wherever the static REs change */
+  uint32_t mod_lz, mod_per, mod_permag;
+  uint32_t crctab[2][256];     /* CRC byte tables (crc_byte.c:98-105): [0] CRC-24A, [1] CRC-24B */
   cw_dev_t cw[2];
   uint32_t symbase[10][14];     /* data REs before symbol l */
   uint32_t symnre[10][14];      /* data REs in symbol l (32-bit: the modulator reads it with a scalar load) */
@@ -273,6 +295,7 @@ hipError_t oai4g_launch_rm_rx(const int16_t *d_soft, uint32_t E, int16_t *d_w, c
 hipError_t oai4g_launch_subblock_deint(uint32_t D, int16_t *d_dfull, const int16_t *d_w, hipStream_t s);
 
 /* OFDM path */
+extern int g_modofdm_grid_cap;   /* oai4g_set_modofdm_grid_cap (oai4g_host.cpp): > 0 caps k_modofdm's grid */
 hipError_t oai4g_launch_modofdm(const cfg_dev_t *d_cfg, const cfg_dev_t *h_cfg, int sf0, int n_sf,
                                 const uint32_t *d_ebits, int32_t *d_iq, hipStream_t s);
 struct ofdm_sym_t {

@@ -904,10 +904,8 @@ __global__ void __launch_bounds__(128) MODOFDM_ATTR k_modofdm(const cfg_dev_t *_
   const int unit = threadIdx.x / T, t = threadIdx.x % T;
   typename idft_sel<LOG2N>::tw_t twr;
   twr.load(c->tw, t);
-  /* symbols per subframe as a constant (the launch checks cfg nsymb): the item -> (subframe, symbol)
-   * split is a multiply-high, not a run-time division per item */
+  /* symbols per slot as a constant (the launch checks cfg nsymb) */
   const uint32_t n_ant = c->n_ant;
-  constexpr uint32_t nsymb = ECP ? 12u : 14u;
   constexpr uint32_t sps = ECP ? 6 : 7;
   for (uint32_t i = threadIdx.x; i < 4 * QROW + 1; i += blockDim.x) {
     const uint32_t row = i / QROW, bits = i - row * QROW, cw = row >> 1, pil = row & 1;
@@ -944,6 +942,12 @@ __global__ void __launch_bounds__(128) MODOFDM_ATTR k_modofdm(const cfg_dev_t *_
    * (lgkmcnt) instead of vector loads the IQ stores would otherwise order behind (shared vmcnt) */
   typedef const __attribute__((address_space(4))) cfg_dev_t ccfg_t;
   const ccfg_t *cc = (const ccfg_t *)c;
+  /* an item is a (subframe, symbol >= lz[, antenna pair]) of the dense item space (oai4g_mod_item): the
+   * split is a multiply-high by a host constant, not a run-time division per item.  A grid with static
+   * REs skips nothing (host rule, launch-checked): those kernels keep constants, and their registers */
+  constexpr uint32_t nsymb = ECP ? 12u : 14u;
+  const uint32_t lz = CRS ? 0u : cc->mod_lz, per = CRS ? nsymb : cc->mod_per;
+  const uint32_t permag = CRS ? oai4g_mod_permag(nsymb) : cc->mod_permag;
   auto fetch = [&](int bse) {
     /* one unit per workgroup: unit is 0, and the item is a scalar from the start (act, nre and the
      * staging offsets become scalar too) */
@@ -951,9 +955,9 @@ __global__ void __launch_bounds__(128) MODOFDM_ATTR k_modofdm(const cfg_dev_t *_
     const bool act = item < n_items;
     /* one unit per workgroup: the item is wave-uniform, so its table reads become scalar loads and
      * the next item's vector loads need no wait before their use */
-    const uint32_t it0 = (act ? (uint32_t)item : 0u) / IPS;
-    const uint32_t it = UNITS == 1 ? __builtin_amdgcn_readfirstlane(it0) : it0;
-    const uint32_t sf = it / nsymb, l = it - sf * nsymb;
+    const uint32_t it0 = act ? (uint32_t)item : 0u;
+    const oai4g_mod_item_t m = oai4g_mod_item(UNITS == 1 ? __builtin_amdgcn_readfirstlane(it0) : it0, IPS, lz, per, permag);
+    const uint32_t sf = m.sf, l = m.l;
     const uint32_t sfi = (cc->first_sf + (sf0 + sf) * cc->sf_step) % 10;
     const uint32_t nre_u = cc->symnre[sfi][l], re0 = cc->symbase[sfi][l];   /* uniform: scalar loads */
     const uint32_t nre = act ? nre_u : 0u;
@@ -983,9 +987,10 @@ __global__ void __launch_bounds__(128) MODOFDM_ATTR k_modofdm(const cfg_dev_t *_
   for (int base = blockIdx.x * UNITS; base < n_items; base += stride) {
     const int item = base + (UNITS == 1 ? 0 : unit);
     const bool active = item < n_items;
-    const uint32_t it0 = (active ? (uint32_t)item : 0u) / IPS, pair = (uint32_t)item % IPS;
+    const uint32_t it0 = active ? (uint32_t)item : 0u;
     const uint32_t it = UNITS == 1 ? __builtin_amdgcn_readfirstlane(it0) : it0;
-    const uint32_t sf = it / nsymb, l = it - sf * nsymb;
+    const oai4g_mod_item_t m = oai4g_mod_item(it, IPS, lz, per, permag);
+    const uint32_t sf = m.sf, l = m.l, pair = m.pair;
     const uint32_t sfi = (cc->first_sf + (sf0 + sf) * cc->sf_step) % 10;
     const uint32_t nre_u = cc->symnre[sfi][l], re0 = cc->symbase[sfi][l];
     const uint32_t nre = active ? nre_u : 0u;
@@ -998,6 +1003,19 @@ __global__ void __launch_bounds__(128) MODOFDM_ATTR k_modofdm(const cfg_dev_t *_
     const uint32_t body = slot * (cc->spt >> 1) + (si == 0 ? cc->cp0 : (N + cc->cp0) + (si - 1) * (N + cc->cp) + cc->cp);
     const int cp = (int)(si == 0 ? cc->cp0 : cc->cp);
     uint32_t *dst0 = (uint32_t *)iq + (size_t)sf * n_ant * cc->spt + body;
+
+    /* symbols 0 .. lz - 1 are no items: the item of symbol lz zero-fills them, prefixes included, in its
+     * antenna pair's planes (MODE 3) or every antenna's.  They are the plane's words [0, CP start of
+     * symbol lz), inside slot 0 (lz < sps); planes start 8-byte aligned (spt even, iq host-checked).
+     * Here, where no load is in flight, not behind the item's IQ stores (measured: DESIGN.md) */
+    if (lz && l == lz && active) {
+      const uint32_t fl = body - (uint32_t)cp;
+      for (uint32_t a = MODE == 3 ? 2 * pair : 0; a < (MODE == 3 ? 2 * pair + 2 : n_ant); a++) {
+        uint32_t *d = (uint32_t *)iq + ((size_t)sf * n_ant + a) * cc->spt;
+        for (uint32_t f = t; f < fl / 2; f += T) ((u32x2_t *)d)[f] = (u32x2_t){0u, 0u};
+        if ((fl & 1u) && t == 0) d[fl - 1] = 0u;
+      }
+    }
 
     if (UNITS == 1 && nre == 0 && !(CRS && stat_sym)) {
       /* control-region symbol: the transform of an all-zero grid is zero */
@@ -1309,6 +1327,7 @@ static hipError_t launch_modofdm_t(const cfg_dev_t *d_cfg, const cfg_dev_t *h_cf
   }
   const int units = modofdm_geom<LOG2N>::UNITS;
   int want = (n_items + units - 1) / units, cap = occ * (int)h_cfg->n_cu;
+  if (g_modofdm_grid_cap > 0 && g_modofdm_grid_cap < cap) cap = g_modofdm_grid_cap;   /* test hook, per launch */
   int grid = want < cap ? want : cap;
   if (grid < 1) grid = 1;
   hipLaunchKernelGGL((k_modofdm<LOG2N, MODE, CRS, ECP, NS>), dim3(grid), dim3(128), 0, s, d_cfg, n_items, d_ebits, d_iq,
@@ -1360,7 +1379,13 @@ hipError_t oai4g_launch_modofdm(const cfg_dev_t *d_cfg, const cfg_dev_t *h_cfg, 
 {
   if (n_sf <= 0) return hipSuccess;
   if (h_cfg->nsymb != 12 && h_cfg->nsymb != 14) return hipErrorInvalidValue;   /* k_modofdm: 12 <=> ECP */
-  const int n_items = n_sf * (int)h_cfg->nsymb;
+  /* the dense item space (oai4g_mod_item): mod_per symbols per subframe; its multiply-high split is exact
+   * while n_sf per^2 <= 2^32; the bound 2^30 also keeps twice the items (4-port kernel) inside an int */
+  const uint32_t lz = h_cfg->mod_lz, per = h_cfg->mod_per;
+  if (lz > OAI4G_MOD_LZ_MAX || lz >= h_cfg->nsymb / 2 || per != h_cfg->nsymb - lz || h_cfg->mod_permag != oai4g_mod_permag(per) ||
+      (uint64_t)n_sf * per * per > (1ull << 30) || (lz && ((h_cfg->spt & 1u) || h_cfg->with_crs || h_cfg->ctl_on)))
+    return hipErrorInvalidValue;
+  const int n_items = n_sf * (int)per;
   d_ebits += (size_t)sf0 * h_cfg->n_cw * h_cfg->ebits_words;
   d_iq += (size_t)sf0 * h_cfg->n_ant * h_cfg->spt;
   /* two antenna transforms per unit only when they differ (LARGE_CDD, ALAMOUTI); TM1 stores one

@@ -1130,6 +1130,11 @@ class UlDecodeBatch:
         self.d_it = self.L.oai4g_dev_alloc(n_tb * self.C)
         _check(bool(self.d_e) and bool(self.d_c) and bool(self.d_it))
 
+    def set_decoder(self, bits):
+        """16: phy_threegpplte_turbo_decoder16 (the default); 8: the 8-bit decoder, for one block size
+        K % 16 == 0, K >= 512 (raises otherwise).  The scratch is reallocated on the next launch."""
+        _check(self.L.oai4g_ul_config_set_decoder(self.cfg, bits) == 0)
+
     def E(self, r):
         return self.L.oai4g_ul_config_E(self.cfg, r)
 

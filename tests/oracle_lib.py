@@ -555,12 +555,14 @@ def chest_subframe(fp, rxF, rxF_next0, sf, p=0):
     return est
 
 
-def ulsch_decode(e, B, G, Qm, rvidx=0, max_it=8, Mdlharq=8):
+def ulsch_decode(e, B, G, Qm, rvidx=0, max_it=8, Mdlharq=8, decoder=None):
     """ulsch_decoding.c:1208-1350 on one TB's soft bits e (first round): per code block r,
     generate_dummy_w(4 + K_r, F if r == 0), lte_rate_matching_turbo_rx (clear), sub-block
     deinterleaving, phy_threegpplte_turbo_decoder16 (CRC24_B if C > 1 else CRC24_A with F).
+    `decoder` replaces the 16-bit decoder (turbo_decode8 for the llr8_flag chain).
     Returns [(iterations, bytes K_r / 8)] per block."""
     import spec_model as S
+    decoder = decoder or turbo_decode
     blocks, F = S.segment([0] * B)
     C = len(blocks)
     e = np.ascontiguousarray(e, dtype=np.int16)
@@ -571,7 +573,7 @@ def ulsch_decode(e, B, G, Qm, rvidx=0, max_it=8, Mdlharq=8):
         w, E = rate_match_rx(e[off:], K, G, C, r, Qm, rvidx=rvidx, Mdlharq=Mdlharq, dw=dw)
         off += E
         d = subblock_deinterleave(w, K)
-        out.append(turbo_decode(d, K, max_it=max_it, crc_type=1 if C > 1 else 0, F=(F if C == 1 else 0)))
+        out.append(decoder(d, K, max_it=max_it, crc_type=1 if C > 1 else 0, F=(F if C == 1 else 0)))
     return out
 
 

@@ -217,37 +217,25 @@ static __device__ __forceinline__ uint32_t crc_chunk(const uint8_t *buf, uint32_
   return reg;
 }
 
-/* lane chunk CRC over 4-byte words: bytes [lane per, (lane + 1) per) of the message base8 + start
- * of nbytes bytes, virtually front-padded to nl per bytes (per % 4 == 0; the zero bytes in front
- * leave the zero register unchanged), one unaligned word read per 4 bytes.  The register is kept
- * in the top 24 bits (tab8[v] = crc_byte.c's table entry << 8), so a byte step is
- * reg = (reg << 8) ^ tab8[(reg >> 24) ^ byte]. */
-static __device__ __forceinline__ uint32_t crc_chunk_w(const uint32_t *base32, uint32_t start, uint32_t nbytes,
-                                                       uint32_t per, uint32_t lane, uint32_t nl, const uint32_t *tab8)
-{
-  const int vstart = (int)(lane * per) - (int)(per * nl - nbytes);
-  uint32_t reg = 0;
-  for (uint32_t i = 0; i < per; i += 4) {
-    const int o = vstart + (int)i;
-    const uint32_t a = start + (uint32_t)(o > 0 ? o : 0), wi = a >> 2;
-    uint32_t w = __builtin_amdgcn_alignbit(base32[wi + 1], base32[wi], (a & 3u) * 8u);
-    if (o < 0) w = o <= -4 ? 0u : w << (8 * (uint32_t)(-o));   /* bytes before the message are zero */
-    reg = (reg << 8) ^ tab8[(reg >> 24) ^ (w & 0xffu)];
-    reg = (reg << 8) ^ tab8[(reg >> 24) ^ ((w >> 8) & 0xffu)];
-    reg = (reg << 8) ^ tab8[(reg >> 24) ^ ((w >> 16) & 0xffu)];
-    reg = (reg << 8) ^ tab8[(reg >> 24) ^ (w >> 24)];
-  }
-  return reg >> 8;
-}
-
-/* crc_chunk_w for both generator polynomials at once (two independent table chains over the same
- * word reads: ra over P_A, rb over P_B), in reflected form: with r = bitrev32(reg) the MSB-first step
- * reg' = (reg << 8) ^ T8[(reg >> 24) ^ b] becomes r' = (r >> 8) ^ R[(r ^ bitrev8(b)) & 0xff],
+/* Lane chunk CRC over the systematic stream words (LDS, base32): bytes [pos per, (pos + 1) per) of the
+ * message of nbytes bytes at stream byte `start`, virtually front-padded to nl per bytes (per % 4 == 0;
+ * the zero bytes in front leave the zero register unchanged), one unaligned word read per 4 bytes.
+ * A stream byte is the message byte bit-reversed (bytes_to_seq), which is what the reflected form
+ * wants: with r = bitrev32(reg) the MSB-first step reg' = (reg << 8) ^ T8[(reg >> 24) ^ b],
+ * T8[v] = crc_byte.c's table entry << 8, becomes r' = (r >> 8) ^ R[(r ^ bitrev8(b)) & 0xff],
  * R[x] = bitrev32(T8[bitrev8(x)]).  Registers and tables are kept shifted left by 2 (r2 = r << 2,
  * R2 = R << 2), so (r2 ^ x2) & 0x3fc is the entry's byte offset (one bitop3; bits 0-1 of r2 pick up
- * bits that the next mask and shift drop): a byte step is bitop3, base add, ds_read, shift, xor --
- * four fast VALU ops against five (two of them slow: lshl, lshl_add) in crc_chunk_w's form.  Bytes of a
- * word enter in order: bitrev32 puts byte q reversed at bits 31-8q..24-8q. */
+ * bits that the next mask and shift drop): a byte step is bitop3, base add, ds_read, shift, xor.
+ * crc_chunk_w2r runs both generator polynomials at once (two independent table chains over the same
+ * word reads: ra over P_A, rb over P_B), crc_chunk_w1r one. */
+static __device__ __forceinline__ uint32_t crc_stream_word(const uint32_t *base32, uint32_t start, int o)
+{
+  const uint32_t ad = start + (uint32_t)(o > 0 ? o : 0), wi = ad >> 2;
+  uint32_t w = __builtin_amdgcn_alignbit(base32[wi + 1], base32[wi], (ad & 3u) * 8u);
+  if (o < 0) w = o <= -4 ? 0u : w << (8 * (uint32_t)(-o));   /* bytes before the message are zero */
+  return w;
+}
+
 static __device__ __forceinline__ void crc_chunk_w2r(const uint32_t *base32, uint32_t start, uint32_t nbytes,
                                                      uint32_t per, uint32_t pos, uint32_t nl, const uint8_t *r2a,
                                                      const uint8_t *r2b, uint32_t &ra, uint32_t &rb)
@@ -255,12 +243,8 @@ static __device__ __forceinline__ void crc_chunk_w2r(const uint32_t *base32, uin
   const int vstart = (int)(pos * per) - (int)(per * nl - nbytes);
   uint32_t a = 0, b = 0;
   for (uint32_t i = 0; i < per; i += 4) {
-    const int o = vstart + (int)i;
-    const uint32_t ad = start + (uint32_t)(o > 0 ? o : 0), wi = ad >> 2;
-    uint32_t w = __builtin_amdgcn_alignbit(base32[wi + 1], base32[wi], (ad & 3u) * 8u);
-    if (o < 0) w = o <= -4 ? 0u : w << (8 * (uint32_t)(-o));   /* bytes before the block are zero */
-    const uint32_t wr = __builtin_bitreverse32(w);
-    const uint32_t x[4] = {wr >> 22, wr >> 14, wr >> 6, wr << 2};
+    const uint32_t w = crc_stream_word(base32, start, vstart + (int)i);
+    const uint32_t x[4] = {w << 2, w >> 6, w >> 14, w >> 22};
 #pragma unroll
     for (int q = 0; q < 4; q++) {
       a = (a >> 8) ^ *(const uint32_t *)(r2a + ((a ^ x[q]) & 0x3fcu));
@@ -269,6 +253,26 @@ static __device__ __forceinline__ void crc_chunk_w2r(const uint32_t *base32, uin
   }
   ra = __builtin_bitreverse32(a >> 2) >> 8;
   rb = __builtin_bitreverse32(b >> 2) >> 8;
+}
+
+static __device__ __forceinline__ uint32_t crc_chunk_w1r(const uint32_t *base32, uint32_t start, uint32_t nbytes,
+                                                         uint32_t per, uint32_t pos, uint32_t nl, const uint8_t *r2a)
+{
+  const int vstart = (int)(pos * per) - (int)(per * nl - nbytes);
+  uint32_t a = 0;
+  for (uint32_t i = 0; i < per; i += 4) {
+    const uint32_t w = crc_stream_word(base32, start, vstart + (int)i);
+    const uint32_t x[4] = {w << 2, w >> 6, w >> 14, w >> 22};
+#pragma unroll
+    for (int q = 0; q < 4; q++) a = (a >> 8) ^ *(const uint32_t *)(r2a + ((a ^ x[q]) & 0x3fcu));
+  }
+  return __builtin_bitreverse32(a >> 2) >> 8;
+}
+
+/* one byte (MSB first, as in the transport block) into a reflected << 2 register */
+static __device__ __forceinline__ uint32_t crc_step_r2(uint32_t a, uint32_t byte, const uint8_t *r2)
+{
+  return (a >> 8) ^ *(const uint32_t *)(r2 + ((a ^ (__builtin_bitreverse32(byte) >> 22)) & 0x3fcu));
 }
 
 /* crc_wave_tree2 over aligned groups of lpb lanes (16, 32 or 64; pos = lane within the group), both
@@ -711,20 +715,18 @@ static __device__ void encode_codeword(const cfg_dev_t *__restrict__ c, uint32_t
   const uint32_t sfi = DEBUG ? sf : (c->first_sf + (sf0 + sf) * c->sf_step) % 10;
   /* wave-uniform: SGPRs, so the per-block stream offsets (r 3 sw) are scalar arithmetic */
   const uint32_t C = __builtin_amdgcn_readfirstlane(cw.C), sw = __builtin_amdgcn_readfirstlane(cw.stream_words);
-  /* LDS carve-up.  Region A: TB || CRC (phases 0-2), the QPP-interleaved words (phase 3), one half
-   * of the e words (phase 4).  Region B: the CRC byte tables (phases 0-1), then the constituent
-   * streams (the QPP planes in the parity slots during phase 3a). */
-  uint32_t *tbw = lds_base;
+  /* LDS carve-up.  Region A: the CRC byte tables (phases 0-1), the QPP-interleaved words (phase 3),
+   * one half of the e words (phase 4).  Region B: the constituent streams from phase 0 on (the QPP
+   * planes in the parity slots during phase 3a).  The transport block itself is never staged: phase
+   * 0 loads it straight into the systematic streams. */
   uint32_t *strm = lds_base + c->lds_a_words;
-  /* the CRC byte tables live in region B until segmentation writes the streams (phases 0-1) */
-  uint32_t *crctab_a = strm;
+  uint32_t *crctab_a = lds_base;
   uint32_t *crctab_b = crctab_a + 256;
   uint32_t *tails = strm + c->lds_b_words;
   uint32_t *crcs = tails + 2 * OAI4G_MAX_CB;             /* [0] = CRC24A, [1+r] = CRC24B of block r */
   uint32_t *red = crcs + OAI4G_MAX_CB + 2;               /* 4 per-wave partials */
   enc_tabs_t *tabs = (enc_tabs_t *)(red + 4);
   uint32_t *dbg_ebuf = (uint32_t *)(tabs + 1);          /* k_encode_debug only: the whole codeword's e words */
-  uint8_t *tbb = (uint8_t *)tbw;
   const uint32_t G = cw.G[sfi];
 
   /* block geometry as wave-uniform scalars: n0 blocks of size kk0 (kw0 words) then blocks of size
@@ -746,43 +748,95 @@ static __device__ void encode_codeword(const cfg_dev_t *__restrict__ c, uint32_t
     s0 = r == 0 ? 0u : (ki ? n0 * cb0 + (r - n0) * cb1 : r * cb0) - F8;
   };
 
-  /* ---- phase 0: TB bytes, stream words past each block's data, tables ---- */
+  /* ---- phase 0: the payload straight into the systematic streams (segmentation,
+   * lte_segmentation.c:52-166, as LSB-first words), stream words past each block's data, tables.
+   * Stream word j of block r is block bytes 4j..4j+3: filler (block 0 only), then the payload from
+   * byte s0 on, then the positions of the CRCs, which stay zero until phase 1 has them. ---- */
   const uint8_t *src = payload + (size_t)(DEBUG ? 0 : (sf * c->n_cw + cwi)) * c->payload_stride;
   const uint32_t Ab = cw.A_bytes;
   {
-    const uint32_t ct = tid, cn = nth;
-    for (uint32_t i = ct; i < c->lds_tb_words; i += cn) {
-      uint32_t v = 0;
-      if (4 * i < Ab) {
-        v = *(const uint32_t *)(src + 4 * i);
-        uint32_t valid = Ab - 4 * i;
-        if (valid < 4) v &= (1u << (8 * valid)) - 1u;
+    /* Wave w takes slab w (words 64w .. 64w + 63) of every block: a block has at most 192 words, so
+     * the lane's word j is fixed and the block loop is scalar, with the block's geometry in SGPRs.
+     * The loads of ENC_BLK blocks are issued before the first of them is stored (the phase is bound by
+     * their latency), all from a clamped address: nothing at or past byte A rounded up to 4 of the row
+     * is read.  A slab inside the block's payload bytes is then the bit reversal and one store per
+     * lane; only block 0's first slab (filler) and the slab from the block's last payload word on take
+     * the byte-exact form, under a scalar branch: everything from the row's byte A on is zero. */
+    constexpr uint32_t ENC_BLK = 6;
+    const uint32_t nsl = (kw1 + 63) >> 6;          /* slabs per block (kw0 <= kw1) */
+    const uint32_t lim = ((Ab + 3) & ~3u) - 4;     /* last row offset a 4-byte load may start at */
+    for (uint32_t sl = wave; sl < nsl; sl += nwaves) {
+      const uint32_t j0 = sl << 6, j = j0 + lane, i0 = 4 * j;
+      for (uint32_t rb = 0; rb < C; rb += ENC_BLK) {
+        uint32_t v[ENC_BLK];
+#pragma unroll
+        for (uint32_t u = 0; u < ENC_BLK; u++) {
+          const uint32_t r = rb + u;
+          v[u] = 0;
+          if (r >= C) break;
+          uint32_t fill, ncopy, s0;
+          seg_of(r, fill, ncopy, s0);
+          const uint32_t a = s0 + (i0 > fill ? i0 - fill : 0u);   /* the word's first payload byte */
+          v[u] = ld_u32_any(src + min(a, lim));
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < ENC_BLK; u++) {
+          const uint32_t r = rb + u;
+          if (r >= C) break;
+          const uint32_t kw = r < n0 ? kw0 : kw1;
+          if (j0 >= kw) continue;
+          uint32_t fill, ncopy, s0;
+          seg_of(r, fill, ncopy, s0);
+          const uint32_t nd = s0 + ncopy > Ab ? (Ab > s0 ? Ab - s0 : 0u) : ncopy;   /* payload bytes of the block */
+          const uint32_t dend = fill + nd;                                          /* at block bytes [fill, dend) */
+          uint32_t *sys = strm + r * 3 * sw;
+          if ((sl == 0 && fill != 0) || 4 * (j0 + 64) > dend) {
+            if (j < kw) {
+              const int pre = (int)fill - (int)i0, valid = (int)dend - (int)i0;
+              const uint32_t a = s0 + (pre < 0 ? (uint32_t)-pre : 0u);
+              uint32_t le = v[u] >> ((8 * (a - min(a, lim))) & 31u);      /* the clamp, undone */
+              if (pre > 0) le <<= (8 * (uint32_t)pre) & 31u;              /* filler bytes in front */
+              if (valid < 4) le &= (1u << ((8 * (uint32_t)valid) & 31u)) - 1u;
+              if (valid <= 0 || pre >= 4) le = 0;
+              sys[j] = bytes_to_seq(le);
+            }
+          } else {
+            sys[j] = bytes_to_seq(v[u]);   /* unclamped: a + 4 <= A */
+          }
+        }
       }
-      tbw[i] = v;
     }
-    if (ct == 0) crcs[0] = 0u;                    /* phase 1's XOR accumulator (C > 1) */
-    if (C > 1) {
-      for (uint32_t v = ct; v < 256; v += cn) {   /* reflected, << 2 (crc_chunk_w2r) */
-        const uint32_t iv = __builtin_bitreverse32(v) >> 24;
-        crctab_a[v] = __builtin_bitreverse32(c->crctab[0][iv] << 8) << 2;
-        crctab_b[v] = __builtin_bitreverse32(c->crctab[1][iv] << 8) << 2;
+    /* stream words past the data of each block (tail bits, read-ahead); the data words of the parity
+     * streams are fully written by the phase-3 planes / turbo */
+    for (uint32_t i = tid; i < C * 3 * 4; i += nth) {
+      const uint32_t slot = i >> 2, r = slot / 3;
+      const uint32_t w = (r < n0 ? kw0 : kw1) + (i & 3u);
+      if (w < sw) strm[slot * sw + w] = 0u;
+    }
+    if (tid == 0) crcs[0] = 0u;                    /* phase 1's XOR accumulator (C > 1) */
+    /* one table entry per thread (256 threads): reflected, << 2 (crc_chunk_w2r),
+     * R2[v] = bitrev32(T8[bitrev8(v)]) << 2.  Every load ahead of the first store: the stores go
+     * through generic pointers, which the loads behind them would wait for. */
+    {
+      const uint32_t tv = __builtin_bitreverse32(tid) >> 24, tr = tid & 127u;
+      const uint32_t ta = c->crctab[0][tv], tb = c->crctab[1][tv];
+      const uint32_t rsc_n = (&c_rsc.next[0][0])[tr], rsc_p = (&c_rsc.par[0][0])[tr];
+      const uint32_t rsc_a = (&c_rsc.apow[0][0])[tr & 63u], rsc_z = c_rsc.zs[tr & 7u];
+      crctab_a[tid] = __builtin_bitreverse32(ta << 8) << 2;
+      if (C > 1) crctab_b[tid] = __builtin_bitreverse32(tb << 8) << 2;
+      if (tid < 128) {
+        (&tabs->next[0][0])[tid] = (uint8_t)rsc_n;
+        (&tabs->par[0][0])[tid] = (uint8_t)rsc_p;
+        if (tid < 64) (&tabs->apow[0][0])[tid] = (uint8_t)rsc_a;
+        if (tid < 8) tabs->zs[tid] = rsc_z;
       }
-    } else {
-      for (uint32_t v = ct; v < 256; v += cn)     /* the register-in-the-top-24-bits form */
-        crctab_a[v] = c->crctab[0][v] << 8;
-    }
-    for (uint32_t i = ct; i < 128; i += cn) {
-      (&tabs->next[0][0])[i] = (&c_rsc.next[0][0])[i];
-      (&tabs->par[0][0])[i] = (&c_rsc.par[0][0])[i];
-      if (i < 64) (&tabs->apow[0][0])[i] = (&c_rsc.apow[0][0])[i];
-      if (i < 8) tabs->zs[i] = c_rsc.zs[i];
     }
   }
   __syncthreads();
   if (stop_phase <= 0) return;
 
   /* ---- phase 1: CRC-24A over the TB (dlsch_coding.c:296-300) and CRC-24B of every block's data
-   * bytes (lte_segmentation.c:156-166) ---- */
+   * bytes (lte_segmentation.c:156-166), read from the stream words, then spliced into them ---- */
   if (C > 1) {
     /* one pass for both: crc_lpb lanes per block, each lane a chunk of one block through both byte
      * tables; the groups combine their chunks per block (-> CRC-24B) and multiply the block's
@@ -794,7 +848,8 @@ static __device__ void encode_codeword(const cfg_dev_t *__restrict__ c, uint32_t
       seg_of(r, fill, n, s0);
       if (s0 + n > Ab) n = Ab > s0 ? Ab - s0 : 0;
       uint32_t ra, rb;
-      crc_chunk_w2r(tbw, s0, n, per, pos, lpb, (const uint8_t *)crctab_a, (const uint8_t *)crctab_b, ra, rb);
+      crc_chunk_w2r(strm, 4 * (r * 3 * sw) + fill, n, per, pos, lpb, (const uint8_t *)crctab_a, (const uint8_t *)crctab_b, ra,
+                    rb);
       crc_group_tree2(ra, rb, pos, lpb, cw.crc2_cb[0], cw.crc2_cb[1]);
       if (pos == 0) {
         crcs[1 + r] = rb;
@@ -802,50 +857,59 @@ static __device__ void encode_codeword(const cfg_dev_t *__restrict__ c, uint32_t
       }
     }
     __syncthreads();
+    /* the splice: a block's CRC-24B is its stream bits [K - 24, K) (one writer per block: lane r + 1
+     * for block r < C - 1, thread 0 for the last); LSB first it is bitrev32(crc << 8) */
+    if (tid >= 1 && tid < C) {
+      const uint32_t r = tid - 1;
+      const uint32_t v = __builtin_bitreverse32(crcs[1 + r] << 8);
+      uint8_t *p = (uint8_t *)(strm + r * 3 * sw) + ((r < n0 ? kk0 : kk1) >> 3) - 3;
+      p[0] = (uint8_t)v;
+      p[1] = (uint8_t)(v >> 8);
+      p[2] = (uint8_t)(v >> 16);
+    }
     if (tid == 0) {
-      const uint32_t crc = crcs[0];
-      tbb[Ab] = (uint8_t)(crc >> 16);
-      tbb[Ab + 1] = (uint8_t)(crc >> 8);
-      tbb[Ab + 2] = (uint8_t)crc;
       /* the TB-CRC bytes end the last block's data (lte_segmentation.c: the last block copies the
-       * TB through its CRC-24A), folded into its CRC-24B through the reflected LDS table
-       * (crc_chunk_w2r's register form) */
+       * TB through its CRC-24A), folded into its CRC-24B through the reflected LDS table */
+      const uint32_t crc = crcs[0];
       uint32_t a = __builtin_bitreverse32(crcs[C] << 8) << 2;
       const uint8_t *r2b = (const uint8_t *)crctab_b;
-      a = (a >> 8) ^ *(const uint32_t *)(r2b + ((a ^ (__builtin_bitreverse32(crc >> 16) >> 22)) & 0x3fcu));
-      a = (a >> 8) ^ *(const uint32_t *)(r2b + ((a ^ (__builtin_bitreverse32((crc >> 8) & 0xffu) >> 22)) & 0x3fcu));
-      a = (a >> 8) ^ *(const uint32_t *)(r2b + ((a ^ (__builtin_bitreverse32(crc & 0xffu) >> 22)) & 0x3fcu));
-      crcs[C] = __builtin_bitreverse32(a >> 2) >> 8;
+      a = crc_step_r2(a, crc >> 16, r2b);
+      a = crc_step_r2(a, (crc >> 8) & 0xffu, r2b);
+      a = crc_step_r2(a, crc & 0xffu, r2b);
+      const uint32_t va = __builtin_bitreverse32(crc << 8), vb = a >> 2;   /* a >> 2: the register, LSB first */
+      uint8_t *p = (uint8_t *)(strm + (C - 1) * 3 * sw) + (kk1 >> 3) - 6;
+      p[0] = (uint8_t)va;
+      p[1] = (uint8_t)(va >> 8);
+      p[2] = (uint8_t)(va >> 16);
+      p[3] = (uint8_t)vb;
+      p[4] = (uint8_t)(vb >> 8);
+      p[5] = (uint8_t)(vb >> 16);
     }
   } else {
-    uint32_t reg = crc_chunk_w(tbw, 0, Ab, cw.crc_per_tb, tid, nth, crctab_a);
-    reg = crc_wave_tree2(reg, cw.crc2_tb);
+    const uint32_t reg = crc_wave_tree2(crc_chunk_w1r(strm, F8, Ab, cw.crc_per_tb, tid, nth, (const uint8_t *)crctab_a), cw.crc2_tb);
     if (lane == 0) red[wave] = reg;
     __syncthreads();
     if (tid == 0) {
       uint32_t v01 = crc_mul_tab(red[0], cw.crcmul_tb[6][0]) ^ red[1];
       uint32_t v23 = crc_mul_tab(red[2], cw.crcmul_tb[6][0]) ^ red[3];
       uint32_t crc = crc_mul_tab(v01, cw.crcmul_tb[7][0]) ^ v23;
-      tbb[Ab] = (uint8_t)(crc >> 16);
-      tbb[Ab + 1] = (uint8_t)(crc >> 8);
-      tbb[Ab + 2] = (uint8_t)crc;
+      const uint32_t va = __builtin_bitreverse32(crc << 8);
+      uint8_t *p = (uint8_t *)strm + F8 + Ab;
+      p[0] = (uint8_t)va;
+      p[1] = (uint8_t)(va >> 8);
+      p[2] = (uint8_t)(va >> 16);
+      if (DEBUG) crcs[0] = crc;
     }
   }
   __syncthreads();
-  if (DEBUG && dbg.b)
-    for (uint32_t i = tid; i < Ab + 3; i += nth) dbg.b[i] = tbb[i];
-  if (stop_phase <= 1) return;
-
-  /* stream words past the data of each block (tail bits, read-ahead; region B held the CRC tables
-   * until here); the data words are fully written by segmentation (systematic) and the phase-3
-   * planes / turbo (parity) */
-  /* ---- phase 2: segmentation -> systematic streams (LSB-first words), one word per thread over
-   * the words of all blocks; a word inside the copied bytes is one unaligned 4-byte read ---- */
-  for (uint32_t i = tid; i < C * 3 * 4; i += nth) {
-    const uint32_t slot = i >> 2, r = slot / 3;
-    const uint32_t w = (r < n0 ? kw0 : kw1) + (i & 3u);
-    if (w < sw) strm[slot * sw + w] = 0u;
+  if (DEBUG && dbg.b) {   /* b = TB || CRC-24A in the reference's layout */
+    for (uint32_t i = tid; i < Ab; i += nth) dbg.b[i] = src[i];
+    if (tid < 3) dbg.b[Ab + tid] = (uint8_t)(crcs[0] >> (8 * (2 - tid)));
   }
+  /* the systematic streams are complete: stop_phase 1 and 2 (there was a segmentation pass between them) both cut here */
+  if (stop_phase <= 2) return;
+
+  /* flattened word i over all blocks -> block r, word j, block size K, size index (phase 3a's units) */
   auto unit_of = [&](uint32_t i, uint32_t &r, uint32_t &j, uint32_t &K, uint32_t &ki) {
     ki = i >= u0 ? 1u : 0u;
     const uint32_t ii = ki ? i - u0 : i, kw = ki ? kw1 : kw0;
@@ -854,43 +918,6 @@ static __device__ void encode_codeword(const cfg_dev_t *__restrict__ c, uint32_t
     r = ki ? n0 + rr : rr;
     K = ki ? kk1 : kk0;
   };
-  for (uint32_t i = tid; i < nw; i += nth) {
-    uint32_t r, j, K, ki;
-    unit_of(i, r, j, K, ki);
-    uint32_t fill, ncopy, s0;
-    seg_of(r, fill, ncopy, s0);
-    const uint32_t i0 = 4 * j;
-    uint32_t le;
-    if (i0 >= fill) {
-      /* the data bytes as one unaligned read; a block's last word (or two) also takes the CRC-24B
-       * bytes from byte sh = fill + ncopy - i0 on, spliced in without a byte loop (bytes past the
-       * block are masked off below) */
-      const uint32_t a = s0 + i0 - fill, wi = a >> 2;
-      le = __builtin_amdgcn_alignbit(tbw[wi + 1], tbw[wi], (a & 3u) * 8u);
-      const int sh = (int)(fill + ncopy) - (int)i0;
-      if (C > 1 && sh < 4) {                                   /* sh in [-2, 3] */
-        const uint32_t crcle = __builtin_bswap32(crcs[1 + r] << 8);   /* CRC bytes MSB first */
-        const uint32_t cw32 = (uint32_t)(((uint64_t)crcle << (8 * (sh + 4))) >> 32);
-        le = (sh > 0 ? le & (0xffffffffu >> (32 - 8 * sh)) : 0u) | cw32;
-      }
-    } else {
-      const uint32_t crcb = C > 1 ? crcs[1 + r] : 0;
-      le = 0;
-      for (uint32_t q = 0; q < 4; q++) {
-        const uint32_t ib = i0 + q;
-        uint32_t byte = 0;
-        if (ib < fill) byte = 0;
-        else if (ib < fill + ncopy) byte = tbb[s0 + ib - fill];
-        else if (C > 1 && ib < fill + ncopy + 3) byte = (crcb >> (8 * (2 - (ib - fill - ncopy)))) & 0xffu;
-        le |= byte << (8 * q);
-      }
-    }
-    uint32_t wv = bytes_to_seq(le);
-    if (32 * (j + 1) > K) wv &= (1u << (K - 32 * j)) - 1u;
-    strm[r * 3 * sw + j] = wv;
-  }
-  __syncthreads();
-  if (stop_phase <= 2) return;
 
   /* ---- phase 3a: QPP-interleaved input words of every block, folded by quarters.  With
    * Q = K/4, Pi(k + qQ) = Pi(k) + q c4 (mod K), so one walk over k < Q reads output bits k, k+Q,

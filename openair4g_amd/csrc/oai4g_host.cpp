@@ -1171,7 +1171,7 @@ static int derive_cfg(oai4g_tx_config *cfg, const oai4g_tx_params_t *p, const ui
   h.lds_w_words = max_w;
   (void)max_inw;
   /* encoder LDS regions with phase-disjoint lifetimes (see oai4g_encode.hip) */
-  h.lds_a_words = max_tb_words;
+  h.lds_a_words = OAI4G_ENC_CRC_TABLE_WORDS;   /* the CRC tables, phases 0-1 (the TB is never staged) */
   for (int cw = 0; cw < p->n_cw; cw++) {
     const cw_dev_t &c = h.cw[cw];
     /* region A also holds the interleaved words in phase 3 (the planes sit in the parity slots) */
@@ -1187,7 +1187,6 @@ static int derive_cfg(oai4g_tx_config *cfg, const oai4g_tx_params_t *p, const ui
     }
   }
   h.lds_b_words = max_stream_words;
-  if (h.lds_b_words < OAI4G_ENC_CRC_TABLE_WORDS) h.lds_b_words = OAI4G_ENC_CRC_TABLE_WORDS;   /* the CRC tables, phases 0-1 */
 
   /* RE maps */
   if (need_remap) {

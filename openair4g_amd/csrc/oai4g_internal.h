@@ -67,6 +67,13 @@ static inline __host__ __device__ oai4g_mod_item_t oai4g_mod_item(uint32_t item,
 #define OAI4G_MAX_GOLD_WORDS (OAI4G_GOLD_LANES * OAI4G_GOLD_STRIDE) /* >= (14*1200*6)/32 */
 #define OAI4G_TW_TOTAL (16 + 64 + 128 + 256 + 512 + 1024 + 2048)
 
+/* 4 bytes from any byte address of global memory (unaligned dword load) */
+typedef uint32_t __attribute__((aligned(1))) u32_a1_t;
+static __device__ __forceinline__ uint32_t ld_u32_any(const uint8_t *p)
+{
+  return *(const __attribute__((address_space(1))) u32_a1_t *)p;
+}
+
 /* twiddle table offsets (packed int16 pairs), indexed by log2 of the level size */
 static inline __host__ __device__ uint32_t oai4g_tw_offset(int log2s)
 {
@@ -183,12 +190,12 @@ struct cfg_dev_t {
   uint32_t n_cw, mimo_mode, num_pdcch, rnti, Nid_cell, first_sf, sf_step;
   uint32_t payload_stride;
   uint32_t ebits_words;         /* per codeword per subframe */
-  uint32_t lds_tb_words;        /* LDS words for TB || CRC */
+  uint32_t lds_tb_words;        /* words of TB || CRC (k_encode no longer stages it) */
   uint32_t lds_stream_words;    /* LDS words for all block streams of one codeword */
   uint32_t lds_gold_words;      /* = e-bit staging words (Gold-prefilled) */
   uint32_t lds_w_words;         /* packed sub-block interleaver output of every block */
-  uint32_t lds_a_words;         /* region A: TB + CRC tables (0-2) | interleaved words (3) | packed w (4) */
-  uint32_t lds_b_words;         /* region B: constituent streams */
+  uint32_t lds_a_words;         /* region A: CRC tables (0-1) | interleaved words (3) | half of the e words (4) */
+  uint32_t lds_b_words;         /* region B: constituent streams, from phase 0 on */
   uint32_t mod_nosat;            /* 1: k_modofdm may take the fused IDFT levels (oai4g_host.cpp mod_nosat_ok) */
   /* k_modofdm's dense item space (oai4g_mod_item): leading symbols that are no items, nsymb - mod_lz,
    * ceil(2^32 / mod_per); set by oai4g_host.cpp mod_items_setup wherever the static REs change */

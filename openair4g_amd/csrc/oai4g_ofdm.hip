@@ -843,13 +843,6 @@ struct modofdm_geom {
  * while the full grid gains 0.9 % and C4 4-6 %, profiles/mod_ab_r03_zband.txt) */
 static constexpr bool modofdm_zband(int MODE, bool CRS) { return CRS || MODE != 2; }
 
-/* 4 bytes from any byte address of global memory (unaligned dword load) */
-typedef uint32_t __attribute__((aligned(1))) u32_a1_t;
-static __device__ __forceinline__ uint32_t ld_u32_any(const uint8_t *p)
-{
-  return *(const __attribute__((address_space(1))) u32_a1_t *)p;
-}
-
 #define MODOFDM_WAVES_OF(L) (OAI4G_MODOFDM_WAVES > 0 ? OAI4G_MODOFDM_WAVES : ((L) == 11 ? 4 : 3))
 #define MODOFDM_ATTR __attribute__((amdgpu_waves_per_eu(MODOFDM_WAVES_OF(LOG2N))))
 /* MODE: 0 = TM1 (one transform stored to every antenna), 1 = ALAMOUTI, 2 = LARGE_CDD, 3 = 4-port

@@ -35,7 +35,19 @@ extern "C" {
 #define OAI4G_W_BYTES (3 * 6144 + 96)
 
 /* MIMO_mode_t subset (PHY/impl_defs_lte.h) */
-enum { OAI4G_SISO = 0, OAI4G_ALAMOUTI = 1, OAI4G_LARGE_CDD = 2 };
+enum {
+  OAI4G_SISO = 0,
+  OAI4G_ALAMOUTI = 1,
+  OAI4G_LARGE_CDD = 2,
+  /* transmission modes 4-6, one layer on two ports (dlsch_modulation.c:750-866).  All six take one
+   * branch: the precoder of an RB comes from pmi_alloc (oai4g_get_pmi), never from the mode's name */
+  OAI4G_UNIFORM_PRECODING11 = 3,
+  OAI4G_UNIFORM_PRECODING1m1 = 4,
+  OAI4G_UNIFORM_PRECODING1j = 5,
+  OAI4G_UNIFORM_PRECODING1mj = 6,
+  OAI4G_PUSCH_PRECODING0 = 7,
+  OAI4G_PUSCH_PRECODING1 = 8
+};
 /* Extension_t (PHY/MODULATION/defs.h) */
 enum { OAI4G_CYCLIC_PREFIX = 0, OAI4G_CYCLIC_SUFFIX = 1, OAI4G_ZEROS = 2, OAI4G_NONE = 3 };
 
@@ -94,6 +106,8 @@ typedef struct {
   uint8_t Nl;
   uint8_t Nlayers;
   uint8_t first_layer;
+  uint16_t pmi_alloc;                      /* modes 3..8: two precoder bits per subband (oai4g_get_pmi); in
+                                              what was padding, 0 from oai4g_new_dlsch */
 } oai4g_dl_harq_t;
 
 /* LTE_eNB_DLSCH_t (PHY/LTE_TRANSPORT/defs.h:240-274), path fields only. */
@@ -169,6 +183,12 @@ int oai4g_rm_pair_schedule(uint32_t C, uint32_t n0, const uint32_t nt[2], const 
  * else 0; < 0 for arguments out of range (ips 1 or 2, lz <= 4, per >= 1). */
 int oai4g_mod_item_map(uint32_t item, uint32_t ips, uint32_t lz, uint32_t per, uint32_t *sf, uint32_t *l,
                        uint32_t *pair);
+/* get_pmi (dlsch_modulation.c:1136): the precoder index of resource block rb.  Modes up to
+ * OAI4G_PUSCH_PRECODING1 read two bits per subband, (pmi_alloc >> 2 (rb / S)) & 3, the later modes one,
+ * (pmi_alloc >> (rb / S)) & 1; a subband is S = 1 RB at 6 PRB, 6 at 50, 8 at 100 and 4 at every other
+ * bandwidth.  pmi_alloc is the reference's 16-bit field widened to 32 bits before the shift, so a
+ * subband whose shift reaches 16 (subband 8 at 50 PRB, 8..12 at 100 PRB) reads precoder 0. */
+uint8_t oai4g_get_pmi(uint8_t N_RB_DL, uint8_t mimo_mode, uint16_t pmi_alloc, uint16_t rb);
 /* Test hook: at most n_workgroups in the fused modulator's grid, so that small batches run many rounds
  * per workgroup and a ragged last round; 0 restores the default (workgroups per CU x CUs). */
 void oai4g_set_modofdm_grid_cap(int n_workgroups);
@@ -598,7 +618,9 @@ typedef struct {
   uint8_t mode1_flag;
   uint8_t frame_type;
   uint8_t n_cw;               /* 1 (TM1) or 2 (TM3) */
-  uint8_t mimo_mode;          /* OAI4G_SISO or OAI4G_LARGE_CDD */
+  uint8_t mimo_mode;          /* OAI4G_SISO, _ALAMOUTI, _LARGE_CDD, or a single-layer precoding mode
+                                 OAI4G_UNIFORM_PRECODING11 .. OAI4G_PUSCH_PRECODING1 (one codeword, two
+                                 antennas, mode1_flag 0) */
   uint8_t num_pdcch_symbols;
   uint8_t Kmimo;
   uint8_t Mdlharq;
@@ -620,7 +642,9 @@ typedef struct {
                                  rate matching when Ncb < Kw, where the reference prints "RM condition"
                                  and emits E = 0 (lte_rate_matching.c:518-521); unlocks TM3 MCS >= 20.
                                  0 (default) keeps the reference's behaviour (config_create fails). */
-  uint32_t reserved[7];
+  uint32_t pmi_alloc;         /* modes 3..8: the harq process's pmi_alloc for every subframe of the batch
+                                 (oai4g_get_pmi); only the low 16 bits may be set */
+  uint32_t reserved[6];
 } oai4g_tx_params_t;
 
 typedef struct oai4g_tx_config oai4g_tx_config_t;

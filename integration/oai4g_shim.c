@@ -32,6 +32,7 @@ static void harq_to(LTE_DL_eNB_HARQ_t *r, oai4g_dl_harq_t *o)
   o->C = r->C;  o->Cminus = r->Cminus;  o->Cplus = r->Cplus;
   o->Kminus = r->Kminus;  o->Kplus = r->Kplus;  o->F = r->F;
   o->Nl = r->Nl;  o->Nlayers = r->Nlayers;  o->first_layer = r->first_layer;
+  o->pmi_alloc = r->pmi_alloc;
 }
 
 static void harq_from(const oai4g_dl_harq_t *o, LTE_DL_eNB_HARQ_t *r)

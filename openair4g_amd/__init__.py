@@ -22,6 +22,9 @@ MAX_CHANNEL_BITS = 14 * 1200 * 6
 D_BYTES = 96 + 12 + 3 + 3 * 6144
 W_BYTES = 3 * 6144 + 96
 SISO, ALAMOUTI, LARGE_CDD = 0, 1, 2
+# single-layer closed-loop precoding (TM4-6): the precoder of an RB comes from pmi_alloc (get_pmi)
+(UNIFORM_PRECODING11, UNIFORM_PRECODING1m1, UNIFORM_PRECODING1j, UNIFORM_PRECODING1mj, PUSCH_PRECODING0,
+ PUSCH_PRECODING1) = 3, 4, 5, 6, 7, 8
 CYCLIC_PREFIX = 0
 
 
@@ -60,7 +63,8 @@ class DlHarq(ctypes.Structure):
                 ("nb_rb", ctypes.c_uint16), ("e", u8p), ("d", u8p * MAX_SEGMENTS), ("w", u8p * MAX_SEGMENTS),
                 ("C", ctypes.c_uint32), ("Cminus", ctypes.c_uint32), ("Cplus", ctypes.c_uint32),
                 ("Kminus", ctypes.c_uint32), ("Kplus", ctypes.c_uint32), ("F", ctypes.c_uint32),
-                ("Nl", ctypes.c_uint8), ("Nlayers", ctypes.c_uint8), ("first_layer", ctypes.c_uint8)]
+                ("Nl", ctypes.c_uint8), ("Nlayers", ctypes.c_uint8), ("first_layer", ctypes.c_uint8),
+                ("pmi_alloc", ctypes.c_uint16)]
 
 
 class Dlsch(ctypes.Structure):
@@ -81,7 +85,7 @@ class TxParams(ctypes.Structure):
                 ("rb_alloc", ctypes.c_uint32 * 4), ("nb_rb", ctypes.c_uint16), ("mcs", ctypes.c_uint8 * 2),
                 ("rvidx", ctypes.c_uint8 * 2), ("q", ctypes.c_uint8 * 2), ("TBS", ctypes.c_uint32 * 2),
                 ("payload_stride", ctypes.c_uint32), ("rm_limited_buffer", ctypes.c_uint32),
-                ("reserved", ctypes.c_uint32 * 7)]
+                ("pmi_alloc", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 6)]
 
     def to_bytes(self):
         return bytes(ctypes.string_at(ctypes.addressof(self), ctypes.sizeof(self)))
@@ -341,6 +345,7 @@ _SIGS = {
     "oai4g_mod_item_map": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                           ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
                                           ctypes.POINTER(ctypes.c_uint32)]),
+    "oai4g_get_pmi": (ctypes.c_uint8, [ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint16, ctypes.c_uint16]),
     "oai4g_set_modofdm_grid_cap": (None, [ctypes.c_int]),
     "oai4g_tx_mod_lz": (ctypes.c_int, [ctypes.c_void_p]),
 }
@@ -1306,6 +1311,11 @@ FULL_ALLOC_15 = (0x7FFF, 0, 0, 0)
 FULL_ALLOC_50 = (0xFFFFFFFF, 0x3FFFF, 0, 0)
 FULL_ALLOC_25 = (0x1FFFFFF, 0, 0, 0)
 
+def get_pmi(N_RB_DL, mimo_mode, pmi_alloc, rb):
+    """get_pmi (dlsch_modulation.c:1136): the precoder index of resource block rb (host-side)."""
+    return lib().oai4g_get_pmi(N_RB_DL, mimo_mode, pmi_alloc, rb)
+
+
 def get_TBS_DL(mcs, nb_rb):
     """get_TBS_DL (lte_mcs.c:118): transport block size in BYTES, from the library's TBStable."""
     return lib().oai4g_get_TBS_DL(mcs, nb_rb)
@@ -1335,6 +1345,10 @@ CONFIGS = {
     # TM2 at 1.4 MHz, QPSK (MCS 9), 3 PDCCH symbols
     "TM2S": dict(N_RB_DL=6, nb_antennas_tx=2, mode1_flag=0, n_cw=1, mimo_mode=ALAMOUTI, num_pdcch_symbols=3,
                  mcs=(9, 0), rb_alloc=FULL_ALLOC_6, nb_rb=6, Kmimo=1),
+    # TM6: dlsim -x 6 at 20 MHz: one layer on two ports, closed-loop precoder per subband from pmi_alloc
+    # (every mode 3..8 takes the same branch), 64-QAM (MCS 22)
+    "TM6": dict(N_RB_DL=100, nb_antennas_tx=2, mode1_flag=0, n_cw=1, mimo_mode=PUSCH_PRECODING0, num_pdcch_symbols=1,
+                mcs=(22, 0), rb_alloc=FULL_ALLOC_100, nb_rb=100, Kmimo=1, pmi_alloc=0xE4B1),
 }
 
 
@@ -1363,6 +1377,7 @@ def make_params(name="C3", subframe=7, subframe_step=0, rnti=0x1234, Nid_cell=0,
     for i in range(4):
         p.rb_alloc[i] = c["rb_alloc"][i]
     p.nb_rb = c["nb_rb"]
+    p.pmi_alloc = c.get("pmi_alloc", 0)
     tbs = c.get("TBS")
     for cw in range(p.n_cw):
         p.mcs[cw] = c["mcs"][cw]

@@ -538,6 +538,10 @@ static void crc_mul_tables(uint32_t per, int levels, uint32_t poly, uint32_t (*t
 
 /* QAM tables (dlsch_modulation.c:79-103, 1223-1246).  The raw tables are int (LTE_TRANSPORT/
  * vars.h:72): the outer 64-QAM level 35393 exceeds int16 and is only narrowed after the scaling. */
+/* `alamouti` also serves the single-layer precoding modes 3..8 (:753, :758-770, :801-802, :851-852), whose
+ * arithmetic is the same: amp' = (amp_rho 23170) >> 15, a QAM level (amp' raw table) >> 15 on antenna 0
+ * and its exact rotation on antenna 1; a QPSK component +-g rotated first and scaled after,
+ * (+-g 23170) >> 15, so its two levels are kept apart (the negative one is the floor, not the negation) */
 static void qam_tables_scaled(int Qm, int16_t amp, int16_t srho_a, int16_t srho_b, bool alamouti, cw_dev_t &c)
 {
   int32_t q16[4], q64[8];
@@ -576,7 +580,8 @@ static void qam_tables_scaled(int Qm, int16_t amp, int16_t srho_a, int16_t srho_
  * Every twiddle has modulus < 1 (Q15, |t| <= 32767.7), so a value's modulus is at most (occupied
  * subcarriers of its class) x (largest input modulus) x scale, plus the truncations of the levels
  * below (< 64 in modulus).  Every transform input is a QAM word (TM1), a sign-flipped / swapped one
- * (ALAMOUTI), a CDD pair (floor((x0 + x1) / 2), +-floor((x0 - x1) / 2)) of two (LARGE_CDD) or a halved
+ * (ALAMOUTI), a QAM word and its rotation by 1, -1, j or -j (single-layer precoding: one word per RE
+ * and antenna from the same tables, so V and the bounds are ALAMOUTI's), a CDD pair (floor((x0 + x1) / 2), +-floor((x0 - x1) / 2)) of two (LARGE_CDD) or a halved
  * one (4-port CDD): components <= the largest level V of the configuration's QAM / QPSK tables,
  * modulus <= sqrt(2) V, and only 12 N_RB_DL subcarriers carry anything.  When the four bounds stay inside
  * int16 with a margin of 128, no add of those levels saturates or wraps, packs_epi32 never clamps
@@ -645,6 +650,15 @@ extern "C" int oai4g_mod_item_map(uint32_t item, uint32_t ips, uint32_t lz, uint
 int g_modofdm_grid_cap = 0;
 extern "C" void oai4g_set_modofdm_grid_cap(int n_workgroups) { g_modofdm_grid_cap = n_workgroups > 0 ? n_workgroups : 0; }
 
+/* get_pmi (dlsch_modulation.c:1136-1178).  The reference widens its uint16_t pmi_alloc to uint32_t and
+ * shifts: a shift of 16 or more (subband 8 at 50 PRB, 8..12 at 100 PRB) reads 0. */
+extern "C" uint8_t oai4g_get_pmi(uint8_t N_RB_DL, uint8_t mimo_mode, uint16_t pmi_alloc, uint16_t rb)
+{
+  const uint32_t sb = N_RB_DL == 6 ? rb : N_RB_DL == 50 ? rb / 6u : N_RB_DL == 100 ? rb >> 3 : rb >> 2;
+  const uint32_t two = mimo_mode <= OAI4G_PUSCH_PRECODING1, sh = two ? sb << 1 : sb;
+  return sh >= 32 ? 0 : (uint8_t)(((uint32_t)pmi_alloc >> sh) & (two ? 3u : 1u));
+}
+
 /* ------------------------------------------------------------------------------------------
  * RE map: restatement of dlsch_modulation's control flow (dlsch_modulation.c:1258-1493 and
  * allocate_REs_in_RB :139-249, 745-748) producing, per symbol, the data-RE order.
@@ -659,10 +673,10 @@ static int not_pilot(int pilots, int re, int nushift, int use2nd)
 }
 
 static int build_remap(const oai4g_frame_parms_t *fp, const uint32_t *rb_alloc, int num_pdcch, int subframe,
-                       int mimo_mode, uint16_t *remap /* [14][N] */, uint32_t *symbase /* [14] */,
+                       int mimo_mode, uint16_t pmi_alloc, uint16_t *remap /* [14][N] */, uint32_t *symbase /* [14] */,
                        int *re_alloc /* the reference's re_allocated */)
 {
-  const bool alm = mimo_mode == OAI4G_ALAMOUTI;
+  const bool alm = mimo_mode == OAI4G_ALAMOUTI, prec1 = oai4g_mode_prec1((uint32_t)mimo_mode);
   int ralloc = 0;
   int N = fp->ofdm_symbol_size, nsymb = fp->Ncp == 0 ? 14 : 12, half = fp->N_RB_DL >> 1;
   int use2nd = fp->mode1_flag == 1;
@@ -737,7 +751,12 @@ static int build_remap(const oai4g_frame_parms_t *fp, const uint32_t *rb_alloc, 
             }
             continue;
           }
-          remap[l * N + k] = (uint16_t)(idx | (par << 15));
+          /* single-layer precoding: the RB's precoder (:1461) instead of the CDD parity */
+          if (prec1)
+            remap[l * N + k] = (uint16_t)(idx | ((uint32_t)oai4g_get_pmi(fp->N_RB_DL, (uint8_t)mimo_mode, pmi_alloc, (uint16_t)rb)
+                                                 << OAI4G_MOD_PMI_SHIFT));
+          else
+            remap[l * N + k] = (uint16_t)(idx | (par << 15));
           idx++;
           ralloc++;
           par ^= 1;
@@ -901,10 +920,17 @@ static int derive_cfg(oai4g_tx_config *cfg, const oai4g_tx_params_t *p, const ui
     return -1;
   cfg_dev_t &h = cfg->h;
   if (p->n_cw < 1 || p->n_cw > 2) { set_err("n_cw must be 1 or 2"); return -1; }
-  if (p->mimo_mode != OAI4G_SISO && p->mimo_mode != OAI4G_LARGE_CDD && p->mimo_mode != OAI4G_ALAMOUTI) {
-    set_err("mimo_mode %u not supported (SISO, ALAMOUTI and LARGE_CDD)", p->mimo_mode);
+  const bool prec1 = oai4g_mode_prec1(p->mimo_mode);
+  if (p->mimo_mode != OAI4G_SISO && p->mimo_mode != OAI4G_LARGE_CDD && p->mimo_mode != OAI4G_ALAMOUTI && !prec1) {
+    set_err("mimo_mode %u not supported (SISO, ALAMOUTI, LARGE_CDD and the single-layer precoding modes 3..8)", p->mimo_mode);
     return -1;
   }
+  if (prec1 && (p->n_cw != 1 || p->nb_antennas_tx > 2)) {
+    set_err("single-layer precoding (mimo_mode %u) takes one codeword and at most 2 TX antennas (dlsch_modulation.c:750)",
+            p->mimo_mode);
+    return -1;
+  }
+  if (p->pmi_alloc > 0xFFFFu) { set_err("pmi_alloc %#x: only the low 16 bits may be set", p->pmi_alloc); return -1; }
   if (p->mimo_mode == OAI4G_ALAMOUTI && (p->nb_antennas_tx != 2 || p->n_cw != 1)) {
     set_err("ALAMOUTI requires 2 TX antennas and one codeword (dlsch_modulation.c:362)");
     return -1;
@@ -1137,7 +1163,8 @@ static int derive_cfg(oai4g_tx_config *cfg, const oai4g_tx_params_t *p, const ui
          * PDSCH RE count x Qm (one layer per codeword) */
         std::vector<uint16_t> tmp((size_t)14 * fp.ofdm_symbol_size);
         uint32_t sb[14];
-        int n = build_remap(&fp, p->rb_alloc, p->num_pdcch_symbols, sf, p->mimo_mode, tmp.data(), sb, nullptr);
+        int n = build_remap(&fp, p->rb_alloc, p->num_pdcch_symbols, sf, p->mimo_mode, (uint16_t)p->pmi_alloc, tmp.data(), sb,
+                            nullptr);
         G = n < 0 ? -1 : n * (int)c.Qm;
       } else {
         G = oai4g_get_G(&fp, p->nb_rb, p->rb_alloc, (uint8_t)c.Qm, Nl[cw], p->num_pdcch_symbols, 0, (uint8_t)sf);
@@ -1162,7 +1189,7 @@ static int derive_cfg(oai4g_tx_config *cfg, const oai4g_tx_params_t *p, const ui
       max_gw = gw > max_gw ? gw : max_gw;
       max_bits = (uint32_t)G > max_bits ? (uint32_t)G : max_bits;
     }
-    qam_tables_scaled((int)c.Qm, p->amp, p->sqrt_rho_a, p->sqrt_rho_b, p->mimo_mode == OAI4G_ALAMOUTI, c);
+    qam_tables_scaled((int)c.Qm, p->amp, p->sqrt_rho_a, p->sqrt_rho_b, p->mimo_mode == OAI4G_ALAMOUTI || prec1, c);
   }
   if (max_gw > OAI4G_MAX_GOLD_WORDS) { set_err("G too large"); return -1; }
   h.lds_tb_words = max_tb_words;
@@ -1194,7 +1221,7 @@ static int derive_cfg(oai4g_tx_config *cfg, const oai4g_tx_params_t *p, const ui
     cfg->h_remap.assign((size_t)10 * 14 * N, 0xFFFF);
     for (int sf = 0; sf < 10; sf++) {
       if (only_sf >= 0 && sf != only_sf) continue;
-      int n = build_remap(&fp, p->rb_alloc, p->num_pdcch_symbols, sf, p->mimo_mode,
+      int n = build_remap(&fp, p->rb_alloc, p->num_pdcch_symbols, sf, p->mimo_mode, (uint16_t)p->pmi_alloc,
                           cfg->h_remap.data() + (size_t)sf * 14 * N, h.symbase[sf], &cfg->re_alloc[sf]);
       if (n < 0) { set_err("RE map construction failed"); return -1; }
       cfg->re_count[sf] = n;
@@ -1321,9 +1348,10 @@ static int upload_remap(oai4g_tx_config *cfg)
              * (dlsch_modulation.c:733-749) and every RB of a two-port grid holds an even number of
              * data REs (12, 8 beside the 4 CRS REs, 6 / 4 in a half RB), so the parity is the index's;
              * checked here for every RE */
-            const uint32_t idx = code & 0x3FFFu, par = code >> 15;
+            const bool prec1 = oai4g_mode_prec1(cfg->h.mimo_mode);   /* precoder bits instead of a parity */
+            const uint32_t idx = code & (prec1 ? oai4g_mod_pmi_idx_mask : 0x3FFFu), par = code >> 15;
             if (pre && par != (idx & 1u)) { set_err("LARGE_CDD: CDD parity differs from the RE index parity"); return -1; }
-            code = (uint16_t)(((pre || pre1 ? 0u : par) << 15) | (idx << esh));
+            code = (uint16_t)(((pre || pre1 ? 0u : par) << 15) | (prec1 ? code & oai4g_mod_pmi_bits : 0u) | (idx << esh));
           }
           both[n + sl * N + t * 16 + k] = code < OAI4G_CTL_CODE ? code : sentinel;
         }
@@ -1410,6 +1438,10 @@ extern "C" oai4g_tx_config_t *oai4g_tx_config_create(const oai4g_tx_params_t *p)
   NEED_INIT(nullptr);
   if (p->N_RB_DL != 6 && p->N_RB_DL != 15 && p->N_RB_DL != 25 && p->N_RB_DL != 50 && p->N_RB_DL != 100) {
     set_err("batched path supports N_RB_DL 6, 15, 25, 50, 100 (IDFT 128/256/512/1024/2048)");
+    return nullptr;
+  }
+  if (oai4g_mode_prec1(p->mimo_mode) && (p->n_cw != 1 || p->nb_antennas_tx != 2 || p->mode1_flag != 0)) {
+    set_err("single-layer precoding (mimo_mode %u) requires one codeword, 2 TX antennas and mode1_flag 0", p->mimo_mode);
     return nullptr;
   }
   oai4g_tx_config *cfg = new oai4g_tx_config();
@@ -1848,6 +1880,7 @@ static void params_from_dlsch(const oai4g_frame_parms_t *fp, uint8_t num_pdcch, 
   p->sqrt_rho_b = d0->sqrt_rho_b;
   memcpy(p->rb_alloc, h0->rb_alloc, sizeof(p->rb_alloc));
   p->nb_rb = h0->nb_rb;
+  p->pmi_alloc = h0->pmi_alloc;
   p->mcs[0] = h0->mcs;
   p->rvidx[0] = h0->rvidx;
   p->TBS[0] = h0->TBS;
@@ -1878,7 +1911,8 @@ extern "C" int oai4g_dlsch_encoding(uint8_t *a, const oai4g_frame_parms_t *frame
   oai4g_tx_params_t p;
   uint8_t Nl[2];
   params_from_dlsch(frame_parms, num_pdcch_symbols, dlsch, nullptr, subframe, &p, Nl);
-  if (p.mimo_mode == OAI4G_ALAMOUTI || p.mimo_mode == OAI4G_LARGE_CDD) p.mimo_mode = OAI4G_SISO; /* coding only */
+  if (p.mimo_mode == OAI4G_ALAMOUTI || p.mimo_mode == OAI4G_LARGE_CDD || oai4g_mode_prec1(p.mimo_mode))
+    p.mimo_mode = OAI4G_SISO; /* coding only */
   if (p.N_RB_DL != 6 && p.N_RB_DL != 15 && p.N_RB_DL != 25 && p.N_RB_DL != 50 && p.N_RB_DL != 100) return -1;
   oai4g_tx_config cfg;
   int rc = derive_cfg(&cfg, &p, Nl, false, -1);
@@ -1944,8 +1978,13 @@ extern "C" int oai4g_dlsch_modulation(int32_t **txdataF, int16_t amp, uint32_t s
   p.amp = amp;
   if (p.mimo_mode == OAI4G_LARGE_CDD && !dlsch1) p.n_cw = 1;
   if (p.mimo_mode == OAI4G_ALAMOUTI) p.n_cw = 1;       /* both symbols of a pair come from dlsch0 */
-  if (p.mimo_mode != OAI4G_SISO && p.mimo_mode != OAI4G_LARGE_CDD && p.mimo_mode != OAI4G_ALAMOUTI) {
+  const bool prec1 = oai4g_mode_prec1(p.mimo_mode);
+  if (p.mimo_mode != OAI4G_SISO && p.mimo_mode != OAI4G_LARGE_CDD && p.mimo_mode != OAI4G_ALAMOUTI && !prec1) {
     set_err("dlsch_modulation: mimo_mode %u not supported", p.mimo_mode);
+    return -1;
+  }
+  if (prec1 && dlsch1) {
+    set_err("dlsch_modulation: single-layer precoding (mimo_mode %u) takes one codeword", p.mimo_mode);
     return -1;
   }
   /* coding geometry is irrelevant here; use the grid-only derivation */

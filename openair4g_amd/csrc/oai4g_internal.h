@@ -38,6 +38,18 @@ static constexpr uint32_t oai4g_mod_entry_shift(uint32_t mimo_mode, uint32_t n_a
 /* the bits of an RE code that address its entry */
 static constexpr uint32_t oai4g_mod_addr_mask(uint32_t shift) { return 0x7FFFu & ~((1u << shift) - 1u); }
 static constexpr uint32_t oai4g_mod_sentinel(uint32_t N) { return (3u * N) / 4u; }
+/* Single-layer precoding (modes 3..8, dlsch_modulation.c:750-866): a data RE's code carries its RB's
+ * precoder index (oai4g_get_pmi) in bits 12-13 and no parity, in the natural map (data index below:
+ * at most 1200 per symbol) and in the thread-major one (2-byte entries: the sentinel's offset
+ * 2 * 3N/4 = 3072 at 2048 points stays below bit 12).  Every other RE's code has precoder 0. */
+static constexpr bool oai4g_mode_prec1(uint32_t mimo_mode)
+{
+  return mimo_mode >= OAI4G_UNIFORM_PRECODING11 && mimo_mode <= OAI4G_PUSCH_PRECODING1;
+}
+#define OAI4G_MOD_PMI_SHIFT 12u
+static constexpr uint32_t oai4g_mod_pmi_bits = 3u << OAI4G_MOD_PMI_SHIFT;
+static constexpr uint32_t oai4g_mod_pmi_idx_mask = (1u << OAI4G_MOD_PMI_SHIFT) - 1u;
+static_assert(2u * (oai4g_mod_sentinel(2048) + 4u) <= (1u << OAI4G_MOD_PMI_SHIFT), "staged offsets must stay below the precoder bits");
 /* a symbol's data REs are staged in quads: the last quad must end below the sentinel */
 static constexpr bool oai4g_mod_nre_fits(uint32_t nre, uint32_t N) { return nre + 3u <= oai4g_mod_sentinel(N); }
 /* k_modofdm's item space is dense over the symbols that can carry anything: the lz leading symbols that
@@ -149,8 +161,9 @@ struct cw_dev_t {
   uint32_t roff[10][OAI4G_MAX_CB + 1];
   int16_t qam_a[8], qam_b[8];   /* amp_rho-scaled QAM levels (dlsch_modulation.c:1223-1246) */
   int16_t qpsk_a, qpsk_b;
-  /* ALAMOUTI (dlsch_modulation.c:362-546): qam_a/qam_b hold the 1/sqrt2-scaled levels
-   * (amp/sqrt2 * table >> 15) and the QPSK symbol is scaled after its sign: [pilot][+g, -g] */
+  /* ALAMOUTI (dlsch_modulation.c:362-546) and single-layer precoding (:750-866): qam_a/qam_b hold the
+   * 1/sqrt2-scaled levels (amp/sqrt2 * table >> 15) and the QPSK symbol is scaled after its sign
+   * (and after its rotation): [pilot][+g, -g] */
   int16_t alm_qpsk[2][2];
   uint32_t stream_words;        /* LDS words per stream per block (padded) */
   /* CRC tree combine (x^(8*per*2^d) mod P as 6 nibble tables of 16 entries per level) */

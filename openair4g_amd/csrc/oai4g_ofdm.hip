@@ -306,6 +306,34 @@ struct idft2048_tw_t {
   s16x2 c1024[2][3];   /* W1024^{r k2}, k2 = 2 t + h */
   s16x2 c2048[8];      /* W2048^{k1}, k1 = 2 t + h + 256 m1 at [h + 2 m1] */
   static constexpr int E2S = 264;   /* E2 words per 256-point transform j */
+  /* The two images as index expressions, used by the passes below, and from them the words of a
+   * transform's region that any pass addresses: callers may leave the rest of the last region
+   * unallocated (k_modofdm MODE 4). */
+  static constexpr int E1S = 144;   /* E1 words per leaf output k4 */
+  /* E1 word of leaf t within row k4 (pass-A stores); diag: the bank-distinct (wrong) placement */
+  static __host__ __device__ constexpr uint32_t e1_lane(uint32_t t, bool diag = false)
+  {
+    return diag ? t : 2u * (t & 31u) + ((t >> 5) & 1u) + 64u * (t >> 6);
+  }
+  /* first E1 word of pass B's b64 read (r2, p) for thread (j, k4): the pair (r3, r3 + 1) = (2p, 2p + 1) */
+  static __host__ __device__ constexpr uint32_t e1_read(uint32_t j, uint32_t k4, uint32_t r2, uint32_t p)
+  {
+    return k4 * E1S + 2u * j + 16u * r2 + 64u * p;
+  }
+  /* E2 word of out256_j[k2] */
+  static __host__ __device__ constexpr uint32_t e2_word(uint32_t j, uint32_t k2) { return (uint32_t)E2S * j + k2; }
+  static __host__ __device__ constexpr uint32_t used_words()
+  {
+    uint32_t m = 0;
+    for (uint32_t t = 0; t < 128; t++)
+      for (int d = 0; d < 2; d++) {
+        const uint32_t w = 15u * E1S + e1_lane(t, d != 0) + 1u;
+        m = w > m ? w : m;
+      }
+    const uint32_t rd = e1_read(7, 15, 3, 1) + 2u, e2 = e2_word(7, 255) + 1u;
+    m = rd > m ? rd : m;
+    return e2 > m ? e2 : m;
+  }
 
   __device__ __forceinline__ void load(const uint32_t *tw, int t)
   {
@@ -380,8 +408,8 @@ typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 /* settled and removed: a build that still passes one of these would silently get the default */
 #if defined(OAI4G_MOD_STAGE) || defined(OAI4G_MOD_PRE) || defined(OAI4G_MOD_ALIAS) || defined(OAI4G_MOD_STATTM) || \
     defined(OAI4G_MOD_STATEARLY) || defined(OAI4G_MOD_ENDSYNC) || defined(OAI4G_MOD_ZBAND) || \
-    defined(OAI4G_MOD_ZB_OPAQUE) || defined(OAI4G_MOD_W0) || defined(OAI4G_PASSC_TWONCE)
-#error "retired k_modofdm switch: OAI4G_MOD_STAGE / _PRE / _ALIAS / _STATTM / _STATEARLY / _ENDSYNC / _ZBAND / _ZB_OPAQUE / _W0 and OAI4G_PASSC_TWONCE no longer exist (DESIGN.md, measured and settled)"
+    defined(OAI4G_MOD_ZB_OPAQUE) || defined(OAI4G_MOD_W0) || defined(OAI4G_PASSC_TWONCE) || defined(OAI4G_MOD_PREC_VALU)
+#error "retired k_modofdm switch: OAI4G_MOD_STAGE / _PRE / _ALIAS / _STATTM / _STATEARLY / _ENDSYNC / _ZBAND / _ZB_OPAQUE / _W0 / _PREC_VALU and OAI4G_PASSC_TWONCE no longer exist (DESIGN.md, measured and settled)"
 #endif
 #if OAI4G_DIAG_MODOFDM != 0 && OAI4G_DIAG_MODOFDM != 1
 #error "OAI4G_DIAG_MODOFDM: only 1 (no IQ stores) remains"
@@ -403,8 +431,8 @@ template <int NA, bool PSYNC, bool NS, class Prod, class Cons2>
 static __device__ __forceinline__ void idft2048_unit(uint32_t *lds, int t, bool active, const idft2048_tw_t &tw,
                                                      Prod prod, Cons2 cons2, int scale, uint32_t dep)
 {
-  constexpr int X1W = idft2048_tw_t::X1W, E2S = idft2048_tw_t::E2S;
-  static_assert(7 * E2S + 256 <= X1W, "E2 must fit the exchange");
+  constexpr int X1W = idft2048_tw_t::X1W;
+  static_assert(idft2048_tw_t::used_words() <= X1W, "E1 and E2 must fit the exchange");
   auto sink = [&](const s16x2 (&v)[16]) {
 #pragma unroll
     for (int k = 0; k < 16; k++) asm volatile("" ::"v"(c2u(v[k])));
@@ -433,12 +461,12 @@ static __device__ __forceinline__ void idft2048_unit(uint32_t *lds, int t, bool 
   if constexpr (OAI4G_DIAG_MODCUT == 1 || OAI4G_DIAG_MODCUT == 2) return;
   if constexpr (PSYNC) IDFT_SYNC();
   if (active) {
-    const uint32_t wo = OAI4G_DIAG_PASSA ? (uint32_t)t : 2u * (t & 31) + ((t >> 5) & 1) + 64u * (t >> 6);
+    const uint32_t wo = idft2048_tw_t::e1_lane((uint32_t)t, OAI4G_DIAG_PASSA != 0);
 #pragma unroll
     for (int a = 0; a < NA; a++) {
       if constexpr (!PSYNC) idft16_reg<NA == 2, NS>(x[a], tw.l16);
 #pragma unroll
-      for (int k = 0; k < 16; k++) lds[a * X1W + k * 144 + wo] = c2u(x[a][k]);
+      for (int k = 0; k < 16; k++) lds[a * X1W + k * idft2048_tw_t::E1S + wo] = c2u(x[a][k]);
     }
   }
   IDFT_SYNC();
@@ -446,14 +474,14 @@ static __device__ __forceinline__ void idft2048_unit(uint32_t *lds, int t, bool 
   const int j = t & 7, k4 = t >> 3;
   if constexpr (OAI4G_MOD_PRIO == 2) __builtin_amdgcn_s_setprio(1);
   if (active) {
-    const uint32_t ro = (uint32_t)k4 * 144u + 2u * j;
+    const uint32_t ro = idft2048_tw_t::e1_read((uint32_t)j, (uint32_t)k4, 0, 0);
 #pragma unroll
     for (int a = 0; a < NA; a++)
 #pragma unroll
       for (int r2 = 0; r2 < 4; r2++)
 #pragma unroll
         for (int p = 0; p < 2; p++) {
-          const u32x2_t v = *(const u32x2_t *)&lds[a * X1W + ro + 16 * r2 + 64 * p];
+          const u32x2_t v = *(const u32x2_t *)&lds[a * X1W + ro + idft2048_tw_t::e1_read(0, 0, r2, p)];
           x[a][4 * r2 + 2 * p] = u2c(v.x);
           x[a][4 * r2 + 2 * p + 1] = u2c(v.y);
         }
@@ -462,7 +490,7 @@ static __device__ __forceinline__ void idft2048_unit(uint32_t *lds, int t, bool 
   if constexpr (OAI4G_MOD_PRIO == 2 || OAI4G_MOD_PRIO == 6) __builtin_amdgcn_s_setprio(0);
   if (active) {
     /* E2 word of out256_j[k2] = E2S j + k2, k2 = k4 + 16 m3 + 64 m2: an affine base plus immediates */
-    const uint32_t wb = (uint32_t)E2S * j + k4;
+    const uint32_t wb = idft2048_tw_t::e2_word((uint32_t)j, (uint32_t)k4);
     const twp_t w64[3] = {tw_use(tw.b64[0], dep), tw_use(tw.b64[1], dep), tw_use(tw.b64[2], dep)};
 #pragma unroll
     for (int a = 0; a < NA; a++) {
@@ -517,7 +545,7 @@ static __device__ __forceinline__ void idft2048_unit(uint32_t *lds, int t, bool 
       s16x2 v[2][8];   /* [h][j] */
 #pragma unroll
       for (int jj = 0; jj < 8; jj++) {
-        const u32x2_t q = *(const u32x2_t *)&lds[a * X1W + E2S * jj + 2 * t];
+        const u32x2_t q = *(const u32x2_t *)&lds[a * X1W + idft2048_tw_t::e2_word(jj, 2 * t)];
         v[0][jj] = u2c(q.x);
         v[1][jj] = u2c(q.y);
       }
@@ -791,6 +819,24 @@ static __device__ __forceinline__ void alm_pair(s16x2 ta, s16x2 tb, uint32_t rol
   y1 = role ? (s16x2){ta.x, (short)-ta.y} : tb;
 }
 
+/* Single-layer precoding, modes 3..8 (dlsch_modulation.c:750-866, layer1prec2A :108-137): antenna 0
+ * carries the ALAMOUTI-scaled symbol (alm_ta), antenna 1 that symbol times 1, -1, j, -j for precoder
+ * 0..3: (re, im), (-re, -im), (-im, re), (im, -re).  A QAM level is negated exactly (int16 wrap); a QPSK
+ * component is rotated as +-g and scaled after, so negating swaps the two stored levels
+ * ((g 23170) >> 15 and (-g 23170) >> 15, the floor) instead of changing the sign. */
+static __device__ __forceinline__ s16x2 prec1_tb(uint32_t bits, const cw_dev_t &w, uint32_t pil, uint32_t prec)
+{
+  const s16x2 a = alm_ta(bits, w, pil);
+  const short p = w.alm_qpsk[pil][0], n = w.alm_qpsk[pil][1];
+  auto neg = [&](short v) { return w.Qm == 2 ? (v == p ? n : p) : (short)-v; };
+  switch (prec & 3u) {
+  case 1: return (s16x2){neg(a.x), neg(a.y)};
+  case 2: return (s16x2){neg(a.y), a.x};
+  case 3: return (s16x2){a.y, neg(a.x)};
+  default: return a;
+  }
+}
+
 /* 4-port large-delay CDD, rank 2 (configuration C4, a build-defined extension: 36.211 6.3.4.2.2,
  * y = W(i) D(i) U x(i), W(i) = C_k/sqrt2 over the codebook entries 12..15, k = floor(i/2) mod 4,
  * D(i) = diag(1, (-1)^i)).  Every entry of 4 W D U is +-1, so each antenna carries +-x0/2 or
@@ -846,7 +892,8 @@ static constexpr bool modofdm_zband(int MODE, bool CRS) { return CRS || MODE != 
 #define MODOFDM_WAVES_OF(L) (OAI4G_MODOFDM_WAVES > 0 ? OAI4G_MODOFDM_WAVES : ((L) == 11 ? 4 : 3))
 #define MODOFDM_ATTR __attribute__((amdgpu_waves_per_eu(MODOFDM_WAVES_OF(LOG2N))))
 /* MODE: 0 = TM1 (one transform stored to every antenna), 1 = ALAMOUTI, 2 = LARGE_CDD, 3 = 4-port
- * LARGE_CDD (C4: two items per symbol, each transforming one antenna pair) */
+ * LARGE_CDD (C4: two items per symbol, each transforming one antenna pair), 4 = single-layer precoding
+ * (modes 3..8: antenna 1 = antenna 0 times the RE's precoder) */
 /* CRS: the grid has static REs (CRS, or the control / common signals of set_control / set_common) */
 /* NS: the fused ibfly4 + shr1 levels (ibfly4_shr1_ns); the host sets it only for configurations whose
  * range check passed (mod_nosat_ok) */
@@ -860,14 +907,24 @@ __global__ void __launch_bounds__(128) MODOFDM_ATTR k_modofdm(const cfg_dev_t *_
   constexpr int NA = MODE == 0 ? 1 : 2;
   constexpr bool CW2 = MODE == 2 || MODE == 3;
   constexpr uint32_t IPS = MODE == 3 ? 2u : 1u;   /* items per (subframe, symbol) */
-  __shared__ __attribute__((aligned(16))) uint32_t lds_data[UNITS * NA * LDSW];
+  /* MODE 4 at 2048 points: the words of the last transform's region that no pass of idft2048_unit
+   * addresses (idft2048_tw_t::used_words, derived from the E1 / E2 index expressions: 16 words) are not
+   * allocated, and without them the 8-row QAM table keeps the workgroup inside 20 KB of LDS (8
+   * workgroups per CU) */
+  constexpr int XTRIM = (MODE == 4 && LOG2N == 11) ? LDSW - (int)idft2048_tw_t::used_words() : 0;
+  static_assert(XTRIM >= 0 && (XTRIM == 0 || UNITS * NA * LDSW * 4 - XTRIM * 4 + 8 * 256 + 4 <= 20480),
+                "MODE 4 at 2048 points must stay inside 20 KB of LDS");
+  __shared__ __attribute__((aligned(16))) uint32_t lds_data[UNITS * NA * LDSW - XTRIM];
   /* a static symbol's words (cfg stat_tm) are read before the staging barrier, not in the prologue.
    * Not in the two-antenna 2048-point kernels: 32 more live VGPRs there spill (20-100 bytes per lane) */
   constexpr bool SEARLY = CRS && (NA == 1 || LOG2N < 11);
   /* per codeword, the qtab byte address of every data RE's QAM word: entries 4q..4q+3 staged from
    * quad q's 4 Qm bits; entries SENT, SENT + 1 address the zero word that non-data REs read */
   constexpr int SW = G::SW, SENT = G::SENT, QPT = G::QPT, QROW = G::QROW;
-  constexpr uint32_t QZERO = 4u * 4u * QROW;     /* byte address of the zero word behind the 4 rows */
+  /* MODE 4: rows 0/1 = antenna 0, rows 2 prec + pilot = antenna 1 under precoder prec = 1..3 (under
+   * precoder 0 it reads antenna 0's rows): an RE's antenna-1 word is 2 prec rows behind its antenna-0 word */
+  constexpr uint32_t QROWS = MODE == 4 ? 8u : 4u;
+  constexpr uint32_t QZERO = 4u * QROWS * QROW;     /* byte address of the zero word behind the rows */
   /* 2048-point symbols: the staged entries share LDS with the IDFT exchange (two more barriers per
    * item), 19.0 KB per workgroup instead of 25.0 KB; smaller transforms keep them in lds_s_own */
   constexpr bool ALIAS = LOG2N == 11;
@@ -876,10 +933,11 @@ __global__ void __launch_bounds__(128) MODOFDM_ATTR k_modofdm(const cfg_dev_t *_
   uint16_t(*lds_s)[2][SW] = ALIAS ? (uint16_t(*)[2][SW])lds_data : lds_s_own;
   /* row cw * 2 + pilot symbol: 64 packed IQ words, 256 bytes, so a row base ORs into an entry's byte
    * offset (bits 8-9 against 2-7); then the zero word */
-  __shared__ uint32_t qtab[4 * QROW + 1];
+  __shared__ uint32_t qtab[QROWS * QROW + 1];
   /* bytes per staged entry as a shift, and the bits of an RE code that address one: the layout
    * upload_remap wrote the codes for (oai4g_internal.h) */
-  constexpr uint32_t ESH = oai4g_mod_entry_shift(MODE == 0 ? OAI4G_SISO : MODE == 1 ? OAI4G_ALAMOUTI : OAI4G_LARGE_CDD,
+  constexpr uint32_t ESH = oai4g_mod_entry_shift(MODE == 0 ? OAI4G_SISO : MODE == 1 ? OAI4G_ALAMOUTI :
+                                                 MODE == 4 ? OAI4G_UNIFORM_PRECODING11 : OAI4G_LARGE_CDD,
                                                  MODE == 3 ? 4 : 2, LOG2N);
   constexpr uint32_t EMASK = oai4g_mod_addr_mask(ESH);
   /* PRE (C3's kernel): the staging step looks the QAM words of both codewords up and stores
@@ -900,13 +958,15 @@ __global__ void __launch_bounds__(128) MODOFDM_ATTR k_modofdm(const cfg_dev_t *_
   /* symbols per slot as a constant (the launch checks cfg nsymb) */
   const uint32_t n_ant = c->n_ant;
   constexpr uint32_t sps = ECP ? 6 : 7;
-  for (uint32_t i = threadIdx.x; i < 4 * QROW + 1; i += blockDim.x) {
+  for (uint32_t i = threadIdx.x; i < QROWS * QROW + 1; i += blockDim.x) {
     const uint32_t row = i / QROW, bits = i - row * QROW, cw = row >> 1, pil = row & 1;
     uint32_t v = 0;
-    if (row < 4) {
+    if (row < QROWS) {
       if constexpr (MODE == 1) {        /* one codeword: rows 0/1 = TA, rows 2/3 = TB */
         const cw_dev_t &w = c->cw[0];
         v = c2u(cw ? alm_tb(bits, w, pil) : alm_ta(bits, w, pil));
+      } else if constexpr (MODE == 4) { /* one codeword: row pair = precoder */
+        v = c2u(prec1_tb(bits, c->cw[0], pil, row >> 1));
       } else {
         const cw_dev_t &w = c->cw[cw];
         v = c2u(qam_map(bits, w.Qm, pil ? w.qam_b : w.qam_a, pil ? w.qpsk_b : w.qpsk_a));
@@ -1132,7 +1192,7 @@ __global__ void __launch_bounds__(128) MODOFDM_ATTR k_modofdm(const cfg_dev_t *_
           constexpr int GR = OAI4G_MOD_GROUP;
           /* a data RE's code is the byte offset of its staged entry, idx << ESH (2-byte entries: | parity
            * << 15; ALAMOUTI: idx = 2i + role, and the pair's TA / TB entries are read from 4i) */
-          constexpr uint32_t AM = MODE == 1 ? EMASK & ~2u : EMASK;
+          constexpr uint32_t AM = MODE == 1 ? EMASK & ~2u : MODE == 4 ? EMASK & ~(oai4g_mod_pmi_bits | 0x4000u) : EMASK;
           constexpr bool ZB = modofdm_zband(MODE, CRS);
           auto zb = [&](int n) { return ZB && n >= G::ZLO && n <= G::ZHI; };   /* constant after unrolling */
           /* the NZ leaf inputs outside the guard band, visited in groups of GZ (the i-th is act(i)) */
@@ -1202,6 +1262,10 @@ __global__ void __launch_bounds__(128) MODOFDM_ATTR k_modofdm(const cfg_dev_t *_
 #endif
 #pragma unroll
             for (int n = 0; n < GZ; n++) {
+              /* MODE 4: precoder bits 12-13 of the code -> 2 prec rows of 256 bytes (a non-data RE's
+               * code has precoder 0: both antennas read the zero word) */
+              if constexpr (MODE == 4)
+                v1[n] = *(const uint32_t *)(qb + QADDR(v0[n] + ((code[n] & oai4g_mod_pmi_bits) >> (OAI4G_MOD_PMI_SHIFT - 9u))));
               v0[n] = *(const uint32_t *)(qb + QADDR(v0[n]));
               if constexpr (MODE == 1 || CW2) v1[n] = *(const uint32_t *)(qb + QADDR(v1[n]));
             }
@@ -1218,6 +1282,9 @@ __global__ void __launch_bounds__(128) MODOFDM_ATTR k_modofdm(const cfg_dev_t *_
 #pragma unroll
                 for (int a = 0; a < 2; a++)
                   x[a][i] = half_signed(((CDD4_QSEL >> (sel + a)) & 1u) ? x1 : x0, (CDD4_NEG >> (sel + a)) & 1u);
+              } else if constexpr (MODE == 4) {
+                x[0][i] = x0;
+                x[1][i] = u2c(v1[n]);
               } else if constexpr (NA == 2) {
                 /* parity bit 15 of the code -> lane mask 0 / ~0 */
                 cdd_pair_m(x0, u2c(v1[n]), (uint32_t)((int32_t)(code[n] << 16) >> 31), x[0][i], x[1][i]);
@@ -1352,6 +1419,9 @@ static hipError_t launch_modofdm_m(const cfg_dev_t *d_cfg, const cfg_dev_t *h_cf
     return h_cfg->n_ant == 4 ? launch_modofdm_c<LOG2N, 3, ECP>(d_cfg, h_cfg, sf0, 2 * n_items, d_ebits, d_iq, s)
                              : launch_modofdm_c<LOG2N, 2, ECP>(d_cfg, h_cfg, sf0, n_items, d_ebits, d_iq, s);
   case OAI4G_ALAMOUTI: return launch_modofdm_c<LOG2N, 1, ECP>(d_cfg, h_cfg, sf0, n_items, d_ebits, d_iq, s);
+  case OAI4G_UNIFORM_PRECODING11: case OAI4G_UNIFORM_PRECODING1m1: case OAI4G_UNIFORM_PRECODING1j:
+  case OAI4G_UNIFORM_PRECODING1mj: case OAI4G_PUSCH_PRECODING0: case OAI4G_PUSCH_PRECODING1:
+    return launch_modofdm_c<LOG2N, 4, ECP>(d_cfg, h_cfg, sf0, n_items, d_ebits, d_iq, s);
   default: return launch_modofdm_c<LOG2N, 0, ECP>(d_cfg, h_cfg, sf0, n_items, d_ebits, d_iq, s);
   }
 }
@@ -1386,6 +1456,8 @@ hipError_t oai4g_launch_modofdm(const cfg_dev_t *d_cfg, const cfg_dev_t *h_cfg, 
   if (h_cfg->mimo_mode != OAI4G_SISO && h_cfg->n_ant != 2 && !(h_cfg->mimo_mode == OAI4G_LARGE_CDD && h_cfg->n_ant == 4))
     return hipErrorInvalidValue;
   if (h_cfg->mimo_mode == OAI4G_LARGE_CDD && h_cfg->n_cw != 2) return hipErrorInvalidValue;
+  if (oai4g_mode_prec1(h_cfg->mimo_mode) && h_cfg->n_cw != 1) return hipErrorInvalidValue;
+  if (h_cfg->mimo_mode > OAI4G_PUSCH_PRECODING1) return hipErrorInvalidValue;
   if (h_cfg->log2N >= 7 && h_cfg->log2N <= 11) {
     /* the guard-band leaf inputs must be zero subcarriers: T ZLO > 6 N_RB_DL, T (ZHI + 1) <= first_carrier */
     const uint32_t T = h_cfg->N >> 4, zlo = h_cfg->log2N == 8 ? 6u : 5u, zhi = h_cfg->log2N == 8 ? 9u : 10u;
@@ -1440,6 +1512,20 @@ __global__ void __launch_bounds__(256) k_modulate_bytes(const cfg_dev_t *__restr
     alm_pair(n0, n1, 1u, y0, y1);
     g0[k2] = c2u(caddw(u2c(g0[k2]), y0));
     g1[k2] = c2u(caddw(u2c(g1[k2]), y1));
+    return;
+  }
+  if (oai4g_mode_prec1(c->mimo_mode)) {
+    /* one layer on antenna 0, and on antenna 1 under the RE's precoder (:750-866); with one TX antenna
+     * the reference writes antenna 0 alone, at the same scaling */
+    const uint32_t base = ((code & oai4g_mod_pmi_idx_mask) + c->symbase[sfi][l]) * cw0.Qm;
+    uint32_t b = 0;
+    for (uint32_t i = 0; i < cw0.Qm; i++) b |= (uint32_t)(e0[base + i] == 1) << i;
+    uint32_t *g0 = (uint32_t *)grid + l * N + k;
+    *g0 = c2u(caddw(u2c(*g0), alm_ta(b, cw0, pil)));
+    if (c->n_ant == 2) {
+      uint32_t *g1 = g0 + (size_t)nsymb * N;
+      *g1 = c2u(caddw(u2c(*g1), prec1_tb(b, cw0, pil, code >> OAI4G_MOD_PMI_SHIFT)));
+    }
     return;
   }
   uint32_t idx = (code & 0x7FFFu) + c->symbase[sfi][l];

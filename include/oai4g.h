@@ -375,6 +375,38 @@ oai4g_rx_config_t *oai4g_rx_config_create_tm2(const oai4g_frame_parms_t *frame_p
 int oai4g_rx_batch_tm2(oai4g_rx_config_t *cfg, int n_sf, const int32_t *d_rxdataF, const int32_t *d_est, int16_t *d_llr,
                        int unscramble, void *stream);
 
+/* TM4-6 single-layer precoding (mimo_mode OAI4G_UNIFORM_PRECODING11 .. OAI4G_PUSCH_PRECODING0: one
+ * codeword on two ports) with dlsim's UE (rx_pdsch with dual_stream_flag = 0, dlsch_demodulation.c:518-533):
+ * dlsch_extract_rbs_dual with pmi_ext, dlsch_channel_level over both ports (log2_maxh = log2_approx(max
+ * avg) / 2, + 1 when dl_power_off == 1), dlsch_channel_compensation_TM56 (prec2A_TM56_128: h0 + w h1,
+ * w = 1, -1, j, -j by the PRB's precoder), dlsch_detection_mrc over nb_rx (1-2), dlsch_qpsk / 16qam /
+ * 64qam_llr.  Buffers as for oai4g_rx_pdsch_tm2.  OAI4G_PUSCH_PRECODING1 is refused as rx_pdsch refuses
+ * it (:595-597); the precoder never comes from the mode's name.  precoded_cqi_dB is not computed and the
+ * estimates are not overwritten.
+ *
+ * The subband of a PRB (pmi_rule):
+ *   OAI4G_RX_PMI_UE  the reference UE's: (pmi_alloc >> ((prb >> 2) << 1)) & 3, 4-RB subbands at every
+ *                    bandwidth (:3812).  It equals the transmitter's get_pmi only at 15 / 25 PRB or for a
+ *                    pmi_alloc whose subbands are all equal.  pmi_alloc is an unsigned short promoted to
+ *                    int there: counts of 16..31 (PRB 32..63) read 0; a count >= 32 (an allocated PRB
+ *                    >= 64) is undefined in C and refused unless pmi_alloc == 0.  The drop-in uses it.
+ *   OAI4G_RX_PMI_TX  oai4g_get_pmi's subbands (1 / 4 / 6 / 8 RBs): decodes this library's transmitter at
+ *                    every bandwidth. */
+enum { OAI4G_RX_PMI_UE = 0, OAI4G_RX_PMI_TX = 1 };
+int oai4g_rx_pdsch_tm56(const oai4g_frame_parms_t *frame_parms, int nb_rx, const int32_t *const *rxdataF,
+                        const int32_t *const *dl_ch_estimates, const uint32_t rb_alloc[4], uint8_t Qm,
+                        uint8_t mimo_mode, uint16_t pmi_alloc, uint8_t dl_power_off, uint8_t num_pdcch_symbols,
+                        uint8_t subframe, int16_t *llr, uint8_t *log2_maxh);
+oai4g_rx_config_t *oai4g_rx_config_create_tm56(const oai4g_frame_parms_t *frame_parms, const uint32_t rb_alloc[4],
+                                               uint8_t Qm, uint8_t mimo_mode, uint16_t pmi_alloc, int pmi_rule,
+                                               uint8_t dl_power_off, uint8_t num_pdcch_symbols, uint16_t rnti,
+                                               uint8_t first_subframe, uint8_t subframe_step, uint8_t nb_rx);
+int oai4g_rx_batch_tm56(oai4g_rx_config_t *cfg, int n_sf, const int32_t *d_rxdataF, const int32_t *d_est, int16_t *d_llr,
+                        int unscramble, void *stream);
+/* from the pilot rows of oai4g_chest_batch_pilots (d_pil as for oai4g_rx_batch_tm3_pilots); bit-identical */
+int oai4g_rx_batch_tm56_pilots(oai4g_rx_config_t *cfg, int n_sf, const int32_t *d_rxdataF, const int32_t *d_pil,
+                               int16_t *d_llr, int unscramble, void *stream);
+
 /* lte_dl_channel_estimation (PHY/LTE_ESTIMATION/lte_dl_channel_estimation.c:37, decl
  * LTE_ESTIMATION/defs.h; called by slot_fep.c:188 for the pilot symbols of every slot) with the
  * reference's defaults high_speed_flag = 1 (dlsim.c:2057), eNB_offset 0, one RX antenna: the

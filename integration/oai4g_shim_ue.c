@@ -1,6 +1,6 @@
 /* oai4g_shim_ue.c — reference-side bindings that take PHY_VARS_UE / PHY_VARS_eNB.
  * Replaces: slot_fep.c:40 slot_fep, pilots.c:43 generate_pilots, lte_dl_channel_estimation.c:37,
- * dlsch_demodulation.c:82 rx_pdsch (TM1/TM2/TM3).
+ * dlsch_demodulation.c:82 rx_pdsch (TM1/TM2/TM3, TM4-6 single-layer precoding).
  * PHY_VARS_UE / PHY_VARS_eNB are defined in PHY/defs.h, whose include chain needs the asn1c-generated
  * RRC headers (PHY/INIT/defs.h:35-42), so this file compiles only inside a full reference build
  * (cmake_targets), next to oai4g_shim.c. */
@@ -66,8 +66,10 @@ int lte_dl_channel_estimation(PHY_VARS_UE *ue, uint8_t eNB_id, uint8_t eNB_offse
                                     (int32_t *const *)ue->lte_ue_common_vars.dl_ch_estimates_time[0]);
 }
 
-/* rx_pdsch (dlsch_demodulation.c:82) for TM1 (one TX port, one RX antenna), TM2 (ALAMOUTI) and TM3
- * (LARGE_CDD; both two TX ports, 1-2 RX antennas, dual_stream_flag 0), localized allocations (rb_alloc_even ==
+/* rx_pdsch (dlsch_demodulation.c:82) for TM1 (one TX port, one RX antenna), TM2 (ALAMOUTI), TM3
+ * (LARGE_CDD) and TM4-6 (UNIFORM_PRECODING11 .. PUSCH_PRECODING0, the precoder per PRB from
+ * pmi_alloc by the UE's 4-RB subband rule; PUSCH_PRECODING1 is refused as the reference refuses it) —
+ * all three with two TX ports, 1-2 RX antennas, dual_stream_flag 0 — localized allocations (rb_alloc_even ==
  * rb_alloc_odd).  CONTRACT: the library demodulates a whole subframe, so the shim accepts dlsim's
  * call sequence only (dlsim.c:3236-3260): first_symbol_flag on symbol num_pdcch_symbols, then
  * every following symbol in order; the work runs at the last symbol, when the LLR stream and
@@ -86,9 +88,11 @@ int rx_pdsch(PHY_VARS_UE *ue, PDSCH_t type, unsigned char eNB_id, unsigned char 
   LTE_DL_UE_HARQ_t *h = ue->dlsch_ue[eNB_id][0]->harq_processes[harq_pid];
   const int tm3 = f->nb_antennas_tx_eNB == 2 && h->mimo_mode == LARGE_CDD;
   const int tm2 = f->nb_antennas_tx_eNB == 2 && h->mimo_mode == ALAMOUTI;
+  const int tm56 = f->nb_antennas_tx_eNB == 2 && h->mimo_mode >= UNIFORM_PRECODING11 &&
+                   h->mimo_mode < DUALSTREAM_UNIFORM_PRECODING1;
   if (type != PDSCH || dual_stream_flag || memcmp(h->rb_alloc_even, h->rb_alloc_odd, 16) != 0 ||
-      (!tm3 && !tm2 && (f->nb_antennas_rx != 1 || f->nb_antennas_tx_eNB != 1)) ||
-      ((tm3 || tm2) && f->nb_antennas_rx > 2))
+      (!tm3 && !tm2 && !tm56 && (f->nb_antennas_rx != 1 || f->nb_antennas_tx_eNB != 1)) ||
+      ((tm3 || tm2 || tm56) && f->nb_antennas_rx > 2))
     return -1;
   const int npdcch = ue->lte_ue_pdcch_vars[eNB_id]->num_pdcch_symbols;
   if (first_symbol_flag) {
@@ -104,7 +108,7 @@ int rx_pdsch(PHY_VARS_UE *ue, PDSCH_t type, unsigned char eNB_id, unsigned char 
   fp_to(f, &fp);
   uint8_t log2_maxh = 0;
   int n;
-  if (tm3 || tm2) {
+  if (tm3 || tm2 || tm56) {
     const int32_t *rxF[2], *est[4];
     for (int a = 0; a < f->nb_antennas_rx; a++) {
       rxF[a] = (const int32_t *)ue->lte_ue_common_vars.rxdataF[a];
@@ -114,6 +118,10 @@ int rx_pdsch(PHY_VARS_UE *ue, PDSCH_t type, unsigned char eNB_id, unsigned char 
     if (tm2) {
       n = oai4g_rx_pdsch_tm2(&fp, f->nb_antennas_rx, rxF, est, h->rb_alloc_even, h->Qm, npdcch, subframe,
                              ue->lte_ue_pdsch_vars[eNB_id]->llr[0], &log2_maxh);
+    } else if (tm56) {
+      n = oai4g_rx_pdsch_tm56(&fp, f->nb_antennas_rx, rxF, est, h->rb_alloc_even, h->Qm, (uint8_t)h->mimo_mode,
+                              h->pmi_alloc, h->dl_power_off, npdcch, subframe,
+                              ue->lte_ue_pdsch_vars[eNB_id]->llr[0], &log2_maxh);
     } else {
       LTE_DL_UE_HARQ_t *h1 = ue->dlsch_ue[eNB_id][1]->harq_processes[harq_pid];
       if (h->Qm == 2 && h1->Qm == 2)   /* both QPSK: dlsch_qpsk_qpsk_llr fills llr[0] and llr[1] */

@@ -245,6 +245,18 @@ _SIGS = {
                                                      ctypes.c_uint8]),
     "oai4g_rx_batch_tm2": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "oai4g_rx_pdsch_tm56": (ctypes.c_int, [ctypes.POINTER(FrameParms), ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint16,
+                                           ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_void_p,
+                                           ctypes.c_void_p]),
+    "oai4g_rx_config_create_tm56": (ctypes.c_void_p, [ctypes.POINTER(FrameParms), ctypes.c_void_p, ctypes.c_uint8,
+                                                      ctypes.c_uint8, ctypes.c_uint16, ctypes.c_int, ctypes.c_uint8,
+                                                      ctypes.c_uint8, ctypes.c_uint16, ctypes.c_uint8, ctypes.c_uint8,
+                                                      ctypes.c_uint8]),
+    "oai4g_rx_batch_tm56": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "oai4g_rx_batch_tm56_pilots": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "oai4g_dl_ch_estimates_time": (ctypes.c_int, [ctypes.POINTER(FrameParms), ctypes.c_int, ctypes.c_void_p,
                                                   ctypes.c_void_p]),
     "oai4g_chest_time_batch": (ctypes.c_int, [ctypes.POINTER(FrameParms), ctypes.c_int, ctypes.c_void_p,
@@ -628,6 +640,31 @@ def rx_pdsch_tm2(fp, rxF, est, rb_alloc, Qm, num_pdcch, subframe):
     return out[:n], sh.value
 
 
+# the subband of a PRB in the TM4-6 receiver: the reference UE's 4-RB rule / the transmitter's get_pmi
+RX_PMI_UE, RX_PMI_TX = 0, 1
+
+
+def rx_pdsch_tm56(fp, rxF, est, rb_alloc, Qm, mimo_mode, pmi_alloc, dl_power_off, num_pdcch, subframe):
+    """rx_pdsch for the single-layer precoding modes 3..7 (TM4-6, dual_stream_flag = 0, the reference UE's
+    subband rule): rxF = [nb_rx][nsymb*N], est[(p, a)] = [nsymb*N].  Returns (LLRs, log2_maxh)."""
+    init()
+    nb_rx = len(rxF)
+    rx = [np.ascontiguousarray(r, dtype=np.int32) for r in rxF]
+    keep = {k: np.ascontiguousarray(v, dtype=np.int32) for k, v in est.items()}
+    ep = (ctypes.c_void_p * 4)()
+    for (p_, a), arr in keep.items():
+        if a < nb_rx:
+            ep[2 * p_ + a] = arr.ctypes.data
+    rp = (ctypes.c_void_p * 2)(*[r.ctypes.data for r in rx] + [None] * (2 - nb_rx))
+    out = np.zeros(14 * 1200 * 6 + 64, dtype=np.int16)
+    sh = ctypes.c_uint8()
+    ra = (ctypes.c_uint32 * 4)(*rb_alloc)
+    n = lib().oai4g_rx_pdsch_tm56(ctypes.byref(fp), nb_rx, rp, ep, ra, Qm, mimo_mode, pmi_alloc, dl_power_off,
+                                  num_pdcch, subframe, _ptr(out), ctypes.byref(sh))
+    _check(n >= 0)
+    return out[:n], sh.value
+
+
 class RxBatchTM3:
     """Device-resident batched TM3 demodulation (oai4g_rx_batch_tm3): codeword 0's LLRs from the FEP
     output of nb_rx antennas and the four estimate planes (ports 0 / 1 per antenna)."""
@@ -769,6 +806,31 @@ class RxBatchTM2(RxBatchTM3):
 
     def launch(self, d_rxF, unscramble=1, stream=None):
         _check(self.L.oai4g_rx_batch_tm2(self.cfg, self.n_sf, d_rxF, self.d_est, self.d_llr, unscramble, stream) == 0)
+
+
+class RxBatchTM56(RxBatchTM3):
+    """Device-resident batched TM4-6 demodulation (oai4g_rx_batch_tm56): the single-layer precoded
+    codeword's LLRs from the FEP output of nb_rx antennas and the four estimate planes (launch), or from
+    the pilot rows (estimate_pilots / launch_pilots)."""
+
+    def __init__(self, fp, rb_alloc, Qm, mimo_mode, pmi_alloc, num_pdcch, rnti, n_sf, nb_rx=2, first_subframe=0,
+                 subframe_step=1, pmi_rule=RX_PMI_UE, dl_power_off=1):
+        init()
+        self.L = lib()
+        ra = (ctypes.c_uint32 * 4)(*rb_alloc)
+        self.cfg = self.L.oai4g_rx_config_create_tm56(ctypes.byref(fp), ra, Qm, mimo_mode, pmi_alloc, pmi_rule,
+                                                      dl_power_off, num_pdcch, rnti, first_subframe, subframe_step,
+                                                      nb_rx)
+        _check(bool(self.cfg))
+        self._setup(fp, n_sf, nb_rx)
+
+    def launch(self, d_rxF, unscramble=1, stream=None):
+        _check(self.L.oai4g_rx_batch_tm56(self.cfg, self.n_sf, d_rxF, self.d_est, self.d_llr, unscramble, stream) == 0)
+
+    def launch_pilots(self, d_rxF, unscramble=1, stream=None):
+        """oai4g_rx_batch_tm56_pilots: the demodulation from the pilot rows (estimate_pilots)"""
+        _check(self.L.oai4g_rx_batch_tm56_pilots(self.cfg, self.n_sf, d_rxF, self._pil(), self.d_llr, unscramble,
+                                                 stream) == 0)
 
 
 def dlsch_unscrambling(fp, rnti, G, llr, q, Ns, mbsfn_flag=0):

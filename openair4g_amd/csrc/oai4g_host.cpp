@@ -3689,9 +3689,11 @@ static void rx_extract_map(const oai4g_frame_parms_t *fp, const uint32_t rb_allo
  * out), so the port-0 estimate pointer moves 144 slots per RB while rxF_ext / dl_ch1_ext move 12.
  * The port-0 writes are tracked with that drift; n = the prefix of slots where the received RE and
  * both estimates come from the same column (past it the reference reads stale or unwritten port-0
- * slots, and its writes run past dl_ch_estimates_ext: a stream reaching there is refused). */
+ * slots, and its writes run past dl_ch_estimates_ext: a stream reaching there is refused).
+ * prbs, when given, receives the PRBs in the order the extraction fills pmi_ext for them. */
 static void rx_extract_map_dual(const oai4g_frame_parms_t *fp, const uint32_t rb_alloc[4], uint32_t subframe, uint32_t l,
-                                std::vector<uint32_t> &map, uint32_t &nb_rb, uint32_t &n)
+                                std::vector<uint32_t> &map, uint32_t &nb_rb, uint32_t &n,
+                                std::vector<uint16_t> *prbs = nullptr)
 {
   const uint32_t smod = l >= 7u - fp->Ncp ? l - (7u - fp->Ncp) : l;
   const bool pil = smod == 0 || smod == 4u - fp->Ncp;
@@ -3719,6 +3721,7 @@ static void rx_extract_map_dual(const oai4g_frame_parms_t *fp, const uint32_t rb
     if (fp->frame_type == 0 && (subframe == 0 || subframe == 5) && prb > half - 3 && prb < half + 3 && li == pss_symb) ind = 0;
     if (fp->frame_type == 1 && subframe == 6 && prb >= half - 3 && prb <= half + 3 && li == pss_symb) ind = 0;
     if (!ind) continue;
+    if (prbs) prbs->push_back((uint16_t)prb);                  /* the PRBs pmi_ext gets an entry for, in order */
     const uint32_t col0 = 12 * prb;
     if ((fp->N_RB_DL & 1) == 0) {
       const uint32_t b0 = prb < half ? fp->first_carrier_offset + 12 * prb : 1 + 12 * (prb - half);
@@ -3791,13 +3794,53 @@ static const uint8_t k_mumimo_off[29][3] = {{0, 6, 5}, {0, 4, 5}, {0, 4, 5}, {0,
                                             {1, 0, 0}, {0, 0, 0}, {0, 1, 0}, {1, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0},
                                             {0, 0, 0}};
 
+/* TM4-6: the precoder word, the subband rule and dl_power_off of oai4g_rx_config_create_tm56 */
+struct rx_tm56_t {
+  uint8_t mimo_mode;
+  uint16_t pmi_alloc;
+  int pmi_rule;
+  uint8_t dl_power_off;
+};
+
+/* pmi_ext of one allocated PRB.  OAI4G_RX_PMI_UE: dlsch_extract_rbs_dual's (pmi >> ((prb >> 2) << 1)) & 3
+ * (:3812, :3907) — 4-RB subbands at every bandwidth; pmi is an unsigned short promoted to int, so a count
+ * of 16..31 reads 0 (counts >= 32 are refused by the caller).  OAI4G_RX_PMI_TX: the transmitter's get_pmi. */
+static uint32_t rx_pmi_of(const oai4g_frame_parms_t *fp, const rx_tm56_t &t, uint32_t prb)
+{
+  if (t.pmi_rule == OAI4G_RX_PMI_TX) return oai4g_get_pmi(fp->N_RB_DL, t.mimo_mode, t.pmi_alloc, (uint16_t)prb);
+  const uint32_t cnt = (prb >> 2) << 1;
+  return cnt >= 32 ? 0u : ((uint32_t)t.pmi_alloc >> cnt) & 3u;
+}
+
 static oai4g_rx_config_t *rx_config_build(const oai4g_frame_parms_t *fp, const uint32_t rb_alloc[4], uint8_t Qm,
                                           uint8_t num_pdcch_symbols, uint16_t rnti, uint8_t first_subframe,
                                           uint8_t subframe_step, int tm3, uint8_t Qm1, uint8_t mcs0, uint8_t nb_rx,
-                                          int tm2 = 0)
+                                          int tm2 = 0, const rx_tm56_t *tm56 = nullptr)
 {
   NEED_INIT(nullptr);
-  const bool dual = tm3 || tm2;
+  const bool dual = tm3 || tm2 || tm56;
+  if (tm56) {
+    if (fp->nb_antennas_tx != 2 || fp->mode1_flag != 0 || (Qm != 2 && Qm != 4 && Qm != 6) || nb_rx < 1 || nb_rx > 2 ||
+        num_pdcch_symbols < 1 || num_pdcch_symbols > 3 ||
+        (tm56->pmi_rule != OAI4G_RX_PMI_UE && tm56->pmi_rule != OAI4G_RX_PMI_TX)) {
+      set_err("rx_config_tm56: two TX ports (mode1_flag 0), Qm 2/4/6, 1-2 RX antennas, 1..3 PDCCH symbols, "
+              "pmi_rule OAI4G_RX_PMI_UE / _TX");
+      return nullptr;
+    }
+    if (tm56->mimo_mode < OAI4G_UNIFORM_PRECODING11 || tm56->mimo_mode > OAI4G_PUSCH_PRECODING0) {
+      set_err("rx_config_tm56: mimo_mode %u: rx_pdsch demodulates the single-layer modes 3..7 (mode 8 ends in "
+              "\"Unknown MIMO mode\", dlsch_demodulation.c:595-597)", tm56->mimo_mode);
+      return nullptr;
+    }
+    if (tm56->pmi_rule == OAI4G_RX_PMI_UE && tm56->pmi_alloc != 0)
+      for (int prb = 64; prb < fp->N_RB_DL; prb++)
+        if (rx_alloc_bit(rb_alloc, prb)) {
+          set_err("rx_config_tm56: PRB %d is allocated: the reference UE shifts its 16-bit pmi_alloc by %d there "
+                  "(dlsch_demodulation.c:3812), which is undefined; only pmi_alloc 0 reads the same either way",
+                  prb, (prb >> 2) << 1);
+          return nullptr;
+        }
+  }
   if (tm2 && (fp->nb_antennas_tx != 2 || fp->mode1_flag != 0 || (Qm != 2 && Qm != 4 && Qm != 6) || nb_rx < 1 ||
               nb_rx > 2 || num_pdcch_symbols < 1 || num_pdcch_symbols > 3)) {
     set_err("rx_config_tm2: two TX ports (mode1_flag 0), Qm 2/4/6, 1-2 RX antennas, 1..3 PDCCH symbols");
@@ -3838,6 +3881,8 @@ static oai4g_rx_config_t *rx_config_build(const oai4g_frame_parms_t *fp, const u
   h.nb_rx = dual ? nb_rx : 1u;
   h.mu_off = tm3 ? k_mumimo_off[mcs0][(Qm1 >> 1) - 1] : 0;
   h.qm1 = tm3 ? Qm1 : 0u;
+  h.tm56 = tm56 ? 1u : 0u;
+  h.lvl_inc = tm56 && tm56->dl_power_off == 1 ? 1u : 0u;
   /* estimate rows from the 5 pilot rows (P0 .. P3 = symbols 0, p1, p2, p3; P4 = the next subframe's
    * symbol 0): lte_dl_channel_estimation.c:639-698 as k_chest's ce_interp applies it */
   {
@@ -3866,7 +3911,18 @@ static oai4g_rx_config_t *rx_config_build(const oai4g_frame_parms_t *fp, const u
       const bool pil = smod == 0 || smod == 4u - fp->Ncp;
       h.map_off[sf][k] = (uint32_t)map.size();
       uint32_t nb_rb = 0, n = 0;
-      if (dual)
+      if (tm56) {
+        /* this configuration's own copy of the dual map: slot j belongs to pmi_ext[j / 12] (j / 8 in
+         * pilot symbols, dlsch_channel_compensation_TM56 :1518-1528, :1641-1654), whose precoder goes
+         * into bits 30-31 (bin and 5 + column stay below 2^11) */
+        std::vector<uint16_t> prbs;
+        rx_extract_map_dual(fp, rb_alloc, sf, l, map, nb_rb, n, &prbs);
+        const uint32_t nre = pil ? 8 : 12;
+        for (size_t j = h.map_off[sf][k]; j < map.size(); j++) {
+          const size_t rb = (j - h.map_off[sf][k]) / nre;
+          if (rb < prbs.size()) map[j] |= rx_pmi_of(fp, *tm56, prbs[rb]) << 30;
+        }
+      } else if (dual)
         rx_extract_map_dual(fp, rb_alloc, sf, l, map, nb_rb, n);
       else
         rx_extract_map(fp, rb_alloc, sf, l, map, nb_rb, n);
@@ -3957,6 +4013,16 @@ extern "C" oai4g_rx_config_t *oai4g_rx_config_create_tm2(const oai4g_frame_parms
                                                          uint8_t first_subframe, uint8_t subframe_step, uint8_t nb_rx)
 {
   return rx_config_build(fp, rb_alloc, Qm, num_pdcch_symbols, rnti, first_subframe, subframe_step, 0, 0, 0, nb_rx, 1);
+}
+
+extern "C" oai4g_rx_config_t *oai4g_rx_config_create_tm56(const oai4g_frame_parms_t *fp, const uint32_t rb_alloc[4],
+                                                          uint8_t Qm, uint8_t mimo_mode, uint16_t pmi_alloc,
+                                                          int pmi_rule, uint8_t dl_power_off,
+                                                          uint8_t num_pdcch_symbols, uint16_t rnti,
+                                                          uint8_t first_subframe, uint8_t subframe_step, uint8_t nb_rx)
+{
+  const rx_tm56_t t = {mimo_mode, pmi_alloc, pmi_rule, dl_power_off};
+  return rx_config_build(fp, rb_alloc, Qm, num_pdcch_symbols, rnti, first_subframe, subframe_step, 0, 0, 0, nb_rx, 0, &t);
 }
 
 extern "C" void oai4g_rx_config_destroy(oai4g_rx_config_t *cfg)
@@ -4111,6 +4177,36 @@ extern "C" int oai4g_rx_batch_tm2(oai4g_rx_config_t *cfg, int n_sf, const int32_
   return 0;
 }
 
+/* TM4-6 single-layer precoding from the estimate planes [p * 2 + a][n_sf][nsymb][N], or (pil) from the
+ * pilot-row pairs oai4g_chest_batch_pilots wrote, as oai4g_rx_batch_tm3_pilots takes them */
+static int rx_batch_tm56(oai4g_rx_config_t *cfg, int n_sf, const int32_t *d_rxdataF, const int32_t *d_est,
+                         int16_t *d_llr, int unscramble, void *stream, int pil)
+{
+  NEED_INIT(-1);
+  if (!cfg || !cfg->h.tm56) { set_err("rx_batch_tm56: not a TM4-6 configuration (oai4g_rx_config_create_tm56)"); return -1; }
+  if (n_sf <= 0) return 0;
+  if (rx_check_batch(cfg, n_sf) != 0) return -1;
+  if (n_sf > cfg->shift_cap) {
+    if (cfg->d_shift) hipFree(cfg->d_shift);
+    HCK(hipMalloc(&cfg->d_shift, (size_t)n_sf), -1);
+    cfg->shift_cap = n_sf;
+  }
+  const size_t plane = pil ? (size_t)n_sf * 4 * cfg->h.N * 2 : (size_t)n_sf * cfg->h.nsymb * cfg->h.N;
+  HCK(oai4g_launch_rx_tm56(cfg->d, &cfg->h, n_sf, d_rxdataF, d_est, plane, d_llr, cfg->d_shift, unscramble,
+                           (hipStream_t)stream, pil), -1);
+  return 0;
+}
+extern "C" int oai4g_rx_batch_tm56(oai4g_rx_config_t *cfg, int n_sf, const int32_t *d_rxdataF, const int32_t *d_est,
+                                   int16_t *d_llr, int unscramble, void *stream)
+{
+  return rx_batch_tm56(cfg, n_sf, d_rxdataF, d_est, d_llr, unscramble, stream, 0);
+}
+extern "C" int oai4g_rx_batch_tm56_pilots(oai4g_rx_config_t *cfg, int n_sf, const int32_t *d_rxdataF,
+                                          const int32_t *d_pil, int16_t *d_llr, int unscramble, void *stream)
+{
+  return rx_batch_tm56(cfg, n_sf, d_rxdataF, d_pil, d_llr, unscramble, stream, 1);
+}
+
 /* The rx_pdsch drop-ins' configurations, cached per calling thread (the UE calls rx_pdsch once per
  * subframe with a handful of distinct (frame, allocation, modulation, subframe) keys; building one
  * costs Gold generation, allocations and copies).  Round-robin over 32 entries; an evicted entry
@@ -4122,6 +4218,8 @@ struct rx_key_t {
   oai4g_frame_parms_t fp;
   uint32_t rb_alloc[4];
   uint8_t Qm, Qm1, mcs0, npdcch, subframe, tm3, nb_rx, pad;
+  uint16_t pmi_alloc;             /* tm3 == 3 (TM4-6): the precoder word, mode and dl_power_off */
+  uint8_t mimo_mode, dl_power_off;
 };
 struct rx_cache_t {
   rx_key_t key[32];
@@ -4131,7 +4229,8 @@ struct rx_cache_t {
 thread_local rx_cache_t t_rx_cache;
 
 oai4g_rx_config_t *rx_cached(const oai4g_frame_parms_t *fp, const uint32_t rb_alloc[4], uint8_t Qm, uint8_t Qm1,
-                             uint8_t mcs0, uint8_t npdcch, uint8_t subframe, int tm3, int nb_rx)
+                             uint8_t mcs0, uint8_t npdcch, uint8_t subframe, int tm3, int nb_rx, uint8_t mimo_mode = 0,
+                             uint16_t pmi_alloc = 0, uint8_t dl_power_off = 0)
 {
   rx_key_t k;
   memset(&k, 0, sizeof(k));
@@ -4139,10 +4238,13 @@ oai4g_rx_config_t *rx_cached(const oai4g_frame_parms_t *fp, const uint32_t rb_al
   memcpy(k.rb_alloc, rb_alloc, sizeof(k.rb_alloc));
   k.Qm = Qm; k.Qm1 = Qm1; k.mcs0 = mcs0; k.npdcch = npdcch; k.subframe = subframe;
   k.tm3 = (uint8_t)tm3; k.nb_rx = (uint8_t)nb_rx;
+  k.pmi_alloc = pmi_alloc; k.mimo_mode = mimo_mode; k.dl_power_off = dl_power_off;
   rx_cache_t &c = t_rx_cache;
   for (int i = 0; i < 32; i++)
     if (c.cfg[i] && memcmp(&c.key[i], &k, sizeof(k)) == 0) return c.cfg[i];
-  oai4g_rx_config_t *cfg = tm3 == 2 ? oai4g_rx_config_create_tm2(fp, rb_alloc, Qm, npdcch, 0, subframe, 1, (uint8_t)nb_rx)
+  oai4g_rx_config_t *cfg = tm3 == 3 ? oai4g_rx_config_create_tm56(fp, rb_alloc, Qm, mimo_mode, pmi_alloc, OAI4G_RX_PMI_UE,
+                                                                  dl_power_off, npdcch, 0, subframe, 1, (uint8_t)nb_rx)
+                          : tm3 == 2 ? oai4g_rx_config_create_tm2(fp, rb_alloc, Qm, npdcch, 0, subframe, 1, (uint8_t)nb_rx)
                           : tm3 ? oai4g_rx_config_create_tm3(fp, rb_alloc, Qm, Qm1, mcs0, npdcch, 0, subframe, 1,
                                                              (uint8_t)nb_rx)
                                 : oai4g_rx_config_create(fp, rb_alloc, Qm, npdcch, 0, subframe, 1);
@@ -4249,6 +4351,40 @@ extern "C" int oai4g_rx_pdsch_tm2(const oai4g_frame_parms_t *fp, int nb_rx, cons
     rc = n;
   else
     set_err("rx_pdsch_tm2: HIP error");
+  return rc;
+}
+
+/* rx_pdsch for the single-layer precoding modes 3..7 (dual_stream_flag 0), the reference UE's subband
+ * rule (OAI4G_RX_PMI_UE); buffers as for oai4g_rx_pdsch_tm2 */
+extern "C" int oai4g_rx_pdsch_tm56(const oai4g_frame_parms_t *fp, int nb_rx, const int32_t *const *rxdataF,
+                                   const int32_t *const *dl_ch_estimates, const uint32_t rb_alloc[4], uint8_t Qm,
+                                   uint8_t mimo_mode, uint16_t pmi_alloc, uint8_t dl_power_off,
+                                   uint8_t num_pdcch_symbols, uint8_t subframe, int16_t *llr, uint8_t *log2_maxh)
+{
+  NEED_INIT(-1);
+  oai4g_rx_config_t *cfg = rx_cached(fp, rb_alloc, Qm, 0, 0, num_pdcch_symbols, subframe, 3, nb_rx, mimo_mode, pmi_alloc,
+                                     dl_power_off);
+  if (!cfg) return -1;
+  if (rx_check_batch(cfg, 1) != 0) return -1;
+  const size_t gb = (size_t)cfg->h.nsymb * cfg->h.N * 4, gs = (gb + 255) & ~(size_t)255;
+  const int n = (int)cfg->llr_count[subframe % 10];
+  uint8_t *buf = scratch(6 * gs + (size_t)cfg->h.llr_stride * 2 + 256);
+  if (!buf) return -1;
+  int32_t *dy = (int32_t *)buf, *de = (int32_t *)(buf + 2 * gs);   /* [nb_rx][grid], planes [p * 2 + a] */
+  int16_t *dl = (int16_t *)(buf + 6 * gs);
+  bool ok = true;
+  for (int a = 0; a < nb_rx && ok; a++) ok = hipMemcpyAsync((uint8_t *)dy + a * gb, rxdataF[a], gb, hipMemcpyHostToDevice, g_scr.s) == hipSuccess;
+  for (int pa = 0; pa < 4 && ok; pa++)
+    if ((pa & 1) < nb_rx)
+      ok = hipMemcpyAsync((uint8_t *)de + pa * gb, dl_ch_estimates[pa], gb, hipMemcpyHostToDevice, g_scr.s) == hipSuccess;
+  int rc = -1;
+  if (ok && oai4g_rx_batch_tm56(cfg, 1, dy, de, dl, 0, g_scr.s) == 0 &&
+      hipMemcpyAsync(llr, dl, (size_t)n * 2, hipMemcpyDeviceToHost, g_scr.s) == hipSuccess &&
+      (!log2_maxh || hipMemcpyAsync(log2_maxh, cfg->d_shift, 1, hipMemcpyDeviceToHost, g_scr.s) == hipSuccess) &&
+      hipStreamSynchronize(g_scr.s) == hipSuccess)
+    rc = n;
+  else
+    set_err("rx_pdsch_tm56: HIP error");
   return rc;
 }
 

@@ -480,6 +480,11 @@ struct rx_dev_t {
    * when ewa[l] == 0, else mulhi(P[ea], ewa) << 1 +sat mulhi(P[eb], ewb) << 1 */
   uint8_t ea[14], eb[14];
   int16_t ewa[14], ewb[14];
+  /* TM4-6 (single-layer precoding, dual extraction; appended so the fields above keep their
+   * offsets): the map is the configuration's own copy with the RE's precoder in bits 30-31
+   * (FFT bin < 2^11 in bits 0-15, estimate column < 2^11 in bits 16-29); lvl_inc = 1 when
+   * dl_power_off == 1 (log2_maxh++, dlsch_demodulation.c:289-292) */
+  uint32_t tm56, lvl_inc;
 };
 hipError_t oai4g_launch_rx_chest(const chest_dev_t *d_ce, const rx_dev_t *d_rx, const rx_dev_t *h_rx, int n_sf,
                                  const int32_t *d_rxF, int16_t *d_llr, uint8_t *d_shift, int unscramble, hipStream_t s);
@@ -493,5 +498,9 @@ hipError_t oai4g_launch_rx_tm3qq(const rx_dev_t *d_cfg, const rx_dev_t *h_cfg, i
 hipError_t oai4g_launch_rx_tm2(const rx_dev_t *d_cfg, const rx_dev_t *h_cfg, int n_sf, const int32_t *d_rxF,
                                const int32_t *d_est, size_t plane, int16_t *d_llr, uint8_t *d_shift, int unscramble,
                                hipStream_t s);
+/* TM4-6 single-layer precoding (a configuration of oai4g_rx_config_create_tm56) */
+hipError_t oai4g_launch_rx_tm56(const rx_dev_t *d_cfg, const rx_dev_t *h_cfg, int n_sf, const int32_t *d_rxF,
+                                const int32_t *d_est, size_t plane, int16_t *d_llr, uint8_t *d_shift, int unscramble,
+                                hipStream_t s, int pil = 0);
 hipError_t oai4g_launch_rx(const rx_dev_t *d_cfg, const rx_dev_t *h_cfg, int n_sf, const int32_t *d_rxF,
                            const int32_t *d_ch, int16_t *d_llr, uint8_t *d_shift, int unscramble, hipStream_t s);

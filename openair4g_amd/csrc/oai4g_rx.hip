@@ -448,6 +448,134 @@ hipError_t oai4g_launch_rx_tm2(const rx_dev_t *d_cfg, const rx_dev_t *h_cfg, int
   return hipGetLastError();
 }
 
+/* ======================================================================================
+ * TM4-6 (MIMO modes 3..7: one codeword precoded onto two ports) with dlsim's UE (rx_pdsch,
+ * dual_stream_flag = 0, the branch at dlsch_demodulation.c:518-533):
+ *   dlsch_extract_rbs_dual      the TM2 / TM3 slots; pmi_ext per allocated PRB (:3812, :3907), read
+ *                               back per 12 (8 in pilot symbols) extracted REs (:1518-1528).  The
+ *                               configuration's own map copy carries that precoder in bits 30-31.
+ *   dlsch_channel_level         as TM2, over the un-precoded estimates; log2_maxh + 1 when
+ *                               dl_power_off == 1 (:285-292)
+ *   dlsch_channel_compensation_TM56 :1466-1669 with prec2A_TM56_128 per antenna
+ *   dlsch_detection_mrc         :2583-2621
+ *   dlsch_qpsk / 16qam / 64qam_llr, unscrambled
+ * One thread per RE, the shape of k_rx_llr_tm3; planes and layouts as for TM3 (PIL: pilot rows).
+ * ==================================================================================== */
+constexpr uint32_t RX_COL_MASK = 0x3FFFu;                     /* estimate column of a TM4-6 map word >> 16 */
+
+template <bool PIL>
+__global__ void __launch_bounds__(256) k_rx_level_tm56(const rx_dev_t *__restrict__ c, const int32_t *__restrict__ est,
+                                                       size_t plane, uint8_t *__restrict__ shift)
+{
+  __shared__ uint32_t tot[4];
+  const uint32_t sf = blockIdx.x, sfi = (c->first_sf + sf * c->sf_step) % 10, l = c->npdcch;
+  if (threadIdx.x < 4) tot[threadIdx.x] = 0;
+  __syncthreads();
+  rg32_t *map = (rg32_t *)(c->map + c->map_off[sfi][0]);
+  uint32_t part[4] = {0, 0, 0, 0};
+  for (uint32_t j = threadIdx.x; j < c->lvl_n[sfi]; j += blockDim.x) {
+    const uint32_t col = (map[j] >> 16) & RX_COL_MASK;
+#pragma unroll
+    for (uint32_t pa = 0; pa < 4; pa++)
+      if ((pa & 1u) < c->nb_rx) part[pa] += rx_h2(rx_est<PIL>(c, est, plane, pa, sf, l, col));
+  }
+#pragma unroll
+  for (int pa = 0; pa < 4; pa++)
+    if (part[pa]) atomicAdd(&tot[pa], part[pa]);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint8_t m = 0;
+    for (uint32_t pa = 0; pa < 4; pa++)
+      if ((pa & 1u) < c->nb_rx) {
+        const uint8_t v = rx_shift_of((int32_t)tot[pa], c->lvl_div[sfi]);   /* log2 monotone: max of shifts */
+        m = v > m ? v : m;
+      }
+    shift[sf] = (uint8_t)(m + c->lvl_inc);
+  }
+}
+
+template <int QM, bool PIL>
+__global__ void __launch_bounds__(256) k_rx_llr_tm56(const rx_dev_t *__restrict__ c, const int32_t *__restrict__ rxF,
+                                                     const int32_t *__restrict__ est, size_t plane,
+                                                     int16_t *__restrict__ llr, const uint8_t *__restrict__ shift,
+                                                     int unscramble)
+{
+  const uint32_t sf = blockIdx.y, k = blockIdx.x, sfi = (c->first_sf + sf * c->sf_step) % 10;
+  const uint32_t l = c->npdcch + k, len = c->len[sfi][k], nb_rx = c->nb_rx, NS = c->nsymb * c->N;
+  rg32_t *map = (rg32_t *)(c->map + c->map_off[sfi][k]);
+  int16_t *out = llr + (size_t)sf * c->llr_stride + c->llr_off[sfi][k];
+  const uint32_t sh = shift[sf], base = c->llr_off[sfi][k];
+  rg32_t *gold = (rg32_t *)(c->gold + (size_t)sfi * c->gold_words);
+  const int16_t a1 = c->a1, a2 = c->a2;
+  uint32_t mw[RX_R];
+#pragma unroll
+  for (int r = 0; r < RX_R; r++) {
+    const uint32_t j = threadIdx.x + 256 * r;
+    mw[r] = j < len ? map[j] : 0u;
+  }
+  uint32_t yv[2][RX_R], h0[2][RX_R], h1[2][RX_R];
+#pragma unroll
+  for (uint32_t a = 0; a < 2; a++)
+#pragma unroll
+    for (int r = 0; r < RX_R; r++) {
+      const uint32_t aa = a < nb_rx ? a : 0u, col = (mw[r] >> 16) & RX_COL_MASK;
+      const size_t yo = ((size_t)sf * nb_rx + aa) * NS + (size_t)l * c->N;
+      yv[a][r] = (uint32_t)rxF[yo + (mw[r] & 0xFFFFu)];
+      h0[a][r] = rx_est<PIL>(c, est, plane, aa, sf, l, col);
+      h1[a][r] = rx_est<PIL>(c, est, plane, 2 + aa, sf, l, col);
+    }
+#pragma unroll
+  for (int r = 0; r < RX_R; r++) {
+    const uint32_t j = threadIdx.x + 256 * r;
+    if (j >= len) break;
+    int16_t cr[2], ci[2], mg[2] = {0, 0}, mgb[2] = {0, 0};
+#pragma unroll
+    for (uint32_t a = 0; a < 2; a++) {
+      const uint32_t p = rx_prec_tm56(h0[a][r], h1[a][r], mw[r] >> 30);
+      rx_conj_mul(p, yv[a][r], sh, cr[a], ci[a]);
+      if (QM > 2) {
+        const int16_t m = rx_sat16((int32_t)rx_h2(p) >> sh);
+        mg[a] = (int16_t)((((int32_t)m * a1) >> 16) << 1);
+        mgb[a] = (int16_t)((((int32_t)m * a2) >> 16) << 1);
+      }
+    }
+    if (nb_rx > 1) {                                          /* dlsch_detection_mrc */
+      cr[0] = rx_sat16((cr[0] >> 1) + (cr[1] >> 1));
+      ci[0] = rx_sat16((ci[0] >> 1) + (ci[1] >> 1));
+      mg[0] = rx_sat16((mg[0] >> 1) + (mg[1] >> 1));
+      mgb[0] = rx_sat16((mgb[0] >> 1) + (mgb[1] >> 1));
+    }
+    int16_t v[6];
+    rx_llr_values<QM>(cr[0], ci[0], mg[0], mgb[0], v);
+    rx_llr_store<QM>(v, unscramble ? gold : nullptr, base + j * QM, out + QM * j);
+  }
+}
+
+template <bool PIL>
+static hipError_t launch_rx_tm56(const rx_dev_t *d_cfg, const rx_dev_t *h_cfg, int n_sf, const int32_t *d_rxF,
+                                 const int32_t *d_est, size_t plane, int16_t *d_llr, uint8_t *d_shift, int unscramble,
+                                 hipStream_t s)
+{
+  hipLaunchKernelGGL(k_rx_level_tm56<PIL>, dim3(n_sf), dim3(256), 0, s, d_cfg, d_est, plane, d_shift);
+  const dim3 g(h_cfg->n_sym, n_sf), b(256);
+  if (h_cfg->Qm == 2)
+    hipLaunchKernelGGL((k_rx_llr_tm56<2, PIL>), g, b, 0, s, d_cfg, d_rxF, d_est, plane, d_llr, d_shift, unscramble);
+  else if (h_cfg->Qm == 4)
+    hipLaunchKernelGGL((k_rx_llr_tm56<4, PIL>), g, b, 0, s, d_cfg, d_rxF, d_est, plane, d_llr, d_shift, unscramble);
+  else
+    hipLaunchKernelGGL((k_rx_llr_tm56<6, PIL>), g, b, 0, s, d_cfg, d_rxF, d_est, plane, d_llr, d_shift, unscramble);
+  return hipGetLastError();
+}
+
+hipError_t oai4g_launch_rx_tm56(const rx_dev_t *d_cfg, const rx_dev_t *h_cfg, int n_sf, const int32_t *d_rxF,
+                                const int32_t *d_est, size_t plane, int16_t *d_llr, uint8_t *d_shift, int unscramble,
+                                hipStream_t s, int pil)
+{
+  if (n_sf <= 0) return hipSuccess;
+  return pil ? launch_rx_tm56<true>(d_cfg, h_cfg, n_sf, d_rxF, d_est, plane, d_llr, d_shift, unscramble, s)
+             : launch_rx_tm56<false>(d_cfg, h_cfg, n_sf, d_rxF, d_est, plane, d_llr, d_shift, unscramble, s);
+}
+
 /* dlsch_unscrambling drop-in: llr[k] *= 2 c(k) - 1 (int16), c = the words of the Gold sequence */
 __global__ void __launch_bounds__(256) k_rx_unscramble(int16_t *__restrict__ llr, const uint32_t *__restrict__ c,
                                                        uint32_t n)

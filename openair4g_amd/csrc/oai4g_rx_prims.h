@@ -183,6 +183,22 @@ static __device__ __forceinline__ void rx_qx_llr(int16_t y0r, int16_t y0i, int16
   v[1] = D(M(met[0], met[2]), M(met[1], met[3]));
 }
 
+/* prec2A_TM56_128 (dlsch_demodulation.c:1273-1315) on one RE: the single-layer precoded channel
+ * h0 + w_p h1, w = 1, -1, j, -j for p = 0..3 (adds / subs_epi16), then mulhi(., 23170) << 1.  p = 2 / 3
+ * rotate h1 to t = (h1.im, -h1.re) first (sign_epi16 by conjugate[], int16 wrap, then the re / im
+ * shuffle) and take h0 - t / h0 + t.  Neighbouring lanes can lie in different subbands, so p selects
+ * by masks: rotate when bit 1 is set, subtract when bit 0 ^ bit 1 is. */
+static __device__ __forceinline__ uint32_t rx_prec_tm56(uint32_t h0, uint32_t h1, uint32_t p)
+{
+  const bool rot = (p & 2u) != 0, sub = ((p ^ (p >> 1)) & 1u) != 0;
+  const int16_t h1r = (int16_t)h1, h1i = (int16_t)(h1 >> 16);
+  const int32_t ur = rot ? h1i : h1r, ui = rot ? (int16_t)(-(int32_t)h1r) : h1i;
+  const int16_t gr = rx_sat16((int32_t)(int16_t)h0 + (sub ? -ur : ur));
+  const int16_t gi = rx_sat16((int32_t)(int16_t)(h0 >> 16) + (sub ? -ui : ui));
+  const int16_t r = rx_shl(rx_mh(gr, 23170), 1), i = rx_shl(rx_mh(gi, 23170), 1);
+  return (uint32_t)(uint16_t)r | ((uint32_t)(uint16_t)i << 16);
+}
+
 /* log2_approx(avg) / 2 of dlsch_channel_level (log2_approx: bits 0..30) */
 static __device__ __forceinline__ uint8_t rx_shift_of(int32_t acc, uint32_t div)
 {

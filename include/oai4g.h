@@ -639,6 +639,13 @@ size_t oai4g_ul_config_w_entries(const oai4g_ul_config_t *cfg);
 int oai4g_ul_decode_batch_harq(oai4g_ul_config_t *cfg, int n_tb, const int16_t *d_e, size_t e_stride, int16_t *d_w,
                                size_t w_stride, uint8_t rvidx, uint8_t clear, uint8_t *d_c, size_t c_stride,
                                uint8_t *d_iters, void *stream);
+/* The same round with a redundancy version and a clear flag per transport block, so that one batch
+ * holds HARQ processes at different rounds: d_rv, d_clear are device arrays [n_tb] (rv is used
+ * masked to 0..3, clear as zero / non-zero).  Transport block i is bit-exact with
+ * oai4g_ul_decode_batch_harq(rvidx = d_rv[i], clear = d_clear[i]). */
+int oai4g_ul_decode_batch_harq_tb(oai4g_ul_config_t *cfg, int n_tb, const int16_t *d_e, size_t e_stride, int16_t *d_w,
+                                  size_t w_stride, const uint8_t *d_rv, const uint8_t *d_clear, uint8_t *d_c,
+                                  size_t c_stride, uint8_t *d_iters, void *stream);
 
 /* ---------------- batched device-resident transmit path ---------------- */
 /* Plain-old-data parameter block: what rank 0 broadcasts (RCCL) to the other ranks. */
@@ -729,6 +736,23 @@ typedef struct {
 int oai4g_tx_config_set_common(oai4g_tx_config_t *cfg, const oai4g_common_sig_t *common);
 /* Stage entry for parity tests: run only the encoder kernel (payload -> packed e bits). */
 int oai4g_tx_encode(const oai4g_tx_config_t *cfg, int n_sf, const uint8_t *d_payload, void *d_work, void *stream);
+/* HARQ retransmissions in a batch: a redundancy version per transport block.  oai4g_tx_params_t's
+ * rvidx[2] holds for every subframe of oai4g_tx_batch; oai4g_tx_config_enable_tb_rv derives, once,
+ * what of the rate-matching plan depends on rv (the circular buffer's start k0, hence where every run
+ * of the buffer lands in e and which run straddles its end) for each of rv 0..3 and uploads it beside
+ * the configuration; everything else (segmentation, E, G, scrambling) is shared.  oai4g_tx_batch_rv
+ * is then oai4g_tx_batch with d_rv, a device array [n_sf][n_cw] of values 0..3 (used masked with 3):
+ * transport block (sf, cw) is bit-exact with a configuration created with rvidx[cw] = d_rv[sf][cw].
+ * Every rv is rate-matched from the transport block's own intact circular buffer w (36.212
+ * 5.1.4.1.2), re-encoded from the payload in the same kernel: what a combining receiver expects.
+ * (The drop-in oai4g_dlsch_encoding keeps the reference's stored, overlapped w instead.)
+ * enable: 0 / -1 (idempotent); batch_rv / encode_rv: -1 when enable was not called.
+ * oai4g_tx_encode_rv is the stage entry (payload -> packed e bits), as oai4g_tx_encode. */
+int oai4g_tx_config_enable_tb_rv(oai4g_tx_config_t *cfg);
+int oai4g_tx_batch_rv(const oai4g_tx_config_t *cfg, int n_sf, const uint8_t *d_payload, const uint8_t *d_rv,
+                      void *d_work, int32_t *d_iq, void *stream);
+int oai4g_tx_encode_rv(const oai4g_tx_config_t *cfg, int n_sf, const uint8_t *d_payload, const uint8_t *d_rv,
+                       void *d_work, void *stream);
 /* Stage entry: run only the modulator kernel (packed scrambled e bits in d_work, as oai4g_tx_encode
  * leaves them -> QAM / RE map / precoding / IDFT / CP -> d_iq). */
 int oai4g_tx_modulate(const oai4g_tx_config_t *cfg, int n_sf, const void *d_work, int32_t *d_iq, void *stream);
@@ -788,6 +812,27 @@ int oai4g_sync(void);
 /* Deterministic device-side payload generator: 8-byte word w = splitmix64 output for the counter
  * seed + 0x9e3779b97f4a7c15 (w + 1) (little-endian bytes). */
 int oai4g_fill_payload(uint8_t *d_payload, size_t bytes, uint64_t seed, void *stream);
+/* HARQ round state of a batch of n_slots HARQ processes, advanced on the device after a decode
+ * (dlsim's round loop, dlsim.c:2141: up to num_rounds <= 4 transmissions of a transport block, rvidx =
+ * round & 3), so that a loop of oai4g_tx_batch_rv -> channel -> receiver ->
+ * oai4g_ul_decode_batch_harq_tb -> oai4g_harq_advance needs no host synchronisation.  All arrays are
+ * device arrays.  Per slot i, from d_iters [n_slots][C] (a block failed when iters > max_iterations):
+ *   - d_counters [8] = dlsim's round_trials[4] then errs[4] (dlsim.c:2143, 3438), accumulated:
+ *     round_trials[d_round[i]]++, and errs[d_round[i]]++ when the slot failed (zero them to start);
+ *   - failed with a round left (d_round[i] + 1 < num_rounds): d_round[i]++, the payload row is kept,
+ *     d_done[i] = 0;
+ *   - else the transport block is finished: d_done[i] = 1 (decoded) or 2 (not decoded), d_round[i] =
+ *     0, d_trial[i]++ (the slot's running transport-block index; start from 0) and the slot's payload
+ *     row, row_bytes at d_payload + i row_bytes (n_cw payload_stride of a tx batch; a multiple of 8,
+ *     8-byte aligned), is refilled with row d_trial[i] n_slots + i of the oai4g_fill_payload stream of
+ *     `seed`: the bytes oai4g_fill_payload(seed) writes at byte offset (d_trial[i] n_slots + i)
+ *     row_bytes of a long enough buffer.  Trial 0 is oai4g_fill_payload over the whole buffer;
+ *   - d_rv[i][cw] = d_round[i] & 3 for cw < n_cw and d_clear[i] = (d_round[i] == 0), for the next
+ *     oai4g_tx_batch_rv / oai4g_ul_decode_batch_harq_tb.
+ * Start with d_round, d_rv zeroed and d_clear set to 1.  0 / -1. */
+int oai4g_harq_advance(int n_slots, int C, uint8_t max_iterations, int num_rounds, int n_cw, const uint8_t *d_iters,
+                       uint8_t *d_round, uint32_t *d_trial, uint8_t *d_rv, uint8_t *d_clear, uint8_t *d_done,
+                       uint32_t *d_counters, uint8_t *d_payload, size_t row_bytes, uint64_t seed, void *stream);
 
 #ifdef __cplusplus
 }

@@ -360,6 +360,16 @@ _SIGS = {
     "oai4g_get_pmi": (ctypes.c_uint8, [ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint16, ctypes.c_uint16]),
     "oai4g_set_modofdm_grid_cap": (None, [ctypes.c_int]),
     "oai4g_tx_mod_lz": (ctypes.c_int, [ctypes.c_void_p]),
+    "oai4g_harq_advance": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_uint8, ctypes.c_int, ctypes.c_int]
+                           + [ctypes.c_void_p] * 8 + [ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p]),
+    "oai4g_tx_config_enable_tb_rv": (ctypes.c_int, [ctypes.c_void_p]),
+    "oai4g_tx_batch_rv": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "oai4g_tx_encode_rv": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_void_p]),
+    "oai4g_ul_decode_batch_harq_tb": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
+                                                     ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 
@@ -1220,6 +1230,25 @@ class UlDecodeBatch:
     def launch_harq(self, rvidx, clear, stream=None):
         """One HARQ round (oai4g_ul_decode_batch_harq) on the uploaded soft bits: the per-block soft
         buffers (allocated zeroed on first use) combine this round's rvidx; clear = 1 on round 0."""
+        self._alloc_w()
+        _check(self.L.oai4g_ul_decode_batch_harq(self.cfg, self.n_tb, self.d_e, self.e_stride, self.d_w, self.w_stride,
+                                                 rvidx, clear, self.d_c, self.c_stride, self.d_it, stream) == 0)
+
+    def launch_harq_tb(self, rv, clear, stream=None):
+        """One HARQ round with a redundancy version and a clear flag per transport block
+        (oai4g_ul_decode_batch_harq_tb): rv, clear are [n_tb] arrays, uploaded here."""
+        self._alloc_w()
+        rc = np.ascontiguousarray(np.stack([np.asarray(rv, np.uint8).reshape(self.n_tb),
+                                            np.asarray(clear, np.uint8).reshape(self.n_tb)]))
+        if getattr(self, "d_rc", None) is None:
+            self.d_rc = self.L.oai4g_dev_alloc(rc.nbytes)
+            _check(bool(self.d_rc))
+        _check(self.L.oai4g_memcpy_h2d(self.d_rc, _ptr(rc), rc.nbytes) == 0)
+        _check(self.L.oai4g_ul_decode_batch_harq_tb(self.cfg, self.n_tb, self.d_e, self.e_stride, self.d_w,
+                                                    self.w_stride, self.d_rc, self.d_rc + self.n_tb, self.d_c,
+                                                    self.c_stride, self.d_it, stream) == 0)
+
+    def _alloc_w(self):
         if getattr(self, "d_w", None) is None:
             self.w_stride = (self.L.oai4g_ul_config_w_entries(self.cfg) + 63) & ~63
             nbytes = self.n_tb * self.C * self.w_stride * 2
@@ -1227,8 +1256,6 @@ class UlDecodeBatch:
             _check(bool(self.d_w))
             z = np.zeros(nbytes // 2, np.int16)
             _check(self.L.oai4g_memcpy_h2d(self.d_w, _ptr(z), nbytes) == 0)
-        _check(self.L.oai4g_ul_decode_batch_harq(self.cfg, self.n_tb, self.d_e, self.e_stride, self.d_w, self.w_stride,
-                                                 rvidx, clear, self.d_c, self.c_stride, self.d_it, stream) == 0)
 
     def soft_buffers(self):
         """[n_tb][C][w_stride] int16 HARQ soft buffers (after launch_harq)."""
@@ -1246,7 +1273,7 @@ class UlDecodeBatch:
         return it, c
 
     def close(self):
-        for p in (self.d_e, self.d_c, self.d_it, getattr(self, "d_w", None)):
+        for p in (self.d_e, self.d_c, self.d_it, getattr(self, "d_w", None), getattr(self, "d_rc", None)):
             if p:
                 self.L.oai4g_dev_free(p)
         self.L.oai4g_ul_config_destroy(self.cfg)
@@ -1468,7 +1495,7 @@ class TxPipeline:
         self.payload_bytes = n_sf * self.n_cw * params.payload_stride
         self.work_bytes = self.L.oai4g_tx_workspace_bytes(self.cfg, n_sf)
         self.iq_samples = n_sf * self.n_ant * self.spt
-        self.d_payload = self.d_work = self.d_iq = None
+        self.d_payload = self.d_work = self.d_iq = self.d_rv = None
         if alloc:
             self.d_payload = self._alloc(self.payload_bytes)
             self.d_work = self._alloc(self.work_bytes)
@@ -1522,6 +1549,30 @@ class TxPipeline:
     def run(self, stream=None):
         _check(self.L.oai4g_tx_batch(self.cfg, self.n_sf, self.d_payload, self.d_work, self.d_iq, stream) == 0)
 
+    def enable_tb_rv(self):
+        """oai4g_tx_config_enable_tb_rv: derive and upload the per-rv plan tables for run_rv."""
+        _check(self.L.oai4g_tx_config_enable_tb_rv(self.cfg) == 0)
+
+    def upload_rv(self, rv):
+        """[n_sf][n_cw] redundancy versions (0..3) for run_rv / encode_only_rv."""
+        rv = np.ascontiguousarray(np.asarray(rv, dtype=np.uint8).reshape(self.n_sf, self.n_cw))
+        if self.d_rv is None:
+            self.d_rv = self._alloc(rv.nbytes)
+        _check(self.L.oai4g_memcpy_h2d(self.d_rv, _ptr(rv), rv.nbytes) == 0)
+
+    def run_rv(self, rv=None, stream=None):
+        """oai4g_tx_batch_rv: the batch with a redundancy version per transport block (rv: [n_sf][n_cw],
+        or None for the array uploaded last)."""
+        if rv is not None:
+            self.upload_rv(rv)
+        _check(self.L.oai4g_tx_batch_rv(self.cfg, self.n_sf, self.d_payload, self.d_rv, self.d_work, self.d_iq,
+                                        stream) == 0)
+
+    def encode_only_rv(self, rv=None, stream=None):
+        if rv is not None:
+            self.upload_rv(rv)
+        _check(self.L.oai4g_tx_encode_rv(self.cfg, self.n_sf, self.d_payload, self.d_rv, self.d_work, stream) == 0)
+
     def run_timed(self, stream=None):
         ms = (ctypes.c_float * 2)()
         _check(self.L.oai4g_tx_batch_timed(self.cfg, self.n_sf, self.d_payload, self.d_work, self.d_iq, stream,
@@ -1570,10 +1621,10 @@ class TxPipeline:
         return out.reshape(self.n_sf, self.n_ant, self.spt)
 
     def close(self):
-        for p in (self.d_payload, self.d_work, self.d_iq):
+        for p in (self.d_payload, self.d_work, self.d_iq, self.d_rv):
             if p:
                 self.L.oai4g_dev_free(p)
-        self.d_payload = self.d_work = self.d_iq = None
+        self.d_payload = self.d_work = self.d_iq = self.d_rv = None
         if self.cfg:
             self.L.oai4g_tx_config_destroy(self.cfg)
             self.cfg = None

@@ -145,3 +145,54 @@ hipError_t oai4g_launch_awgn(const int32_t *d_tx, size_t tx_stride, uint32_t tx_
                      tail_len, d_rx, rx_stride, d_tx_lev, offset_db, (uint32_t)seed, (uint32_t)(seed >> 32), vec0);
   return hipGetLastError();
 }
+
+/* ---------------------------------------------------------------------------------------
+ * HARQ round state of a batch of slots (dlsim's round loop, dlsim.c:2141-3460, one slot per HARQ
+ * process), advanced on the device after a decode.  One wave per slot:
+ *   fail = any of the slot's C blocks has iters > max_it;
+ *   round_trials[round]++, and errs[round]++ on a failure (dlsim.c:2143, 3438);
+ *   failed with a round left: round++, the payload row is kept, done = 0;
+ *   else: done = 1 (decoded) or 2 (not decoded after the last round), round = 0, the slot's running
+ *   trial index advances and its payload row is refilled: row (trial, slot) of the k_fill stream of
+ *   `seed`, i.e. 8-byte word w of the row is word (trial n_slots + slot) row_words + w of that stream
+ *   (trial 0 is oai4g_fill_payload over the whole buffer);
+ *   rv[slot][cw] = round & 3, clear[slot] = (round == 0) for the next step.
+ * ------------------------------------------------------------------------------------- */
+__global__ void __launch_bounds__(64) k_harq_advance(harq_state_t st, uint32_t n_slots, uint32_t C, uint32_t max_it,
+                                                     uint32_t num_rounds, uint32_t n_cw, uint32_t row_words, uint64_t seed,
+                                                     const uint8_t *__restrict__ iters)
+{
+  const uint32_t i = blockIdx.x, lane = threadIdx.x;
+  if (i >= n_slots) return;
+  /* every lane derives the slot's (wave-uniform) state from the same loads */
+  bool fail = false;
+  for (uint32_t r = 0; r < C; r++) fail = fail || iters[(size_t)i * C + r] > max_it;
+  const uint32_t round = st.round[i] & 3u;
+  const bool again = fail && round + 1 < num_rounds;
+  const uint32_t next = again ? round + 1 : 0u;
+  const uint32_t trial = st.trial[i] + (again ? 0u : 1u);
+  if (!again) {
+    uint64_t *row = (uint64_t *)st.payload + (size_t)i * row_words;
+    const uint64_t w0 = ((uint64_t)trial * n_slots + i) * row_words;
+    for (uint32_t w = lane; w < row_words; w += 64) row[w] = oai4g_payload_word(seed, w0 + w);
+  }
+  if (lane == 0) {
+    atomicAdd(&st.counters[round], 1u);
+    if (fail) atomicAdd(&st.counters[4 + round], 1u);
+    st.round[i] = (uint8_t)next;
+    st.trial[i] = trial;
+    st.clear[i] = next == 0 ? 1 : 0;
+    st.done[i] = again ? 0 : (fail ? 2 : 1);
+    for (uint32_t cw = 0; cw < n_cw; cw++) st.rv[(size_t)i * n_cw + cw] = (uint8_t)(next & 3u);
+  }
+}
+
+hipError_t oai4g_launch_harq_advance(const harq_state_t &st, uint32_t n_slots, uint32_t C, uint32_t max_it,
+                                     uint32_t num_rounds, uint32_t n_cw, uint32_t row_words, uint64_t seed,
+                                     const uint8_t *d_iters, hipStream_t s)
+{
+  if (n_slots == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_harq_advance, dim3(n_slots), dim3(64), 0, s, st, n_slots, C, max_it, num_rounds, n_cw, row_words,
+                     seed, d_iters);
+  return hipGetLastError();
+}

@@ -1004,6 +1004,28 @@ __global__ void __launch_bounds__(256) k_ul_rm_harq(const ul_dev_t *__restrict__
   *wp = acc;
 }
 
+/* k_ul_rm_harq with the redundancy version and the clear flag of each transport block: rv[tb] (masked
+ * to 0..3, the four entries of k0cr) and clear[tb] != 0, so one batch holds HARQ processes at different
+ * rounds */
+__global__ void __launch_bounds__(256) k_ul_rm_harq_tb(const ul_dev_t *__restrict__ c, const int16_t *__restrict__ e,
+                                                       size_t e_stride, int16_t *__restrict__ w, size_t w_stride,
+                                                       const uint8_t *__restrict__ rv, const uint8_t *__restrict__ clear,
+                                                       uint32_t j0)
+{
+  const uint32_t j = j0 + blockIdx.y, tb = j / c->C, r = j - tb * c->C;
+  const ul_pat_t &P = c->pat[c->pat_of[r]];
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= P.Ncb) return;
+  int16_t *wp = w + (size_t)j * w_stride + p;
+  int16_t acc = clear[tb] ? (int16_t)0 : *wp;
+  if (P.dummy[p] != OAI4G_LTE_NULL) {
+    const int16_t *soft = e + tb * e_stride + c->off[r];
+    const uint32_t ci = P.cidx[p], E = c->E[r], k0c = P.k0cr[rv[tb] & 3u];
+    for (uint32_t q = ci >= k0c ? ci - k0c : ci + P.Nnn - k0c; q < E; q += P.Nnn) acc = (int16_t)(acc + soft[q]);
+  }
+  *wp = acc;
+}
+
 /* sub_block_deinterleaving_turbo (lte_rate_matching.c:193-243) of every block's soft buffer into
  * its decoder row, one thread per d entry (the inverse map of k_ul_rm_deint); positions past Ncb
  * read 0, as a zero-initialised buffer the RX rate matcher never writes there gives */
@@ -1022,16 +1044,18 @@ __global__ void __launch_bounds__(256) k_ul_deint_w(const ul_dev_t *__restrict__
   dfull[(size_t)j * d_stride + 96 - 3 * (Kpi - P.D) + i] = p < P.Ncb ? w[(size_t)j * w_stride + p] : (int16_t)0;
 }
 
-hipError_t oai4g_launch_ul_rm_harq(const ul_dev_t *d_cfg, const ul_dev_t *h_cfg, int n_tb, const int16_t *d_e,
-                                   size_t e_stride, int16_t *d_w, size_t w_stride, uint32_t rv, int clear,
-                                   int16_t *d_dfull, size_t d_stride, hipStream_t s)
+/* the HARQ round of every row (tb, r): the rate matcher into w (launch_rm(grid, first row)), then w ->
+ * the decoder rows, in chunks of rows within the 65535 limit of gridDim.y */
+template <typename LaunchRm>
+static hipError_t ul_rm_harq_rows(const ul_dev_t *d_cfg, const ul_dev_t *h_cfg, int n_tb, const int16_t *d_w,
+                                  size_t w_stride, int16_t *d_dfull, size_t d_stride, hipStream_t s, LaunchRm launch_rm)
 {
   if (n_tb <= 0) return hipSuccess;
   const uint32_t rows = (uint32_t)n_tb * h_cfg->C, gw = (3 * (h_cfg->Rmax << 5) + 255) / 256,
                  gd = (3 * (h_cfg->Rmax << 5) + 3 + 255) / 256;
   for (uint32_t j0 = 0; j0 < rows; j0 += 65535u) {
     const uint32_t n = rows - j0 < 65535u ? rows - j0 : 65535u;
-    hipLaunchKernelGGL(k_ul_rm_harq, dim3(gw, n), dim3(256), 0, s, d_cfg, d_e, e_stride, d_w, w_stride, rv, clear, j0);
+    launch_rm(dim3(gw, n), j0);
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return err;
     hipLaunchKernelGGL(k_ul_deint_w, dim3(gd, n), dim3(256), 0, s, d_cfg, d_w, w_stride, d_dfull, d_stride, j0);
@@ -1039,6 +1063,24 @@ hipError_t oai4g_launch_ul_rm_harq(const ul_dev_t *d_cfg, const ul_dev_t *h_cfg,
     if (err != hipSuccess) return err;
   }
   return hipSuccess;
+}
+
+hipError_t oai4g_launch_ul_rm_harq(const ul_dev_t *d_cfg, const ul_dev_t *h_cfg, int n_tb, const int16_t *d_e,
+                                   size_t e_stride, int16_t *d_w, size_t w_stride, uint32_t rv, int clear,
+                                   int16_t *d_dfull, size_t d_stride, hipStream_t s)
+{
+  return ul_rm_harq_rows(d_cfg, h_cfg, n_tb, d_w, w_stride, d_dfull, d_stride, s, [&](dim3 grid, uint32_t j0) {
+    hipLaunchKernelGGL(k_ul_rm_harq, grid, dim3(256), 0, s, d_cfg, d_e, e_stride, d_w, w_stride, rv, clear, j0);
+  });
+}
+
+hipError_t oai4g_launch_ul_rm_harq_tb(const ul_dev_t *d_cfg, const ul_dev_t *h_cfg, int n_tb, const int16_t *d_e,
+                                      size_t e_stride, int16_t *d_w, size_t w_stride, const uint8_t *d_rv,
+                                      const uint8_t *d_clear, int16_t *d_dfull, size_t d_stride, hipStream_t s)
+{
+  return ul_rm_harq_rows(d_cfg, h_cfg, n_tb, d_w, w_stride, d_dfull, d_stride, s, [&](dim3 grid, uint32_t j0) {
+    hipLaunchKernelGGL(k_ul_rm_harq_tb, grid, dim3(256), 0, s, d_cfg, d_e, e_stride, d_w, w_stride, d_rv, d_clear, j0);
+  });
 }
 
 hipError_t oai4g_launch_rm_rx(const int16_t *d_soft, uint32_t E, int16_t *d_w, const uint8_t *d_dummy,

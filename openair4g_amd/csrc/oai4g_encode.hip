@@ -703,10 +703,14 @@ static __device__ __forceinline__ void or_bits2(uint32_t *w, uint32_t bit, uint3
 /* ---------------------------------------------------------------------------------------
  * The fused encoder.
  * ------------------------------------------------------------------------------------- */
-template <bool DEBUG>
+/* RV (k_encode_rv): what phase 4 takes from the rate-matching plan per redundancy version (the run
+ * offsets and wrap marks of rm_dst, the wrap tiles, the pair schedule) comes from rvt, the table of
+ * this transport block's rv, not from cw; everything else is the same code. */
+template <bool DEBUG, bool RV = false>
 static __device__ void encode_codeword(const cfg_dev_t *__restrict__ c, uint32_t sf, uint32_t cwi,
                                        const uint8_t *__restrict__ payload, uint32_t *__restrict__ ebits,
-                                       enc_debug_t dbg, uint32_t *lds_base, int stop_phase = 99, uint32_t sf0 = 0)
+                                       enc_debug_t dbg, uint32_t *lds_base, int stop_phase = 99, uint32_t sf0 = 0,
+                                       const enc_rv_tab_t *__restrict__ rvt = nullptr)
 {
   const cw_dev_t &cw = c->cw[cwi];
   const uint32_t tid = threadIdx.x, nth = blockDim.x, lane = tid & 63, nwaves = nth >> 6;
@@ -1157,7 +1161,8 @@ static __device__ void encode_codeword(const cfg_dev_t *__restrict__ c, uint32_t
     bool once;
     {
       const uint32_t Elo = __builtin_amdgcn_readfirstlane(cw.E[sfi][0]), Ehi = __builtin_amdgcn_readfirstlane(cw.E[sfi][C - 1]);
-      const uint32_t wrapt0 = __builtin_amdgcn_readfirstlane(cw.rm_wrapt[0]), wrapt1 = __builtin_amdgcn_readfirstlane(cw.rm_wrapt[1]);
+      const uint32_t *wrapt = RV ? rvt->rm_wrapt : cw.rm_wrapt;
+      const uint32_t wrapt0 = __builtin_amdgcn_readfirstlane(wrapt[0]), wrapt1 = __builtin_amdgcn_readfirstlane(wrapt[1]);
       once = Ehi <= min(Nnn0, Nnn1) && Elo <= min(Nnn0, Nnn1) && wrapt0 != ~1u && wrapt1 != ~1u;
     }
     /* The tile pairs come from the host's schedule (cw.rm_pairs, oai4g_rm_pair_schedule): one
@@ -1166,7 +1171,7 @@ static __device__ void encode_codeword(const cfg_dev_t *__restrict__ c, uint32_t
      * (E and the offset staged in LDS and read by block index next to the stream words instead:
      * measured, the kernel 12 % slower.) */
     typedef const __attribute__((address_space(4))) uint32_t cu32_t;
-    cu32_t *pdesc = (cu32_t *)cw.rm_pairs, *ppair0 = (cu32_t *)cw.rm_pair0;
+    cu32_t *pdesc = (cu32_t *)(RV ? rvt->rm_pairs : cw.rm_pairs), *ppair0 = (cu32_t *)(RV ? rvt->rm_pair0 : cw.rm_pair0);
     cu32_t *pE = (cu32_t *)cw.E[sfi], *proff = (cu32_t *)cw.roff[sfi];
     gu32_t *gold = (gu32_t *)(c->gold_tab + (size_t)(sfi * c->n_cw + cwi) * c->ebits_words);
     uint32_t *eout = DEBUG ? nullptr : ebits + (size_t)(sf * c->n_cw + cwi) * c->ebits_words;
@@ -1184,7 +1189,8 @@ static __device__ void encode_codeword(const cfg_dev_t *__restrict__ c, uint32_t
       __syncthreads();
       const uint32_t pb = ppair0[rb0], pe = ppair0[rb1], bit0 = 32 * w0;
       /* plan rows of a pair: the descriptor's byte offset (scalar) and 4 lane from the plan bases */
-      const char *rsrc0 = (const char *)&cw.rm_src[0][0][0], *rdst0 = (const char *)&cw.rm_dst[0][0][0];
+      const char *rsrc0 = (const char *)&cw.rm_src[0][0][0];
+      const char *rdst0 = (const char *)(RV ? &rvt->rm_dst[0][0][0] : &cw.rm_dst[0][0][0]);
       /* The pair loop: round-robin pairs P = pb + wave + k nwaves of the schedule, versioned on `once`
        * (wave-uniform, loop-invariant) so that neither version tests it per pair.  The descriptor is
        * fetched two pairs ahead, and with it, one pair ahead, the block's E and e-bit offset and the
@@ -1292,6 +1298,19 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) k_en
   encode_codeword<false>(c, sf, cwi, payload, ebits, none, lds_dyn, stop_phase, sf0);
 }
 
+/* k_encode with a redundancy version per transport block: rv[sf n_cw + cw], one scalar load, masked
+ * to 0..3 so that no value indexes outside the four tables of the codeword (tabs [4][n_cw]) */
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) k_encode_rv(const cfg_dev_t *__restrict__ c, const uint8_t *__restrict__ payload,
+                                                const uint8_t *__restrict__ rv, const enc_rv_tab_t *__restrict__ tabs,
+                                                uint32_t *__restrict__ ebits)
+{
+  extern __shared__ uint32_t lds_dyn[];
+  uint32_t sf = blockIdx.x / c->n_cw, cwi = blockIdx.x % c->n_cw;
+  const uint32_t v = __builtin_amdgcn_readfirstlane((uint32_t)rv[blockIdx.x]) & 3u;
+  enc_debug_t none = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  encode_codeword<false, true>(c, sf, cwi, payload, ebits, none, lds_dyn, 99, 0, tabs + (v * c->n_cw + cwi));
+}
+
 __global__ void __launch_bounds__(256) k_encode_debug(const cfg_dev_t *__restrict__ c, uint32_t sf, uint32_t cwi,
                                                       const uint8_t *__restrict__ payload, enc_debug_t dbg)
 {
@@ -1340,6 +1359,20 @@ static hipError_t launch_encode_impl(const cfg_dev_t *d_cfg, const cfg_dev_t *h_
   }
   hipLaunchKernelGGL(k_encode, dim3(n_sf * h_cfg->n_cw), dim3(256), lds, s, d_cfg, d_payload, d_ebits, stop_phase,
                      (uint32_t)sf0);
+  return hipGetLastError();
+}
+
+hipError_t oai4g_launch_encode_rv(const cfg_dev_t *d_cfg, const cfg_dev_t *h_cfg, int n_sf, const uint8_t *d_payload,
+                                  const uint8_t *d_rv, const enc_rv_tab_t *d_tabs, uint32_t *d_ebits, hipStream_t s)
+{
+  if (n_sf <= 0) return hipSuccess;
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void *)k_encode_rv, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(k_encode_rv, dim3(n_sf * h_cfg->n_cw), dim3(256), enc_lds_bytes(h_cfg), s, d_cfg, d_payload, d_rv,
+                     d_tabs, d_ebits);
   return hipGetLastError();
 }
 
@@ -1468,8 +1501,8 @@ hipError_t oai4g_launch_subblock_bytes(uint32_t D, const uint8_t *d_dfull, uint8
 
 /* lte_rate_matching_turbo on caller bytes: compaction of the non-NULL entries of w[0..Ncb)
  * (block-wide prefix count), then e[k] = compact[(start + k) mod nnz].  One workgroup. */
-__global__ void __launch_bounds__(256) k_rm_bytes(const uint8_t *__restrict__ w, uint32_t Ncb, uint32_t k0,
-                                                   uint32_t E, uint8_t *__restrict__ e, uint32_t *status)
+static __device__ __forceinline__ void rm_bytes_block(const uint8_t *__restrict__ w, uint32_t Ncb, uint32_t k0,
+                                                      uint32_t E, uint8_t *__restrict__ e, uint32_t *status)
 {
   extern __shared__ uint8_t comp[];
   __shared__ uint32_t wsum[4];
@@ -1503,10 +1536,35 @@ __global__ void __launch_bounds__(256) k_rm_bytes(const uint8_t *__restrict__ w,
   if (tid == 0) status[0] = 0;
 }
 
+__global__ void __launch_bounds__(256) k_rm_bytes(const uint8_t *__restrict__ w, uint32_t Ncb, uint32_t k0,
+                                                   uint32_t E, uint8_t *__restrict__ e, uint32_t *status)
+{
+  rm_bytes_block(w, Ncb, k0, E, e, status);
+}
+
+/* the code blocks of one transport block, one workgroup each (dlsch_encoding's retransmission rounds,
+ * dlsch_coding.c:383-406): block r rate-matches the Ncb bytes at w + blk[r].woff into e + blk[r].eoff;
+ * a block with E = 0 (the "RM condition" exit) writes nothing */
+__global__ void __launch_bounds__(256) k_rm_bytes_blocks(const uint8_t *__restrict__ w, const rm_blk_t *__restrict__ blk,
+                                                          uint8_t *__restrict__ e, uint32_t *status)
+{
+  const rm_blk_t b = blk[blockIdx.x];
+  if (b.E == 0) return;
+  rm_bytes_block(w + b.woff, b.Ncb, b.k0, b.E, e + b.eoff, status + blockIdx.x);
+}
+
 hipError_t oai4g_launch_rm_bytes(const uint8_t *d_w, uint32_t Ncb, uint32_t k0, uint32_t E, uint8_t *d_e,
                                  uint32_t *d_status, hipStream_t s)
 {
   hipLaunchKernelGGL(k_rm_bytes, dim3(1), dim3(256), (Ncb + 15) & ~15u, s, d_w, Ncb, k0, E, d_e, d_status);
+  return hipGetLastError();
+}
+
+hipError_t oai4g_launch_rm_bytes_blocks(const uint8_t *d_w, const rm_blk_t *d_blk, int C, uint32_t max_Ncb, uint8_t *d_e,
+                                        uint32_t *d_status, hipStream_t s)
+{
+  if (C <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_rm_bytes_blocks, dim3(C), dim3(256), (max_Ncb + 15) & ~15u, s, d_w, d_blk, d_e, d_status);
   return hipGetLastError();
 }
 
@@ -1533,15 +1591,12 @@ hipError_t oai4g_launch_scramble_bytes(uint8_t *d_e, int n_entries, uint32_t c_i
   return hipGetLastError();
 }
 
-/* deterministic payload: 8-byte word w = splitmix64 output for the counter seed + gamma (w + 1) */
+/* deterministic payload: 8-byte word w = oai4g_payload_word(seed, w) */
 __global__ void k_fill(uint8_t *__restrict__ d, size_t bytes, uint64_t seed)
 {
   size_t nw = bytes / 8;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < (bytes + 7) / 8; i += (size_t)gridDim.x * blockDim.x) {
-    uint64_t z = seed + 0x9e3779b97f4a7c15ull * (i + 1);
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    z ^= z >> 31;
+    const uint64_t z = oai4g_payload_word(seed, i);
     if (i < nw) ((uint64_t *)d)[i] = z;
     else
       for (size_t b = 0; b < bytes - 8 * i; b++) d[8 * i + b] = (uint8_t)(z >> (8 * b));

@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <vector>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <vector>
 
@@ -782,6 +783,7 @@ struct oai4g_tx_config {
   uint16_t *d_remap = nullptr;
   std::vector<uint16_t> h_remap;
   uint32_t *d_gold = nullptr;           /* [10][n_cw][ebits_words] scrambling words */
+  enc_rv_tab_t *d_rvtab = nullptr;      /* [4][n_cw] per-rv plan tables (oai4g_tx_config_enable_tb_rv), else null */
   /* build_stat_tm's inputs (host only) */
   std::vector<uint32_t> h_crs;          /* [10][6][200] packed CRS IQ of pilot entry i, index m (empty without CRS) */
   std::vector<uint32_t> h_ctl;          /* [10][14][ctl_planes][N] packed IQ of the static REs of set_control /
@@ -1427,6 +1429,8 @@ static void release_cfg(oai4g_tx_config *cfg)
   if (cfg->d_remap) hipFree(cfg->d_remap);
   if (cfg->d_stat) hipFree(cfg->d_stat);
   if (cfg->d_gold) hipFree(cfg->d_gold);
+  if (cfg->d_rvtab) hipFree(cfg->d_rvtab);
+  cfg->d_rvtab = nullptr;
   cfg->d_stat = nullptr;
   cfg->d_gold = nullptr;
   cfg->d = nullptr;
@@ -1487,6 +1491,101 @@ extern "C" int oai4g_tx_encode(const oai4g_tx_config_t *cfg, int n_sf, const uin
 {
   NEED_INIT(-1);
   HCK(oai4g_launch_encode(cfg->d, &cfg->h, 0, n_sf, d_payload, (uint32_t *)d_work, (hipStream_t)stream), -1);
+  return 0;
+}
+
+/* Compacted start of the circular buffer for redundancy version rv and block size index ki
+ * (lte_rate_matching.c:523-524: k0 = R (2 + rv ceil(Ncb / 8R) 2), less the NULLs below it), as
+ * derive_cfg computes it per block for the configuration's own rvidx */
+static uint32_t rm_k0c_of_rv(const cw_dev_t &c, uint32_t ki, uint32_t rv)
+{
+  const uint32_t R = c.Rk[ki], Ncb = c.Ncbk[ki], ncol8 = R << 3;
+  const uint32_t k0 = R * (2 + rv * ((Ncb % ncol8 ? 1 : 0) + Ncb / ncol8) * 2);
+  uint32_t before = 0;
+  for (uint32_t i = 0; i < c.nnull[ki]; i++) before += c.nullpos[ki][i] < k0 ? 1u : 0u;
+  return k0 - before;
+}
+
+extern "C" int oai4g_tx_config_enable_tb_rv(oai4g_tx_config_t *cfg)
+{
+  NEED_INIT(-1);
+  if (!cfg) { set_err("tx_config_enable_tb_rv: null configuration"); return -1; }
+  if (cfg->d_rvtab) return 0;
+  const uint32_t n_cw = cfg->h.n_cw;
+  std::vector<enc_rv_tab_t> tabs(4 * (size_t)n_cw);
+  for (uint32_t rv = 0; rv < 4; rv++)
+    for (uint32_t cw = 0; cw < n_cw; cw++) {
+      /* the configuration's own plan builder on a copy of the codeword with this rv's k0c: the
+       * limited-buffer extension and the general-path test hook apply per rv as they do there.  The
+       * "RM condition" exit (Ncb < Kw without the extension) depends on no rv: a configuration that
+       * takes it was refused at creation. */
+      std::unique_ptr<cw_dev_t> c(new cw_dev_t(cfg->h.cw[cw]));
+      enc_rv_tab_t &t = tabs[rv * n_cw + cw];
+      memset(&t, 0, sizeof(t));
+      /* with one block size (n0 = 0) index 0 mirrors index 1, whose NULL list is the size's */
+      c->k0ck[1] = rm_k0c_of_rv(*c, 1, rv);
+      c->k0ck[0] = c->n0 ? rm_k0c_of_rv(*c, 0, rv) : c->k0ck[1];
+      for (int ki = 0; ki < 2; ki++) {
+        if (c->k0ck[ki] >= c->Nnnk[ki]) {
+          set_err("tx_config_enable_tb_rv: rv %u starts at %u of %u circular-buffer entries", rv, c->k0ck[ki], c->Nnnk[ki]);
+          return -1;
+        }
+        rm_plan(*c, ki);
+      }
+      if (oai4g_rm_pair_schedule(c->C, c->n0, c->ntk, c->rm_wrapt, c->rm_pairs, c->rm_pair0) < 0) {
+        set_err("tx_config_enable_tb_rv: rate-matching pair schedule");
+        return -1;
+      }
+      if (memcmp(c->rm_src, cfg->h.cw[cw].rm_src, sizeof(c->rm_src)) != 0) {
+        set_err("tx_config_enable_tb_rv: the source plan depends on rv");
+        return -1;
+      }
+      memcpy(t.rm_dst, c->rm_dst, sizeof(t.rm_dst));
+      memcpy(t.rm_pair0, c->rm_pair0, sizeof(t.rm_pair0));
+      memcpy(t.rm_pairs, c->rm_pairs, sizeof(t.rm_pairs));
+      memcpy(t.rm_wrapt, c->rm_wrapt, sizeof(t.rm_wrapt));
+      memcpy(t.k0ck, c->k0ck, sizeof(t.k0ck));
+    }
+  enc_rv_tab_t *d = nullptr;
+  HCK(hipMalloc(&d, tabs.size() * sizeof(enc_rv_tab_t)), -1);
+  if (hipMemcpy(d, tabs.data(), tabs.size() * sizeof(enc_rv_tab_t), hipMemcpyHostToDevice) != hipSuccess) {
+    hipFree(d);
+    set_err("tx_config_enable_tb_rv: upload failed");
+    return -1;
+  }
+  cfg->d_rvtab = d;
+  return 0;
+}
+
+static int iq_aligned(const int32_t *d_iq);
+
+static int tb_rv_ready(const oai4g_tx_config_t *cfg, const uint8_t *d_rv, const char *who)
+{
+  if (!cfg || !cfg->d_rvtab) { set_err("%s: oai4g_tx_config_enable_tb_rv was not called", who); return 0; }
+  if (!d_rv) { set_err("%s: null rv array", who); return 0; }
+  return 1;
+}
+
+extern "C" int oai4g_tx_encode_rv(const oai4g_tx_config_t *cfg, int n_sf, const uint8_t *d_payload, const uint8_t *d_rv,
+                                  void *d_work, void *stream)
+{
+  NEED_INIT(-1);
+  if (!tb_rv_ready(cfg, d_rv, "tx_encode_rv")) return -1;
+  HCK(oai4g_launch_encode_rv(cfg->d, &cfg->h, n_sf, d_payload, d_rv, cfg->d_rvtab, (uint32_t *)d_work,
+                             (hipStream_t)stream), -1);
+  return 0;
+}
+
+extern "C" int oai4g_tx_batch_rv(const oai4g_tx_config_t *cfg, int n_sf, const uint8_t *d_payload, const uint8_t *d_rv,
+                                 void *d_work, int32_t *d_iq, void *stream)
+{
+  NEED_INIT(-1);
+  if (!tb_rv_ready(cfg, d_rv, "tx_batch_rv")) return -1;
+  if (n_sf <= 0) return 0;
+  if (!iq_aligned(d_iq)) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  HCK(oai4g_launch_encode_rv(cfg->d, &cfg->h, n_sf, d_payload, d_rv, cfg->d_rvtab, (uint32_t *)d_work, s), -1);
+  HCK(oai4g_launch_modofdm(cfg->d, &cfg->h, 0, n_sf, (const uint32_t *)d_work, d_iq, s), -1);
   return 0;
 }
 
@@ -1694,6 +1793,31 @@ extern "C" int oai4g_fill_payload(uint8_t *d_payload, size_t bytes, uint64_t see
   return 0;
 }
 
+extern "C" int oai4g_harq_advance(int n_slots, int C, uint8_t max_iterations, int num_rounds, int n_cw,
+                                  const uint8_t *d_iters, uint8_t *d_round, uint32_t *d_trial, uint8_t *d_rv,
+                                  uint8_t *d_clear, uint8_t *d_done, uint32_t *d_counters, uint8_t *d_payload,
+                                  size_t row_bytes, uint64_t seed, void *stream)
+{
+  NEED_INIT(-1);
+  if (n_slots <= 0) return 0;
+  if (C < 1 || C > OAI4G_MAX_SEGMENTS || num_rounds < 1 || num_rounds > 4 || n_cw < 1 || n_cw > 2) {
+    set_err("harq_advance: C %d (1..16), num_rounds %d (1..4), n_cw %d (1..2)", C, num_rounds, n_cw);
+    return -1;
+  }
+  if (!d_iters || !d_round || !d_trial || !d_rv || !d_clear || !d_done || !d_counters || !d_payload) {
+    set_err("harq_advance: null array");
+    return -1;
+  }
+  if (row_bytes == 0 || (row_bytes & 7) || ((uintptr_t)d_payload & 7) || row_bytes / 8 > 0xFFFFFFFFu) {
+    set_err("harq_advance: payload rows must be 8-byte aligned multiples of 8 bytes (row_bytes %zu)", row_bytes);
+    return -1;
+  }
+  harq_state_t st = {d_round, d_trial, d_rv, d_clear, d_done, d_counters, d_payload};
+  HCK(oai4g_launch_harq_advance(st, (uint32_t)n_slots, (uint32_t)C, max_iterations, (uint32_t)num_rounds, (uint32_t)n_cw,
+                                (uint32_t)(row_bytes / 8), seed, d_iters, (hipStream_t)stream), -1);
+  return 0;
+}
+
 /* ------------------------------------------------------------------------------------------
  * dlsch containers (new_eNB_dlsch / free_eNB_dlsch, dlsch_coding.c:85-220)
  * ---------------------------------------------------------------------------------------- */
@@ -1898,16 +2022,83 @@ static void params_from_dlsch(const oai4g_frame_parms_t *fp, uint8_t num_pdcch, 
   p->payload_stride = (maxA + 3 + 15) & ~15u;
 }
 
+/* dlsch_encoding for round != 0 (dlsch_coding.c:286, 383-406): no CRC, segmentation, coding or
+ * interleaving; every block's stored w is rate-matched again with the round's rvidx.  The caller's
+ * w[r] bytes are taken as they lie, Ncb <= 3 Kpi of them from the row's start: in the reference's
+ * w[MAX_NUM_DLSCH_SEGMENTS][3 * 6144] a K = 6144 row (3 Kpi = 18528) runs into the next one, which
+ * the first round's interleaver has overwritten, and that is what the reference reads.  One upload,
+ * one launch (a workgroup per block), one download; only e[0..G) is written. */
+static int dlsch_encoding_retx(const oai4g_frame_parms_t *fp, uint8_t num_pdcch_symbols, const oai4g_dlsch_t *dlsch,
+                               oai4g_dl_harq_t *h, int frame, uint8_t subframe)
+{
+  const uint32_t C = h->C, Qm = oai4g_get_Qm(h->mcs), Nl = h->Nl ? h->Nl : 1;   /* Nl as the first round takes it */
+  if (C < 1 || C > OAI4G_MAX_SEGMENTS || dlsch->Kmimo == 0 || dlsch->Mdlharq == 0) {
+    set_err("dlsch_encoding: round %u with C %u, Nl %u, Kmimo %u, Mdlharq %u", h->round, C, Nl, dlsch->Kmimo, dlsch->Mdlharq);
+    return -1;
+  }
+  const int Gi = oai4g_get_G(fp, h->nb_rb, h->rb_alloc, (uint8_t)Qm, (uint8_t)Nl, num_pdcch_symbols, frame, subframe);
+  if (Gi <= 0 || Gi > OAI4G_MAX_CHANNEL_BITS) { set_err("dlsch_encoding: G=%d out of range", Gi); return -1; }
+  const uint32_t G = (uint32_t)Gi, Gp = G / Nl / Qm, GpmodC = Gp % C;
+  const uint32_t Nir = OAI4G_NSOFT / dlsch->Kmimo / (dlsch->Mdlharq < 8 ? dlsch->Mdlharq : 8);
+  /* device layout: w rows | block descriptors | status words (uploaded as 0) | e: the upload ends
+   * behind the status words and the download starts at them */
+  rm_blk_t blk[OAI4G_MAX_SEGMENTS];
+  memset(blk, 0, sizeof(blk));
+  const size_t st_bytes = 4 * OAI4G_MAX_SEGMENTS;
+  size_t wtot = 0;
+  uint32_t etot = 0, max_Ncb = 0;
+  for (uint32_t r = 0; r < C; r++) {
+    const uint32_t RTC = h->RTC[r], Kw = 3 * (RTC << 5);
+    if (RTC == 0 || Kw > OAI4G_W_BYTES) { set_err("dlsch_encoding: RTC[%u] = %u", r, RTC); return -1; }
+    const uint32_t Ncb = (Nir / C < Kw) ? Nir / C : Kw;
+    if (Ncb < Kw) {   /* lte_rate_matching_turbo returns 0: e untouched, r_offset stays (lte_rate_matching.c:518-521) */
+      printf("Exiting, RM condition (Nir %u, Nsoft %u, Kw %u\n", Nir, OAI4G_NSOFT, Kw);
+      continue;
+    }
+    const uint32_t ncol8 = RTC << 3;
+    blk[r].woff = (uint32_t)wtot;
+    blk[r].Ncb = Ncb;
+    blk[r].k0 = RTC * (2 + h->rvidx * ((Ncb % ncol8 ? 1 : 0) + Ncb / ncol8) * 2);
+    blk[r].E = r < C - GpmodC ? Nl * Qm * (Gp / C) : Nl * Qm * ((GpmodC ? 1 : 0) + Gp / C);
+    blk[r].eoff = etot;
+    etot += blk[r].E;
+    wtot += (Ncb + 63) & ~(size_t)63;
+    max_Ncb = Ncb > max_Ncb ? Ncb : max_Ncb;
+  }
+  if (etot == 0) return 0;
+  if (etot > OAI4G_MAX_CHANNEL_BITS) { set_err("dlsch_encoding: %u e bits", etot); return -1; }
+  const size_t off_blk = wtot, off_s = off_blk + sizeof(blk), off_e = off_s + st_bytes;
+  std::vector<uint8_t> up(off_e, 0);
+  for (uint32_t r = 0; r < C; r++)
+    if (blk[r].E) memcpy(up.data() + blk[r].woff, h->w[r], blk[r].Ncb);
+  memcpy(up.data() + off_blk, blk, sizeof(blk));
+  uint8_t *buf = scratch(off_e + etot + 64);
+  if (!buf) return -1;
+  HCK(hipMemcpyAsync(buf, up.data(), off_e, hipMemcpyHostToDevice, g_scr.s), -1);
+  HCK(oai4g_launch_rm_bytes_blocks(buf, (const rm_blk_t *)(buf + off_blk), (int)C, max_Ncb, buf + off_e,
+                                   (uint32_t *)(buf + off_s), g_scr.s), -1);
+  std::vector<uint8_t> down(st_bytes + etot);
+  HCK(hipMemcpyAsync(down.data(), buf + off_s, down.size(), hipMemcpyDeviceToHost, g_scr.s), -1);
+  HCK(hipStreamSynchronize(g_scr.s), -1);
+  /* a row without a single non-NULL byte has nothing to repeat (the block's status word is 1, its e
+   * bytes were not written): no stored w of a first round looks like that, so e stays as it was */
+  uint32_t status[OAI4G_MAX_SEGMENTS];
+  memcpy(status, down.data(), st_bytes);
+  for (uint32_t r = 0; r < C; r++)
+    if (status[r]) {
+      set_err("dlsch_encoding: round %u, w[%u] holds no non-NULL entry below Ncb %u", h->round, r, blk[r].Ncb);
+      return -1;
+    }
+  memcpy(h->e, down.data() + st_bytes, etot);
+  return 0;
+}
+
 extern "C" int oai4g_dlsch_encoding(uint8_t *a, const oai4g_frame_parms_t *frame_parms, uint8_t num_pdcch_symbols,
                                     oai4g_dlsch_t *dlsch, int frame, uint8_t subframe)
 {
-  (void)frame;
   NEED_INIT(-1);
   oai4g_dl_harq_t *h = dlsch->harq_processes[dlsch->current_harq_pid];
-  if (h->round != 0) {
-    set_err("dlsch_encoding: retransmission rounds re-use the stored w (not supported by the drop-in yet)");
-    return -1;
-  }
+  if (h->round != 0) return dlsch_encoding_retx(frame_parms, num_pdcch_symbols, dlsch, h, frame, subframe);
   oai4g_tx_params_t p;
   uint8_t Nl[2];
   params_from_dlsch(frame_parms, num_pdcch_symbols, dlsch, nullptr, subframe, &p, Nl);
@@ -2560,6 +2751,25 @@ extern "C" int oai4g_ul_decode_batch_harq(oai4g_ul_config_t *cfg, int n_tb, cons
   hipStream_t s = (hipStream_t)stream;
   HCK(oai4g_launch_ul_rm_harq(cfg->d, &cfg->h, n_tb, d_e, e_stride, d_w, w_stride, rvidx, clear, cfg->d_dfull,
                               cfg->d_stride, s), -1);
+  return ul_decode_rows(cfg, n_tb, d_c, c_stride, d_iters, s);
+}
+
+/* the same round with rv and clear per transport block (device arrays [n_tb]) */
+extern "C" int oai4g_ul_decode_batch_harq_tb(oai4g_ul_config_t *cfg, int n_tb, const int16_t *d_e, size_t e_stride,
+                                             int16_t *d_w, size_t w_stride, const uint8_t *d_rv, const uint8_t *d_clear,
+                                             uint8_t *d_c, size_t c_stride, uint8_t *d_iters, void *stream)
+{
+  NEED_INIT(-1);
+  if (n_tb <= 0) return 0;
+  if (!cfg || !d_rv || !d_clear) { set_err("ul_decode_batch_harq_tb: null configuration, rv or clear array"); return -1; }
+  if (c_stride < cfg->Kplus / 8 || e_stride < cfg->G || w_stride < oai4g_ul_config_w_entries(cfg)) {
+    set_err("ul_decode_batch_harq_tb: strides too small");
+    return -1;
+  }
+  if (ul_scratch(cfg, n_tb) != 0) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  HCK(oai4g_launch_ul_rm_harq_tb(cfg->d, &cfg->h, n_tb, d_e, e_stride, d_w, w_stride, d_rv, d_clear, cfg->d_dfull,
+                                 cfg->d_stride, s), -1);
   return ul_decode_rows(cfg, n_tb, d_c, c_stride, d_iters, s);
 }
 

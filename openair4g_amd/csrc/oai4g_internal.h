@@ -86,6 +86,16 @@ static __device__ __forceinline__ uint32_t ld_u32_any(const uint8_t *p)
   return *(const __attribute__((address_space(1))) u32_a1_t *)p;
 }
 
+/* the device payload generator (k_fill; the refills of k_harq_advance): 8-byte word w of the stream of
+ * `seed` is splitmix64's output for the counter seed + gamma (w + 1) */
+static inline __host__ __device__ uint64_t oai4g_payload_word(uint64_t seed, uint64_t w)
+{
+  uint64_t z = seed + 0x9e3779b97f4a7c15ull * (w + 1);
+  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+  return z ^ (z >> 31);
+}
+
 /* twiddle table offsets (packed int16 pairs), indexed by log2 of the level size */
 static inline __host__ __device__ uint32_t oai4g_tw_offset(int log2s)
 {
@@ -243,8 +253,27 @@ struct cfg_dev_t {
   uint32_t pad2;
 };
 
+/* What of a codeword's rate-matching plan depends on the redundancy version, for k_encode_rv
+ * (oai4g_tx_config_enable_tb_rv): the k0c-relative run offsets and wrap marks of rm_dst, the wrap
+ * tiles and the pair schedule's wrap bits.  One table per (rv, codeword), [4][n_cw], outside
+ * cfg_dev_t; rm_dst, rm_pairs and rm_pair0 have cw_dev_t's layouts, so a pair descriptor's byte
+ * offset addresses cw.rm_src and this rm_dst alike. */
+struct enc_rv_tab_t {
+  uint32_t rm_dst[2][OAI4G_RM_TILES + 1][32];
+  uint32_t rm_pair0[OAI4G_MAX_CB + 1];
+  uint32_t rm_pairs[OAI4G_MAX_CB * ((OAI4G_RM_TILES + 1) / 2)];
+  uint32_t rm_wrapt[2];
+  uint32_t k0ck[2];            /* the rv's compacted start per block size (host-side record) */
+  uint32_t pad[3];
+};
+static_assert(sizeof(enc_rv_tab_t) % 16 == 0, "tables are laid out back to back");
+
 /* ---------------- launch helpers implemented in the .hip files ---------------- */
 /* encoder path */
+/* k_encode_rv: transport block (sf, cw) takes its redundancy version d_rv[sf n_cw + cw] & 3 and that
+ * rv's table d_tabs[rv n_cw + cw] */
+hipError_t oai4g_launch_encode_rv(const cfg_dev_t *d_cfg, const cfg_dev_t *h_cfg, int n_sf, const uint8_t *d_payload,
+                                  const uint8_t *d_rv, const enc_rv_tab_t *d_tabs, uint32_t *d_ebits, hipStream_t s);
 hipError_t oai4g_launch_encode(const cfg_dev_t *d_cfg, const cfg_dev_t *h_cfg, int sf0, int n_sf,
                                const uint8_t *d_payload, uint32_t *d_ebits, hipStream_t s);
 hipError_t oai4g_encode_occupancy(const cfg_dev_t *h_cfg, int *blocks_per_cu, size_t *lds_bytes);
@@ -265,6 +294,13 @@ hipError_t oai4g_launch_turbo_bytes(const uint8_t *d_c, int nbytes, uint8_t *d_o
 hipError_t oai4g_launch_subblock_bytes(uint32_t D, const uint8_t *d_dfull, uint8_t *d_w, hipStream_t s);
 hipError_t oai4g_launch_rm_bytes(const uint8_t *d_w, uint32_t Ncb, uint32_t k0, uint32_t E, uint8_t *d_e,
                                  uint32_t *d_status, hipStream_t s);
+/* k_rm_bytes for the C blocks of a transport block in one launch: per block the byte offset of its
+ * w in d_w, Ncb, k0, E and the offset of its e bytes in d_e */
+struct rm_blk_t {
+  uint32_t woff, Ncb, k0, E, eoff, pad[3];
+};
+hipError_t oai4g_launch_rm_bytes_blocks(const uint8_t *d_w, const rm_blk_t *d_blk, int C, uint32_t max_Ncb, uint8_t *d_e,
+                                        uint32_t *d_status, hipStream_t s);
 hipError_t oai4g_launch_scramble_bytes(uint8_t *d_e, int n_entries, uint32_t c_init, const uint32_t *d_gold_x1,
                                        const uint32_t *d_gold_x2j, hipStream_t s);
 hipError_t oai4g_launch_fill(uint8_t *d, size_t bytes, uint64_t seed, hipStream_t s);
@@ -310,6 +346,10 @@ hipError_t oai4g_launch_ul_rm_deint(const ul_dev_t *d_cfg, const ul_dev_t *h_cfg
 hipError_t oai4g_launch_ul_rm_harq(const ul_dev_t *d_cfg, const ul_dev_t *h_cfg, int n_tb, const int16_t *d_e,
                                    size_t e_stride, int16_t *d_w, size_t w_stride, uint32_t rv, int clear,
                                    int16_t *d_dfull, size_t d_stride, hipStream_t s);
+/* the same with rv (0..3) and clear (0 / 1) per transport block: device arrays [n_tb] */
+hipError_t oai4g_launch_ul_rm_harq_tb(const ul_dev_t *d_cfg, const ul_dev_t *h_cfg, int n_tb, const int16_t *d_e,
+                                      size_t e_stride, int16_t *d_w, size_t w_stride, const uint8_t *d_rv,
+                                      const uint8_t *d_clear, int16_t *d_dfull, size_t d_stride, hipStream_t s);
 hipError_t oai4g_launch_rm_rx(const int16_t *d_soft, uint32_t E, int16_t *d_w, const uint8_t *d_dummy,
                               const uint32_t *d_cidx, uint32_t Ncb, uint32_t Nnn, uint32_t k0c, int clear, hipStream_t s);
 hipError_t oai4g_launch_subblock_deint(uint32_t D, int16_t *d_dfull, const int16_t *d_w, hipStream_t s);
@@ -447,6 +487,19 @@ hipError_t oai4g_launch_signal_energy(const int32_t *d_x, int n, size_t stride, 
 hipError_t oai4g_launch_awgn(const int32_t *d_tx, size_t tx_stride, uint32_t tx_len, const int32_t *d_tail,
                              uint32_t tail_len, int32_t *d_rx, size_t rx_stride, int n, const int32_t *d_tx_lev,
                              double offset_db, uint64_t seed, uint32_t vec0, hipStream_t s);
+/* device arrays of oai4g_harq_advance (oai4g_channel.hip: k_harq_advance) */
+struct harq_state_t {
+  uint8_t *round;        /* [n_slots] 0 .. num_rounds - 1 */
+  uint32_t *trial;       /* [n_slots] running transport-block index of the slot */
+  uint8_t *rv;           /* [n_slots][n_cw] */
+  uint8_t *clear;        /* [n_slots] */
+  uint8_t *done;         /* [n_slots] 0: retransmission follows; 1: finished, decoded; 2: finished, not decoded */
+  uint32_t *counters;    /* [8] round_trials[4] | errs[4] */
+  uint8_t *payload;      /* [n_slots][8 row_words] bytes, 8-byte aligned */
+};
+hipError_t oai4g_launch_harq_advance(const harq_state_t &st, uint32_t n_slots, uint32_t C, uint32_t max_it,
+                                     uint32_t num_rounds, uint32_t n_cw, uint32_t row_words, uint64_t seed,
+                                     const uint8_t *d_iters, hipStream_t s);
 hipError_t oai4g_launch_unscramble(int16_t *d_llr, const uint32_t *d_c, int n, hipStream_t s);
 hipError_t oai4g_launch_chest(const chest_dev_t *d_cfg, const chest_dev_t *h_cfg, int n_sf, const int32_t *d_rxF,
                               int32_t *d_est, hipStream_t s);

@@ -17,11 +17,18 @@ one, tests/test_gpu_dlsim.py):
     (perfect_ce = 0, high_speed_flag = 1), rx_pdsch, dlsch_unscrambling, dlsch_decoding with the
     16-bit decoder (dlsim's default, llr8_flag = 0 at dlsim.c:339; `-L` selects the 8-bit one, llr8
     here) and MAX_TURBO_ITERATIONS = 4 (PHY/CODING/defs.h:51);
-  - a trial errs when dlsch_decoding returns more than max_turbo_iterations (:3330-3350); one round
-    (the CSVs hold no retransmission counts).
+  - a trial errs when dlsch_decoding returns more than max_turbo_iterations (:3330-3350).  run_batch /
+    run_point run one round (the CSVs hold no retransmission counts);
+  - with num_rounds = 2..4, run_steps runs dlsim's round loop (:2141, rvidx = round & 3 at :2331): a
+    failed transport block is sent again with the next redundancy version and combined into the kept
+    soft buffers (dlsch_decoding.c:348-383, clear = (round == 0)).  Every batch slot is a HARQ process
+    with its own round, so one step carries first transmissions and retransmissions side by side.
 On the GPU: TxPipeline (k_encode + k_modofdm with CRS + control) -> k_signal_energy -> k_awgn ->
 k_fep over [trial][2 subframes] -> k_rx_chest (estimation + demodulation + unscrambling, elements two
-subframes apart) -> k_ul_rm_deint + k_td16.  Nothing here runs on the CPU but bookkeeping."""
+subframes apart) -> k_ul_rm_deint + k_td16.  The round loop: k_encode_rv (a redundancy version per
+slot) ... k_ul_rm_harq_tb (rv and clear per slot) + k_td16 -> k_harq_advance, which keeps the rounds,
+dlsim's round_trials / errs counters and the payload refills on the device: a step needs no host
+synchronisation.  Nothing here runs on the CPU but bookkeeping."""
 import ctypes
 import math
 
@@ -44,7 +51,7 @@ class DlsimBler:
     """Batched BLER trials of one (N_RB_DL, MCS) configuration; see the module docstring."""
 
     def __init__(self, mcs, N_RB_DL=25, batch=4096, subframe=7, num_pdcch_symbols=1, Nid_cell=0, rnti=0x1234,
-                 max_iterations=4, with_dci=True, llr8=False):
+                 max_iterations=4, with_dci=True, llr8=False, num_rounds=1):
         self.L = init()
         self.mcs, self.N_RB, self.B, self.sf = mcs, N_RB_DL, batch, subframe
         self.max_it = max_iterations
@@ -87,6 +94,22 @@ class DlsimBler:
             _check(self.L.oai4g_ul_config_set_decoder(self.dec.cfg, 8) == 0)
         self.C = self.dec.C
         self.offset_fac = 10 * math.log10(self.N / (12.0 * N_RB_DL))
+        if not 1 <= num_rounds <= 4:
+            raise ValueError("num_rounds must be 1..4 (dlsim's round loop)")
+        self.num_rounds = num_rounds
+        self.d_state = None
+        if num_rounds > 1:
+            # per-slot round state (oai4g_harq_advance): round | rv | clear | done [B] bytes each, then the
+            # running trial index [B] and round_trials[4] | errs[4] as uint32
+            self.tx.enable_tb_rv()
+            self.dec._alloc_w()
+            nb = (4 * batch + 7) & ~7
+            self.d_state = L.oai4g_dev_alloc(nb + 4 * batch + 32)
+            _check(bool(self.d_state))
+            self.d_round, self.d_rv = self.d_state, self.d_state + batch
+            self.d_clear, self.d_done = self.d_state + 2 * batch, self.d_state + 3 * batch
+            self.d_trial, self.d_counters = self.d_state + nb, self.d_state + nb + 4 * batch
+            self._state_bytes = nb + 4 * batch + 32
 
     def sigma_offset(self, snr_db, pa_db=0.0):
         return self.offset_fac - snr_db - pa_db
@@ -109,6 +132,62 @@ class DlsimBler:
         if not want_bits:
             return err
         return err, c, self.tx.download_payload()
+
+    def reset_rounds(self, seed):
+        """Every slot at round 0 of its transport block 0: payloads oai4g_fill_payload(seed), counters 0."""
+        if self.d_state is None:
+            raise OAI4GError("DlsimBler was created with num_rounds = 1")
+        B = self.B
+        st = np.zeros(self._state_bytes, np.uint8)
+        st[2 * B:3 * B] = 1                                   # clear
+        _check(self.L.oai4g_memcpy_h2d(self.d_state, _ptr(st), st.nbytes) == 0)
+        self.tx.fill_payload(seed)
+        self._seed, self._step = seed, 0
+
+    def step(self, snr_db):
+        """One subframe of every slot, enqueued without a host synchronisation: transmit with the slot's
+        rv, fresh noise, receive, combine and decode with the slot's (rv, clear), advance the rounds."""
+        L, B = self.L, self.B
+        _check(L.oai4g_tx_batch_rv(self.tx.cfg, B, self.tx.d_payload, self.d_rv, self.tx.d_work, self.tx.d_iq,
+                                   None) == 0)
+        d_iq = self.tx.d_iq
+        _check(L.oai4g_signal_energy_batch(d_iq, B, self.spt, self.spt, self.d_lev, None) == 0)
+        _check(L.oai4g_awgn_batch(d_iq, self.spt, self.spt, self.d_tail, self.spt, self.fep.d_rx, 2 * self.spt, B,
+                                  self.d_lev, self.sigma_offset(snr_db), self._seed, self._step * B, None) == 0)
+        self.fep.run()
+        self.rx.launch_estimated(self.ce, self.fep.d_rxF, 1)
+        _check(L.oai4g_ul_decode_batch_harq_tb(self.dec.cfg, B, self.rx.d_llr, self.rx.stride, self.dec.d_w,
+                                               self.dec.w_stride, self.d_rv, self.d_clear, self.dec.d_c,
+                                               self.dec.c_stride, self.dec.d_it, None) == 0)
+        _check(L.oai4g_harq_advance(B, self.C, self.max_it, self.num_rounds, 1, self.dec.d_it, self.d_round,
+                                    self.d_trial, self.d_rv, self.d_clear, self.d_done, self.d_counters,
+                                    self.tx.d_payload, self.p.payload_stride, self._seed, None) == 0)
+        self._step += 1
+
+    def round_state(self):
+        """(round, rv, clear, done, trial, counters) after the steps enqueued so far (synchronises)."""
+        B = self.B
+        st = np.empty(self._state_bytes, np.uint8)
+        _check(self.L.oai4g_sync() == 0)
+        _check(self.L.oai4g_memcpy_d2h(_ptr(st), self.d_state, st.nbytes) == 0)
+        nb = (4 * B + 7) & ~7
+        u32 = st[nb:].view(np.uint32)
+        return st[:B].copy(), st[B:2 * B].copy(), st[2 * B:3 * B].copy(), st[3 * B:4 * B].copy(), u32[:B].copy(), \
+            u32[B:B + 8].copy()
+
+    def run_steps(self, snr_db, n_steps, seed=1):
+        """n_steps subframes of dlsim's round loop over the batch, from a reset state, with no host
+        synchronisation between steps.  Returns dlsim's counters and figures (dlsim.c:3685-3713):
+        round_trials[4], errs[4], effective_rate = round_trials[0] / sum(round_trials) and throughput =
+        rate effective_rate with rate = TBS / G."""
+        self.reset_rounds(seed)
+        for _ in range(n_steps):
+            self.step(snr_db)
+        cnt = self.round_state()[5]
+        rt, errs = [int(v) for v in cnt[:4]], [int(v) for v in cnt[4:]]
+        eff = rt[0] / max(1, sum(rt))
+        return dict(round_trials=rt, errs=errs, effective_rate=eff, rate=self.TBS / self.G,
+                    throughput=self.TBS / self.G * eff)
 
     def tx_lev(self):
         out = np.empty(self.B, np.int32)
@@ -133,6 +212,9 @@ class DlsimBler:
             o.close()
         self.L.oai4g_dev_free(self.d_tail)
         self.L.oai4g_dev_free(self.d_lev)
+        if self.d_state:
+            self.L.oai4g_dev_free(self.d_state)
+            self.d_state = None
 
 
 def tb_bytes_from_blocks(c, TBS, C, K_list, F):

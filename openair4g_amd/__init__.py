@@ -586,10 +586,9 @@ def rx_pdsch_siso(fp, rxdataF, dl_ch, rb_alloc, Qm, num_pdcch, subframe):
     return out[:n], sh.value
 
 
-def rx_pdsch_tm3(fp, rxF, est, rb_alloc, Qm0, Qm1, mcs0, num_pdcch, subframe):
-    """rx_pdsch for TM3 (dual_stream_flag = 0): rxF = [nb_rx][nsymb*N], est[(p, a)] = [nsymb*N].
-    Returns (codeword-0 LLRs, log2_maxh)."""
-    init()
+def _rx_dual_args(rxF, est):
+    """(nb_rx, antenna pointers, plane pointers [p * 2 + a], the arrays they point into) of a two-port
+    drop-in: rxF = [nb_rx][nsymb*N], est[(p, a)] = [nsymb*N]"""
     nb_rx = len(rxF)
     rx = [np.ascontiguousarray(r, dtype=np.int32) for r in rxF]
     keep = {k: np.ascontiguousarray(v, dtype=np.int32) for k, v in est.items()}
@@ -598,56 +597,38 @@ def rx_pdsch_tm3(fp, rxF, est, rb_alloc, Qm0, Qm1, mcs0, num_pdcch, subframe):
         if a < nb_rx:
             ep[2 * p_ + a] = arr.ctypes.data
     rp = (ctypes.c_void_p * 2)(*[r.ctypes.data for r in rx] + [None] * (2 - nb_rx))
-    out = np.zeros(14 * 1200 * 6 + 64, dtype=np.int16)
+    return nb_rx, rp, ep, (rx, keep)
+
+
+def _rx_dual(entry, fp, rxF, est, rb_alloc, args, n_out=1):
+    """one two-port drop-in: `args` go between rb_alloc and the n_out LLR outputs; returns the outputs
+    cut to the stream length, then log2_maxh"""
+    init()
+    nb_rx, rp, ep, _keep = _rx_dual_args(rxF, est)
+    outs = [np.zeros(14 * 1200 * 6 + 64, dtype=np.int16) for _ in range(n_out)]
     sh = ctypes.c_uint8()
     ra = (ctypes.c_uint32 * 4)(*rb_alloc)
-    n = lib().oai4g_rx_pdsch_tm3(ctypes.byref(fp), nb_rx, rp, ep, ra, Qm0, Qm1, mcs0, num_pdcch, subframe, _ptr(out),
-                                 ctypes.byref(sh))
+    n = getattr(lib(), entry)(ctypes.byref(fp), nb_rx, rp, ep, ra, *args, *[_ptr(o) for o in outs], ctypes.byref(sh))
     _check(n >= 0)
-    return out[:n], sh.value
+    return (*[o[:n] for o in outs], sh.value)
+
+
+def rx_pdsch_tm3(fp, rxF, est, rb_alloc, Qm0, Qm1, mcs0, num_pdcch, subframe):
+    """rx_pdsch for TM3 (dual_stream_flag = 0): rxF = [nb_rx][nsymb*N], est[(p, a)] = [nsymb*N].
+    Returns (codeword-0 LLRs, log2_maxh)."""
+    return _rx_dual("oai4g_rx_pdsch_tm3", fp, rxF, est, rb_alloc, (Qm0, Qm1, mcs0, num_pdcch, subframe))
 
 
 def rx_pdsch_tm3_2cw(fp, rxF, est, rb_alloc, mcs0, num_pdcch, subframe):
     """rx_pdsch for TM3 with both codewords QPSK: rxF = [nb_rx][nsymb*N], est[(p, a)] = [nsymb*N].
     Returns (codeword-0 LLRs, codeword-1 LLRs, log2_maxh)."""
-    init()
-    nb_rx = len(rxF)
-    rx = [np.ascontiguousarray(r, dtype=np.int32) for r in rxF]
-    keep = {k: np.ascontiguousarray(v, dtype=np.int32) for k, v in est.items()}
-    ep = (ctypes.c_void_p * 4)()
-    for (p_, a), arr in keep.items():
-        if a < nb_rx:
-            ep[2 * p_ + a] = arr.ctypes.data
-    rp = (ctypes.c_void_p * 2)(*[r.ctypes.data for r in rx] + [None] * (2 - nb_rx))
-    o0 = np.zeros(14 * 1200 * 2 + 64, dtype=np.int16)
-    o1 = np.zeros_like(o0)
-    sh = ctypes.c_uint8()
-    ra = (ctypes.c_uint32 * 4)(*rb_alloc)
-    n = lib().oai4g_rx_pdsch_tm3_2cw(ctypes.byref(fp), nb_rx, rp, ep, ra, mcs0, num_pdcch, subframe, _ptr(o0),
-                                     _ptr(o1), ctypes.byref(sh))
-    _check(n >= 0)
-    return o0[:n], o1[:n], sh.value
+    return _rx_dual("oai4g_rx_pdsch_tm3_2cw", fp, rxF, est, rb_alloc, (mcs0, num_pdcch, subframe), n_out=2)
 
 
 def rx_pdsch_tm2(fp, rxF, est, rb_alloc, Qm, num_pdcch, subframe):
     """rx_pdsch for TM2 (ALAMOUTI): rxF = [nb_rx][nsymb*N], est[(p, a)] = [nsymb*N].
     Returns (LLRs, log2_maxh)."""
-    init()
-    nb_rx = len(rxF)
-    rx = [np.ascontiguousarray(r, dtype=np.int32) for r in rxF]
-    keep = {k: np.ascontiguousarray(v, dtype=np.int32) for k, v in est.items()}
-    ep = (ctypes.c_void_p * 4)()
-    for (p_, a), arr in keep.items():
-        if a < nb_rx:
-            ep[2 * p_ + a] = arr.ctypes.data
-    rp = (ctypes.c_void_p * 2)(*[r.ctypes.data for r in rx] + [None] * (2 - nb_rx))
-    out = np.zeros(14 * 1200 * 6 + 64, dtype=np.int16)
-    sh = ctypes.c_uint8()
-    ra = (ctypes.c_uint32 * 4)(*rb_alloc)
-    n = lib().oai4g_rx_pdsch_tm2(ctypes.byref(fp), nb_rx, rp, ep, ra, Qm, num_pdcch, subframe, _ptr(out),
-                                 ctypes.byref(sh))
-    _check(n >= 0)
-    return out[:n], sh.value
+    return _rx_dual("oai4g_rx_pdsch_tm2", fp, rxF, est, rb_alloc, (Qm, num_pdcch, subframe))
 
 
 # the subband of a PRB in the TM4-6 receiver: the reference UE's 4-RB rule / the transmitter's get_pmi
@@ -657,44 +638,28 @@ RX_PMI_UE, RX_PMI_TX = 0, 1
 def rx_pdsch_tm56(fp, rxF, est, rb_alloc, Qm, mimo_mode, pmi_alloc, dl_power_off, num_pdcch, subframe):
     """rx_pdsch for the single-layer precoding modes 3..7 (TM4-6, dual_stream_flag = 0, the reference UE's
     subband rule): rxF = [nb_rx][nsymb*N], est[(p, a)] = [nsymb*N].  Returns (LLRs, log2_maxh)."""
-    init()
-    nb_rx = len(rxF)
-    rx = [np.ascontiguousarray(r, dtype=np.int32) for r in rxF]
-    keep = {k: np.ascontiguousarray(v, dtype=np.int32) for k, v in est.items()}
-    ep = (ctypes.c_void_p * 4)()
-    for (p_, a), arr in keep.items():
-        if a < nb_rx:
-            ep[2 * p_ + a] = arr.ctypes.data
-    rp = (ctypes.c_void_p * 2)(*[r.ctypes.data for r in rx] + [None] * (2 - nb_rx))
-    out = np.zeros(14 * 1200 * 6 + 64, dtype=np.int16)
-    sh = ctypes.c_uint8()
-    ra = (ctypes.c_uint32 * 4)(*rb_alloc)
-    n = lib().oai4g_rx_pdsch_tm56(ctypes.byref(fp), nb_rx, rp, ep, ra, Qm, mimo_mode, pmi_alloc, dl_power_off,
-                                  num_pdcch, subframe, _ptr(out), ctypes.byref(sh))
-    _check(n >= 0)
-    return out[:n], sh.value
+    return _rx_dual("oai4g_rx_pdsch_tm56", fp, rxF, est, rb_alloc,
+                    (Qm, mimo_mode, pmi_alloc, dl_power_off, num_pdcch, subframe))
 
 
-class RxBatchTM3:
-    """Device-resident batched TM3 demodulation (oai4g_rx_batch_tm3): codeword 0's LLRs from the FEP
-    output of nb_rx antennas and the four estimate planes (ports 0 / 1 per antenna)."""
+class _RxBatchDual:
+    """Device-resident batched demodulation of a two-port mode: the FEP output of nb_rx antennas and the
+    four estimate planes (ports 0 / 1 per antenna), or the pilot rows, to LLRs.  A subclass creates its
+    configuration and names its batch entry points (_pilots None: estimate planes only)."""
+    _batch = _pilots = None
 
-    def __init__(self, fp, rb_alloc, Qm0, Qm1, mcs0, num_pdcch, rnti, n_sf, nb_rx=2, first_subframe=0,
-                 subframe_step=1):
+    def _setup(self, create, fp, rb_alloc, args, n_sf, nb_rx):
+        """create(fp, rb_alloc, *args) is the configuration; then the device buffers of n_sf subframes"""
         init()
         self.L = lib()
-        ra = (ctypes.c_uint32 * 4)(*rb_alloc)
-        self.cfg = self.L.oai4g_rx_config_create_tm3(ctypes.byref(fp), ra, Qm0, Qm1, mcs0, num_pdcch, rnti,
-                                                     first_subframe, subframe_step, nb_rx)
+        self.cfg = getattr(self.L, create)(ctypes.byref(fp), (ctypes.c_uint32 * 4)(*rb_alloc), *args)
         _check(bool(self.cfg))
-        self._setup(fp, n_sf, nb_rx)
-
-    def _setup(self, fp, n_sf, nb_rx):
         self.fp, self.n_sf, self.nb_rx = fp, n_sf, nb_rx
         self.stride = self.L.oai4g_rx_llr_stride(self.cfg)
         self.plane = n_sf * fp.symbols_per_tti * fp.ofdm_symbol_size
         self.d_est = self.L.oai4g_dev_alloc(4 * self.plane * 4)
         self.d_llr = self.L.oai4g_dev_alloc(n_sf * self.stride * 2)
+        self.d_llr1 = self.d_pil = None
         _check(bool(self.d_est) and bool(self.d_llr))
         self._chest = {}
 
@@ -728,14 +693,20 @@ class RxBatchTM3:
                                                 self.est_plane(p, a), stream) == 0)
 
     def launch(self, d_rxF, unscramble=1, stream=None):
-        _check(self.L.oai4g_rx_batch_tm3(self.cfg, self.n_sf, d_rxF, self.d_est, self.d_llr, unscramble, stream) == 0)
+        _check(getattr(self.L, self._batch)(self.cfg, self.n_sf, d_rxF, self.d_est, self.d_llr, unscramble, stream) == 0)
 
     def _pil(self):
-        if not getattr(self, "d_pil", None):
+        if not self.d_pil:
             self.pil_plane = self.n_sf * 4 * self.fp.ofdm_symbol_size * 2
             self.d_pil = self.L.oai4g_dev_alloc(4 * self.pil_plane * 4)
             _check(bool(self.d_pil))
         return self.d_pil
+
+    def _llr1(self):
+        if not self.d_llr1:
+            self.d_llr1 = self.L.oai4g_dev_alloc(self.n_sf * self.stride * 2)
+            _check(bool(self.d_llr1))
+        return self.d_llr1
 
     def estimate_pilots(self, d_rxF, first_subframe=0, subframe_step=1, stream=None):
         """The four pilot-row estimations (oai4g_chest_batch_pilots): 5 rows per subframe instead of 14."""
@@ -748,36 +719,19 @@ class RxBatchTM3:
                                                        stream) == 0)
 
     def launch_pilots(self, d_rxF, unscramble=1, stream=None):
-        """oai4g_rx_batch_tm3_pilots: the demodulation from the pilot rows (estimate_pilots)"""
-        _check(self.L.oai4g_rx_batch_tm3_pilots(self.cfg, self.n_sf, d_rxF, self._pil(), self.d_llr, unscramble,
-                                                stream) == 0)
+        """the demodulation from the pilot rows (estimate_pilots)"""
+        if not self._pilots:
+            raise RuntimeError(f"{type(self).__name__} demodulates from the estimate planes only")
+        _check(getattr(self.L, self._pilots)(self.cfg, self.n_sf, d_rxF, self._pil(), self.d_llr, unscramble, stream) == 0)
 
-    def launch_2cw_pilots(self, d_rxF, unscramble=1, stream=None):
-        if not getattr(self, "d_llr1", None):
-            self.d_llr1 = self.L.oai4g_dev_alloc(self.n_sf * self.stride * 2)
-            _check(bool(self.d_llr1))
-        _check(self.L.oai4g_rx_batch_tm3_2cw_pilots(self.cfg, self.n_sf, d_rxF, self._pil(), self.d_llr, self.d_llr1,
-                                                    unscramble, stream) == 0)
-
-    def launch_2cw(self, d_rxF, unscramble=1, stream=None):
-        """both codewords QPSK: codeword 0 into d_llr, codeword 1 into d_llr1 (llrs1())"""
-        if not getattr(self, "d_llr1", None):
-            self.d_llr1 = self.L.oai4g_dev_alloc(self.n_sf * self.stride * 2)
-            _check(bool(self.d_llr1))
-        _check(self.L.oai4g_rx_batch_tm3_2cw(self.cfg, self.n_sf, d_rxF, self.d_est, self.d_llr, self.d_llr1,
-                                             unscramble, stream) == 0)
-
-    def llrs1(self):
+    def _download(self, ptr):
         _check(self.L.oai4g_sync() == 0)
         out = np.empty((self.n_sf, self.stride), dtype=np.int16)
-        _check(self.L.oai4g_memcpy_d2h(_ptr(out), self.d_llr1, out.nbytes) == 0)
+        _check(self.L.oai4g_memcpy_d2h(_ptr(out), ptr, out.nbytes) == 0)
         return out
 
     def llrs(self):
-        _check(self.L.oai4g_sync() == 0)
-        out = np.empty((self.n_sf, self.stride), dtype=np.int16)
-        _check(self.L.oai4g_memcpy_d2h(_ptr(out), self.d_llr, out.nbytes) == 0)
-        return out
+        return self._download(self.d_llr)
 
     def estimates(self):
         _check(self.L.oai4g_sync() == 0)
@@ -791,56 +745,55 @@ class RxBatchTM3:
             for cfg in cfgs:
                 self.L.oai4g_chest_config_destroy(cfg)
         self._chest = {}
-        self.L.oai4g_dev_free(self.d_est)
-        self.L.oai4g_dev_free(self.d_llr)
-        if getattr(self, "d_llr1", None):
-            self.L.oai4g_dev_free(self.d_llr1)
-            self.d_llr1 = None
-        if getattr(self, "d_pil", None):
-            self.L.oai4g_dev_free(self.d_pil)
-            self.d_pil = None
+        for ptr in (self.d_est, self.d_llr, self.d_llr1, self.d_pil):
+            if ptr:
+                self.L.oai4g_dev_free(ptr)
+        self.d_llr1 = self.d_pil = None
         self.L.oai4g_rx_config_destroy(self.cfg)
 
-class RxBatchTM2(RxBatchTM3):
-    """Device-resident batched TM2 demodulation (oai4g_rx_batch_tm2): the ALAMOUTI-combined stream's
-    LLRs from the FEP output of nb_rx antennas and the four estimate planes (ports 0 / 1 per antenna)."""
+
+class RxBatchTM3(_RxBatchDual):
+    """Device-resident batched TM3 demodulation (oai4g_rx_batch_tm3): codeword 0's LLRs; with both
+    codewords QPSK launch_2cw / launch_2cw_pilots add codeword 1's (llrs1())."""
+    _batch, _pilots = "oai4g_rx_batch_tm3", "oai4g_rx_batch_tm3_pilots"
+
+    def __init__(self, fp, rb_alloc, Qm0, Qm1, mcs0, num_pdcch, rnti, n_sf, nb_rx=2, first_subframe=0,
+                 subframe_step=1):
+        self._setup("oai4g_rx_config_create_tm3", fp, rb_alloc,
+                    (Qm0, Qm1, mcs0, num_pdcch, rnti, first_subframe, subframe_step, nb_rx), n_sf, nb_rx)
+
+    def launch_2cw_pilots(self, d_rxF, unscramble=1, stream=None):
+        _check(self.L.oai4g_rx_batch_tm3_2cw_pilots(self.cfg, self.n_sf, d_rxF, self._pil(), self.d_llr, self._llr1(),
+                                                    unscramble, stream) == 0)
+
+    def launch_2cw(self, d_rxF, unscramble=1, stream=None):
+        """both codewords QPSK: codeword 0 into d_llr, codeword 1 into d_llr1 (llrs1())"""
+        _check(self.L.oai4g_rx_batch_tm3_2cw(self.cfg, self.n_sf, d_rxF, self.d_est, self.d_llr, self._llr1(),
+                                             unscramble, stream) == 0)
+
+    def llrs1(self):
+        return self._download(self.d_llr1)
+
+
+class RxBatchTM2(_RxBatchDual):
+    """Device-resident batched TM2 demodulation (oai4g_rx_batch_tm2): the ALAMOUTI-combined stream's LLRs."""
+    _batch = "oai4g_rx_batch_tm2"
 
     def __init__(self, fp, rb_alloc, Qm, num_pdcch, rnti, n_sf, nb_rx=2, first_subframe=0, subframe_step=1):
-        init()
-        self.L = lib()
-        ra = (ctypes.c_uint32 * 4)(*rb_alloc)
-        self.cfg = self.L.oai4g_rx_config_create_tm2(ctypes.byref(fp), ra, Qm, num_pdcch, rnti, first_subframe,
-                                                     subframe_step, nb_rx)
-        _check(bool(self.cfg))
-        self._setup(fp, n_sf, nb_rx)
-
-    def launch(self, d_rxF, unscramble=1, stream=None):
-        _check(self.L.oai4g_rx_batch_tm2(self.cfg, self.n_sf, d_rxF, self.d_est, self.d_llr, unscramble, stream) == 0)
+        self._setup("oai4g_rx_config_create_tm2", fp, rb_alloc,
+                    (Qm, num_pdcch, rnti, first_subframe, subframe_step, nb_rx), n_sf, nb_rx)
 
 
-class RxBatchTM56(RxBatchTM3):
-    """Device-resident batched TM4-6 demodulation (oai4g_rx_batch_tm56): the single-layer precoded
-    codeword's LLRs from the FEP output of nb_rx antennas and the four estimate planes (launch), or from
-    the pilot rows (estimate_pilots / launch_pilots)."""
+class RxBatchTM56(_RxBatchDual):
+    """Device-resident batched TM4-6 demodulation (oai4g_rx_batch_tm56 / _tm56_pilots): the single-layer
+    precoded codeword's LLRs."""
+    _batch, _pilots = "oai4g_rx_batch_tm56", "oai4g_rx_batch_tm56_pilots"
 
     def __init__(self, fp, rb_alloc, Qm, mimo_mode, pmi_alloc, num_pdcch, rnti, n_sf, nb_rx=2, first_subframe=0,
                  subframe_step=1, pmi_rule=RX_PMI_UE, dl_power_off=1):
-        init()
-        self.L = lib()
-        ra = (ctypes.c_uint32 * 4)(*rb_alloc)
-        self.cfg = self.L.oai4g_rx_config_create_tm56(ctypes.byref(fp), ra, Qm, mimo_mode, pmi_alloc, pmi_rule,
-                                                      dl_power_off, num_pdcch, rnti, first_subframe, subframe_step,
-                                                      nb_rx)
-        _check(bool(self.cfg))
-        self._setup(fp, n_sf, nb_rx)
-
-    def launch(self, d_rxF, unscramble=1, stream=None):
-        _check(self.L.oai4g_rx_batch_tm56(self.cfg, self.n_sf, d_rxF, self.d_est, self.d_llr, unscramble, stream) == 0)
-
-    def launch_pilots(self, d_rxF, unscramble=1, stream=None):
-        """oai4g_rx_batch_tm56_pilots: the demodulation from the pilot rows (estimate_pilots)"""
-        _check(self.L.oai4g_rx_batch_tm56_pilots(self.cfg, self.n_sf, d_rxF, self._pil(), self.d_llr, unscramble,
-                                                 stream) == 0)
+        self._setup("oai4g_rx_config_create_tm56", fp, rb_alloc, (Qm, mimo_mode, pmi_alloc, pmi_rule, dl_power_off,
+                                                                  num_pdcch, rnti, first_subframe, subframe_step, nb_rx),
+                    n_sf, nb_rx)
 
 
 def dlsch_unscrambling(fp, rnti, G, llr, q, Ns, mbsfn_flag=0):

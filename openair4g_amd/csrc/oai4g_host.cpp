@@ -3764,6 +3764,7 @@ extern "C" int oai4g_phich_group_seq(const oai4g_frame_parms_t *fp, uint16_t fir
  * -------------------------------------------------------------------------------------- */
 struct oai4g_rx_config {
   oai4g_frame_parms_t fp;
+  rx_mode_t mode;
   rx_dev_t h;
   rx_dev_t *d = nullptr;
   uint32_t *d_map = nullptr, *d_gold = nullptr;
@@ -4004,18 +4005,19 @@ static const uint8_t k_mumimo_off[29][3] = {{0, 6, 5}, {0, 4, 5}, {0, 4, 5}, {0,
                                             {1, 0, 0}, {0, 0, 0}, {0, 1, 0}, {1, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0},
                                             {0, 0, 0}};
 
-/* TM4-6: the precoder word, the subband rule and dl_power_off of oai4g_rx_config_create_tm56 */
-struct rx_tm56_t {
-  uint8_t mimo_mode;
-  uint16_t pmi_alloc;
+/* what a mode takes beyond the common arguments (no padding: the drop-ins' cache compares it bytewise).
+ * TM3: codeword 1's modulation and codeword 0's MCS; TM4-6: the precoder word, the subband rule and
+ * dl_power_off of oai4g_rx_config_create_tm56 */
+struct rx_parms_t {
   int pmi_rule;
-  uint8_t dl_power_off;
+  uint16_t pmi_alloc;
+  uint8_t nb_rx, Qm1, mcs0, mimo_mode, dl_power_off, pad;
 };
 
 /* pmi_ext of one allocated PRB.  OAI4G_RX_PMI_UE: dlsch_extract_rbs_dual's (pmi >> ((prb >> 2) << 1)) & 3
  * (:3812, :3907) — 4-RB subbands at every bandwidth; pmi is an unsigned short promoted to int, so a count
  * of 16..31 reads 0 (counts >= 32 are refused by the caller).  OAI4G_RX_PMI_TX: the transmitter's get_pmi. */
-static uint32_t rx_pmi_of(const oai4g_frame_parms_t *fp, const rx_tm56_t &t, uint32_t prb)
+static uint32_t rx_pmi_of(const oai4g_frame_parms_t *fp, const rx_parms_t &t, uint32_t prb)
 {
   if (t.pmi_rule == OAI4G_RX_PMI_TX) return oai4g_get_pmi(fp->N_RB_DL, t.mimo_mode, t.pmi_alloc, (uint16_t)prb);
   const uint32_t cnt = (prb >> 2) << 1;
@@ -4024,25 +4026,25 @@ static uint32_t rx_pmi_of(const oai4g_frame_parms_t *fp, const rx_tm56_t &t, uin
 
 static oai4g_rx_config_t *rx_config_build(const oai4g_frame_parms_t *fp, const uint32_t rb_alloc[4], uint8_t Qm,
                                           uint8_t num_pdcch_symbols, uint16_t rnti, uint8_t first_subframe,
-                                          uint8_t subframe_step, int tm3, uint8_t Qm1, uint8_t mcs0, uint8_t nb_rx,
-                                          int tm2 = 0, const rx_tm56_t *tm56 = nullptr)
+                                          uint8_t subframe_step, rx_mode_t mode, const rx_parms_t &mp)
 {
   NEED_INIT(nullptr);
-  const bool dual = tm3 || tm2 || tm56;
+  const bool tm2 = mode == RX_TM2, tm3 = mode == RX_TM3, tm56 = mode == RX_TM56, dual = mode != RX_SISO;
+  const uint8_t nb_rx = mp.nb_rx, Qm1 = mp.Qm1, mcs0 = mp.mcs0;
   if (tm56) {
     if (fp->nb_antennas_tx != 2 || fp->mode1_flag != 0 || (Qm != 2 && Qm != 4 && Qm != 6) || nb_rx < 1 || nb_rx > 2 ||
         num_pdcch_symbols < 1 || num_pdcch_symbols > 3 ||
-        (tm56->pmi_rule != OAI4G_RX_PMI_UE && tm56->pmi_rule != OAI4G_RX_PMI_TX)) {
+        (mp.pmi_rule != OAI4G_RX_PMI_UE && mp.pmi_rule != OAI4G_RX_PMI_TX)) {
       set_err("rx_config_tm56: two TX ports (mode1_flag 0), Qm 2/4/6, 1-2 RX antennas, 1..3 PDCCH symbols, "
               "pmi_rule OAI4G_RX_PMI_UE / _TX");
       return nullptr;
     }
-    if (tm56->mimo_mode < OAI4G_UNIFORM_PRECODING11 || tm56->mimo_mode > OAI4G_PUSCH_PRECODING0) {
+    if (mp.mimo_mode < OAI4G_UNIFORM_PRECODING11 || mp.mimo_mode > OAI4G_PUSCH_PRECODING0) {
       set_err("rx_config_tm56: mimo_mode %u: rx_pdsch demodulates the single-layer modes 3..7 (mode 8 ends in "
-              "\"Unknown MIMO mode\", dlsch_demodulation.c:595-597)", tm56->mimo_mode);
+              "\"Unknown MIMO mode\", dlsch_demodulation.c:595-597)", mp.mimo_mode);
       return nullptr;
     }
-    if (tm56->pmi_rule == OAI4G_RX_PMI_UE && tm56->pmi_alloc != 0)
+    if (mp.pmi_rule == OAI4G_RX_PMI_UE && mp.pmi_alloc != 0)
       for (int prb = 64; prb < fp->N_RB_DL; prb++)
         if (rx_alloc_bit(rb_alloc, prb)) {
           set_err("rx_config_tm56: PRB %d is allocated: the reference UE shifts its 16-bit pmi_alloc by %d there "
@@ -4075,6 +4077,7 @@ static oai4g_rx_config_t *rx_config_build(const oai4g_frame_parms_t *fp, const u
   }
   auto *cfg = new oai4g_rx_config();
   cfg->fp = *fp;
+  cfg->mode = mode;
   rx_dev_t &h = cfg->h;
   memset(&h, 0, sizeof(h));
   h.N = N;
@@ -4086,29 +4089,25 @@ static oai4g_rx_config_t *rx_config_build(const oai4g_frame_parms_t *fp, const u
   h.sf_step = subframe_step;
   h.a1 = Qm == 4 ? 20724 : (Qm == 6 ? 20225 : 0);          /* QAM16_n1 / QAM64_n1 (impl_defs_top.h:215-224) */
   h.a2 = Qm == 6 ? 10112 : 0;                               /* QAM64_n2 */
-  h.tm3 = tm3 ? 1u : 0u;
-  h.tm2 = tm2 ? 1u : 0u;
   h.nb_rx = dual ? nb_rx : 1u;
   h.mu_off = tm3 ? k_mumimo_off[mcs0][(Qm1 >> 1) - 1] : 0;
   h.qm1 = tm3 ? Qm1 : 0u;
-  h.tm56 = tm56 ? 1u : 0u;
-  h.lvl_inc = tm56 && tm56->dl_power_off == 1 ? 1u : 0u;
+  h.lvl_inc = tm56 && mp.dl_power_off == 1 ? 1u : 0u;
   /* estimate rows from the 5 pilot rows (P0 .. P3 = symbols 0, p1, p2, p3; P4 = the next subframe's
-   * symbol 0): lte_dl_channel_estimation.c:639-698 as k_chest's ce_interp applies it */
+   * symbol 0): lte_dl_channel_estimation.c:639-698 as k_chest's ce_interp applies it; row l is P[a] alone
+   * (wa 0) or P[a] wa + P[a + 1] wb */
   {
     const uint32_t p1 = fp->Ncp ? 3 : 4, p2 = fp->Ncp ? 6 : 7, p3 = fp->Ncp ? 9 : 11;
-    auto row = [&](uint32_t l, uint8_t a, int16_t wa, uint8_t b, int16_t wb) {
-      h.ea[l] = a; h.ewa[l] = wa; h.eb[l] = b; h.ewb[l] = wb;
-    };
-    row(0, 0, 0, 0, 0); row(p1, 1, 0, 0, 0); row(p2, 2, 0, 0, 0); row(p3, 3, 0, 0, 0);
-    row(p3 + 1, 3, 21845, 4, 10923); row(p3 + 2, 3, 10923, 4, 21845);
-    row(p1 + 1, 1, 21845, 2, 10923); row(p1 + 2, 1, 10923, 2, 21845);
+    auto row = [&](uint32_t l, uint8_t a, int16_t wa, int16_t wb) { h.ea[l] = a; h.ewa[l] = wa; h.ewb[l] = wb; };
+    row(0, 0, 0, 0); row(p1, 1, 0, 0); row(p2, 2, 0, 0); row(p3, 3, 0, 0);
+    row(p3 + 1, 3, 21845, 10923); row(p3 + 2, 3, 10923, 21845);
+    row(p1 + 1, 1, 21845, 10923); row(p1 + 2, 1, 10923, 21845);
     if (fp->Ncp == 0) {
-      row(1, 0, 24576, 1, 8192); row(2, 0, 16384, 1, 16384); row(3, 0, 8192, 1, 24576);
-      row(p2 + 1, 2, 24576, 3, 8192); row(p2 + 2, 2, 16384, 3, 16384); row(p2 + 3, 2, 8192, 3, 24576);
+      row(1, 0, 24576, 8192); row(2, 0, 16384, 16384); row(3, 0, 8192, 24576);
+      row(p2 + 1, 2, 24576, 8192); row(p2 + 2, 2, 16384, 16384); row(p2 + 3, 2, 8192, 24576);
     } else {                                                 /* the reference's 1/3, 2/3 order, as written */
-      row(1, 0, 10923, 1, 21845); row(2, 0, 21845, 1, 10923);
-      row(p2 + 1, 2, 10923, 3, 21845); row(p2 + 2, 2, 21845, 3, 10923);
+      row(1, 0, 10923, 21845); row(2, 0, 21845, 10923);
+      row(p2 + 1, 2, 10923, 21845); row(p2 + 2, 2, 21845, 10923);
     }
   }
   std::vector<uint32_t> map;
@@ -4130,13 +4129,12 @@ static oai4g_rx_config_t *rx_config_build(const oai4g_frame_parms_t *fp, const u
         const uint32_t nre = pil ? 8 : 12;
         for (size_t j = h.map_off[sf][k]; j < map.size(); j++) {
           const size_t rb = (j - h.map_off[sf][k]) / nre;
-          if (rb < prbs.size()) map[j] |= rx_pmi_of(fp, *tm56, prbs[rb]) << 30;
+          if (rb < prbs.size()) map[j] |= rx_pmi_of(fp, mp, prbs[rb]) << 30;
         }
       } else if (dual)
         rx_extract_map_dual(fp, rb_alloc, sf, l, map, nb_rb, n);
       else
         rx_extract_map(fp, rb_alloc, sf, l, map, nb_rb, n);
-      h.n_ext[sf][k] = n;
       const int adj = Qm == 2 ? 0 : rx_adjust_G2(fp, rb_alloc, sf, l);
       /* dlsch_*_llr: pilot symbols carry 10 (one port) or 8 (two ports, mode1_flag 0) REs per RB */
       const int len = pil ? (dual ? (int)nb_rb * 8 - 2 * adj / 3 : (int)nb_rb * 10 - 5 * adj / 6) : (int)nb_rb * 12 - adj;
@@ -4207,7 +4205,9 @@ extern "C" oai4g_rx_config_t *oai4g_rx_config_create(const oai4g_frame_parms_t *
                                                      uint8_t num_pdcch_symbols, uint16_t rnti, uint8_t first_subframe,
                                                      uint8_t subframe_step)
 {
-  return rx_config_build(fp, rb_alloc, Qm, num_pdcch_symbols, rnti, first_subframe, subframe_step, 0, 0, 0, 1);
+  rx_parms_t mp = {};
+  mp.nb_rx = 1;
+  return rx_config_build(fp, rb_alloc, Qm, num_pdcch_symbols, rnti, first_subframe, subframe_step, RX_SISO, mp);
 }
 
 extern "C" oai4g_rx_config_t *oai4g_rx_config_create_tm3(const oai4g_frame_parms_t *fp, const uint32_t rb_alloc[4],
@@ -4215,14 +4215,18 @@ extern "C" oai4g_rx_config_t *oai4g_rx_config_create_tm3(const oai4g_frame_parms
                                                          uint8_t num_pdcch_symbols, uint16_t rnti,
                                                          uint8_t first_subframe, uint8_t subframe_step, uint8_t nb_rx)
 {
-  return rx_config_build(fp, rb_alloc, Qm0, num_pdcch_symbols, rnti, first_subframe, subframe_step, 1, Qm1, mcs0, nb_rx);
+  rx_parms_t mp = {};
+  mp.nb_rx = nb_rx; mp.Qm1 = Qm1; mp.mcs0 = mcs0;
+  return rx_config_build(fp, rb_alloc, Qm0, num_pdcch_symbols, rnti, first_subframe, subframe_step, RX_TM3, mp);
 }
 
 extern "C" oai4g_rx_config_t *oai4g_rx_config_create_tm2(const oai4g_frame_parms_t *fp, const uint32_t rb_alloc[4],
                                                          uint8_t Qm, uint8_t num_pdcch_symbols, uint16_t rnti,
                                                          uint8_t first_subframe, uint8_t subframe_step, uint8_t nb_rx)
 {
-  return rx_config_build(fp, rb_alloc, Qm, num_pdcch_symbols, rnti, first_subframe, subframe_step, 0, 0, 0, nb_rx, 1);
+  rx_parms_t mp = {};
+  mp.nb_rx = nb_rx;
+  return rx_config_build(fp, rb_alloc, Qm, num_pdcch_symbols, rnti, first_subframe, subframe_step, RX_TM2, mp);
 }
 
 extern "C" oai4g_rx_config_t *oai4g_rx_config_create_tm56(const oai4g_frame_parms_t *fp, const uint32_t rb_alloc[4],
@@ -4231,8 +4235,9 @@ extern "C" oai4g_rx_config_t *oai4g_rx_config_create_tm56(const oai4g_frame_parm
                                                           uint8_t num_pdcch_symbols, uint16_t rnti,
                                                           uint8_t first_subframe, uint8_t subframe_step, uint8_t nb_rx)
 {
-  const rx_tm56_t t = {mimo_mode, pmi_alloc, pmi_rule, dl_power_off};
-  return rx_config_build(fp, rb_alloc, Qm, num_pdcch_symbols, rnti, first_subframe, subframe_step, 0, 0, 0, nb_rx, 0, &t);
+  rx_parms_t mp = {};
+  mp.nb_rx = nb_rx; mp.mimo_mode = mimo_mode; mp.pmi_alloc = pmi_alloc; mp.pmi_rule = pmi_rule; mp.dl_power_off = dl_power_off;
+  return rx_config_build(fp, rb_alloc, Qm, num_pdcch_symbols, rnti, first_subframe, subframe_step, RX_TM56, mp);
 }
 
 extern "C" void oai4g_rx_config_destroy(oai4g_rx_config_t *cfg)
@@ -4267,154 +4272,100 @@ static int rx_check_batch(const oai4g_rx_config_t *cfg, int n_sf)
   return 0;
 }
 
+/* The opening of every batch entry point: the library is up, cfg is a configuration of `mode` (else
+ * `refusal` is the error; `not_2cw`, when given, likewise unless both codewords are QPSK), the batch runs
+ * no bad subframe index, d_shift holds n_sf entries.  -1 refused, 0 nothing to do, 1 launch. */
+static int rx_prepare(oai4g_rx_config_t *cfg, int n_sf, rx_mode_t mode, const char *refusal, const char *not_2cw = nullptr)
+{
+  NEED_INIT(-1);
+  if (!cfg || cfg->mode != mode) { set_err("%s", refusal); return -1; }
+  if (not_2cw && (cfg->h.Qm != 2 || cfg->h.qm1 != 2)) { set_err("%s", not_2cw); return -1; }
+  if (n_sf <= 0) return 0;
+  if (rx_check_batch(cfg, n_sf) != 0) return -1;
+  if (n_sf > cfg->shift_cap) {
+    if (cfg->d_shift) hipFree(cfg->d_shift);
+    HCK(hipMalloc(&cfg->d_shift, (size_t)n_sf), -1);
+    cfg->shift_cap = n_sf;
+  }
+  return 1;
+}
+
+/* words per (port, antenna) plane of d_est: [n_sf][nsymb][N] estimates, or (pil) the 4 pilot-row pairs
+ * per subframe that oai4g_chest_batch_pilots wrote */
+static size_t rx_plane(const oai4g_rx_config_t *cfg, int n_sf, int pil)
+{
+  return pil ? (size_t)n_sf * 4 * cfg->h.N * 2 : (size_t)n_sf * cfg->h.nsymb * cfg->h.N;
+}
+
+/* d_est: TM1's estimate grid, else the planes [p * 2 + a][n_sf][nsymb][N], or (pil; TM3 and TM4-6) the
+ * pilot rows [p * 2 + a][n_sf][5][N]: the demodulator forms every other row with the estimator's temporal
+ * interpolation, so the 14-row planes never reach HBM and the LLRs are bit-identical */
+static int rx_batch(oai4g_rx_config_t *cfg, int n_sf, rx_mode_t mode, const char *refusal, const char *not_2cw,
+                    const int32_t *d_rxdataF, const int32_t *d_est, int pil, int16_t *d_llr0, int16_t *d_llr1,
+                    int unscramble, void *stream)
+{
+  const int go = rx_prepare(cfg, n_sf, mode, refusal, not_2cw);
+  if (go <= 0) return go;
+  HCK(oai4g_launch_rx(mode, cfg->d, &cfg->h, n_sf, d_rxdataF, d_est, rx_plane(cfg, n_sf, pil), d_llr0, d_llr1,
+                      cfg->d_shift, unscramble, (hipStream_t)stream, pil), -1);
+  return 0;
+}
+
 extern "C" int oai4g_rx_batch(oai4g_rx_config_t *cfg, int n_sf, const int32_t *d_rxdataF, const int32_t *d_ch,
                               int16_t *d_llr, int unscramble, void *stream)
 {
-  NEED_INIT(-1);
-  if (n_sf <= 0) return 0;
-  if (rx_check_batch(cfg, n_sf) != 0) return -1;
-  if (n_sf > cfg->shift_cap) {
-    if (cfg->d_shift) hipFree(cfg->d_shift);
-    HCK(hipMalloc(&cfg->d_shift, (size_t)n_sf), -1);
-    cfg->shift_cap = n_sf;
-  }
-  HCK(oai4g_launch_rx(cfg->d, &cfg->h, n_sf, d_rxdataF, d_ch, d_llr, cfg->d_shift, unscramble, (hipStream_t)stream), -1);
-  return 0;
+  return rx_batch(cfg, n_sf, RX_SISO, "rx_batch: not a TM1 configuration (oai4g_rx_config_create)", nullptr, d_rxdataF, d_ch,
+                  0, d_llr, nullptr, unscramble, stream);
 }
 
-/* rx_pdsch over the PDSCH symbols of one subframe (dlsim.c:3188-3260) on host buffers:
- * rxdataF / dl_ch_estimates = [nsymb][N] of the subframe; writes the LLR stream (not unscrambled)
- * and log2_maxh; returns the stream length or -1. */
+/* codeword 0 QPSK takes the interference-aware qpsk_qpsk / qpsk_16qam / qpsk_64qam LLRs */
 extern "C" int oai4g_rx_batch_tm3(oai4g_rx_config_t *cfg, int n_sf, const int32_t *d_rxdataF, const int32_t *d_est,
                                   int16_t *d_llr, int unscramble, void *stream)
 {
-  NEED_INIT(-1);
-  if (!cfg || !cfg->h.tm3) { set_err("rx_batch_tm3: not a TM3 configuration (oai4g_rx_config_create_tm3)"); return -1; }
-  if (n_sf <= 0) return 0;
-  if (rx_check_batch(cfg, n_sf) != 0) return -1;
-  if (n_sf > cfg->shift_cap) {
-    if (cfg->d_shift) hipFree(cfg->d_shift);
-    HCK(hipMalloc(&cfg->d_shift, (size_t)n_sf), -1);
-    cfg->shift_cap = n_sf;
-  }
-  const size_t plane = (size_t)n_sf * cfg->h.nsymb * cfg->h.N;
-  if (cfg->h.Qm == 2)   /* codeword 0 QPSK: the interference-aware qpsk_qpsk / qpsk_16qam / qpsk_64qam LLRs */
-    HCK(oai4g_launch_rx_tm3qq(cfg->d, &cfg->h, n_sf, d_rxdataF, d_est, plane, d_llr, nullptr, cfg->d_shift, unscramble,
-                              (hipStream_t)stream), -1);
-  else
-    HCK(oai4g_launch_rx_tm3(cfg->d, &cfg->h, n_sf, d_rxdataF, d_est, plane, d_llr, cfg->d_shift, unscramble,
-                            (hipStream_t)stream), -1);
-  return 0;
+  return rx_batch(cfg, n_sf, RX_TM3, "rx_batch_tm3: not a TM3 configuration (oai4g_rx_config_create_tm3)", nullptr,
+                  d_rxdataF, d_est, 0, d_llr, nullptr, unscramble, stream);
 }
 
-/* The TM3 batch from the pilot rows only: oai4g_chest_batch_pilots wrote [p * 2 + a][n_sf][5][N]
- * (the 5 frequency-interpolated pilot rows per subframe); the demodulator forms every other row
- * with the estimator's temporal interpolation, so the 14-row estimate planes never reach HBM.
- * LLRs bit-identical to oai4g_chest_batch x 4 + oai4g_rx_batch_tm3 / _tm3_2cw. */
-static int rx_batch_tm3_pil(oai4g_rx_config_t *cfg, int n_sf, const int32_t *d_rxdataF, const int32_t *d_pil,
-                            int16_t *d_llr0, int16_t *d_llr1, int unscramble, void *stream, bool two_cw)
-{
-  NEED_INIT(-1);
-  if (!cfg || !cfg->h.tm3) { set_err("rx_batch_tm3_pilots: not a TM3 configuration"); return -1; }
-  if (two_cw && (cfg->h.Qm != 2 || cfg->h.qm1 != 2)) {
-    set_err("rx_batch_tm3_2cw_pilots: not a TM3 configuration with both codewords QPSK");
-    return -1;
-  }
-  if (n_sf <= 0) return 0;
-  if (rx_check_batch(cfg, n_sf) != 0) return -1;
-  if (n_sf > cfg->shift_cap) {
-    if (cfg->d_shift) hipFree(cfg->d_shift);
-    HCK(hipMalloc(&cfg->d_shift, (size_t)n_sf), -1);
-    cfg->shift_cap = n_sf;
-  }
-  const size_t plane = (size_t)n_sf * 4 * cfg->h.N * 2;        /* words: 4 pilot-row pairs per subframe */
-  if (cfg->h.Qm == 2)
-    HCK(oai4g_launch_rx_tm3qq(cfg->d, &cfg->h, n_sf, d_rxdataF, d_pil, plane, d_llr0, two_cw ? d_llr1 : nullptr,
-                              cfg->d_shift, unscramble, (hipStream_t)stream, 1), -1);
-  else
-    HCK(oai4g_launch_rx_tm3(cfg->d, &cfg->h, n_sf, d_rxdataF, d_pil, plane, d_llr0, cfg->d_shift, unscramble,
-                            (hipStream_t)stream, 1), -1);
-  return 0;
-}
 extern "C" int oai4g_rx_batch_tm3_pilots(oai4g_rx_config_t *cfg, int n_sf, const int32_t *d_rxdataF, const int32_t *d_pil,
                                          int16_t *d_llr, int unscramble, void *stream)
 {
-  return rx_batch_tm3_pil(cfg, n_sf, d_rxdataF, d_pil, d_llr, nullptr, unscramble, stream, false);
+  return rx_batch(cfg, n_sf, RX_TM3, "rx_batch_tm3_pilots: not a TM3 configuration", nullptr, d_rxdataF, d_pil, 1, d_llr,
+                  nullptr, unscramble, stream);
 }
+
 extern "C" int oai4g_rx_batch_tm3_2cw_pilots(oai4g_rx_config_t *cfg, int n_sf, const int32_t *d_rxdataF,
                                              const int32_t *d_pil, int16_t *d_llr0, int16_t *d_llr1, int unscramble,
                                              void *stream)
 {
-  return rx_batch_tm3_pil(cfg, n_sf, d_rxdataF, d_pil, d_llr0, d_llr1, unscramble, stream, true);
+  return rx_batch(cfg, n_sf, RX_TM3, "rx_batch_tm3_pilots: not a TM3 configuration",
+                  "rx_batch_tm3_2cw_pilots: not a TM3 configuration with both codewords QPSK", d_rxdataF, d_pil, 1, d_llr0,
+                  d_llr1, unscramble, stream);
 }
 
 extern "C" int oai4g_rx_batch_tm3_2cw(oai4g_rx_config_t *cfg, int n_sf, const int32_t *d_rxdataF, const int32_t *d_est,
                                       int16_t *d_llr0, int16_t *d_llr1, int unscramble, void *stream)
 {
-  NEED_INIT(-1);
-  if (!cfg || !cfg->h.tm3 || cfg->h.Qm != 2 || cfg->h.qm1 != 2) {
-    set_err("rx_batch_tm3_2cw: not a TM3 configuration with both codewords QPSK");
-    return -1;
-  }
-  if (n_sf <= 0) return 0;
-  if (rx_check_batch(cfg, n_sf) != 0) return -1;
-  if (n_sf > cfg->shift_cap) {
-    if (cfg->d_shift) hipFree(cfg->d_shift);
-    HCK(hipMalloc(&cfg->d_shift, (size_t)n_sf), -1);
-    cfg->shift_cap = n_sf;
-  }
-  const size_t plane = (size_t)n_sf * cfg->h.nsymb * cfg->h.N;
-  HCK(oai4g_launch_rx_tm3qq(cfg->d, &cfg->h, n_sf, d_rxdataF, d_est, plane, d_llr0, d_llr1, cfg->d_shift, unscramble,
-                            (hipStream_t)stream), -1);
-  return 0;
+  const char *refusal = "rx_batch_tm3_2cw: not a TM3 configuration with both codewords QPSK";
+  return rx_batch(cfg, n_sf, RX_TM3, refusal, refusal, d_rxdataF, d_est, 0, d_llr0, d_llr1, unscramble, stream);
 }
 
 extern "C" int oai4g_rx_batch_tm2(oai4g_rx_config_t *cfg, int n_sf, const int32_t *d_rxdataF, const int32_t *d_est,
                                   int16_t *d_llr, int unscramble, void *stream)
 {
-  NEED_INIT(-1);
-  if (!cfg || !cfg->h.tm2) { set_err("rx_batch_tm2: not a TM2 configuration (oai4g_rx_config_create_tm2)"); return -1; }
-  if (n_sf <= 0) return 0;
-  if (rx_check_batch(cfg, n_sf) != 0) return -1;
-  if (n_sf > cfg->shift_cap) {
-    if (cfg->d_shift) hipFree(cfg->d_shift);
-    HCK(hipMalloc(&cfg->d_shift, (size_t)n_sf), -1);
-    cfg->shift_cap = n_sf;
-  }
-  const size_t plane = (size_t)n_sf * cfg->h.nsymb * cfg->h.N;
-  HCK(oai4g_launch_rx_tm2(cfg->d, &cfg->h, n_sf, d_rxdataF, d_est, plane, d_llr, cfg->d_shift, unscramble,
-                          (hipStream_t)stream), -1);
-  return 0;
+  return rx_batch(cfg, n_sf, RX_TM2, "rx_batch_tm2: not a TM2 configuration (oai4g_rx_config_create_tm2)", nullptr,
+                  d_rxdataF, d_est, 0, d_llr, nullptr, unscramble, stream);
 }
 
-/* TM4-6 single-layer precoding from the estimate planes [p * 2 + a][n_sf][nsymb][N], or (pil) from the
- * pilot-row pairs oai4g_chest_batch_pilots wrote, as oai4g_rx_batch_tm3_pilots takes them */
-static int rx_batch_tm56(oai4g_rx_config_t *cfg, int n_sf, const int32_t *d_rxdataF, const int32_t *d_est,
-                         int16_t *d_llr, int unscramble, void *stream, int pil)
-{
-  NEED_INIT(-1);
-  if (!cfg || !cfg->h.tm56) { set_err("rx_batch_tm56: not a TM4-6 configuration (oai4g_rx_config_create_tm56)"); return -1; }
-  if (n_sf <= 0) return 0;
-  if (rx_check_batch(cfg, n_sf) != 0) return -1;
-  if (n_sf > cfg->shift_cap) {
-    if (cfg->d_shift) hipFree(cfg->d_shift);
-    HCK(hipMalloc(&cfg->d_shift, (size_t)n_sf), -1);
-    cfg->shift_cap = n_sf;
-  }
-  const size_t plane = pil ? (size_t)n_sf * 4 * cfg->h.N * 2 : (size_t)n_sf * cfg->h.nsymb * cfg->h.N;
-  HCK(oai4g_launch_rx_tm56(cfg->d, &cfg->h, n_sf, d_rxdataF, d_est, plane, d_llr, cfg->d_shift, unscramble,
-                           (hipStream_t)stream, pil), -1);
-  return 0;
-}
+static const char k_not_tm56[] = "rx_batch_tm56: not a TM4-6 configuration (oai4g_rx_config_create_tm56)";
 extern "C" int oai4g_rx_batch_tm56(oai4g_rx_config_t *cfg, int n_sf, const int32_t *d_rxdataF, const int32_t *d_est,
                                    int16_t *d_llr, int unscramble, void *stream)
 {
-  return rx_batch_tm56(cfg, n_sf, d_rxdataF, d_est, d_llr, unscramble, stream, 0);
+  return rx_batch(cfg, n_sf, RX_TM56, k_not_tm56, nullptr, d_rxdataF, d_est, 0, d_llr, nullptr, unscramble, stream);
 }
 extern "C" int oai4g_rx_batch_tm56_pilots(oai4g_rx_config_t *cfg, int n_sf, const int32_t *d_rxdataF,
                                           const int32_t *d_pil, int16_t *d_llr, int unscramble, void *stream)
 {
-  return rx_batch_tm56(cfg, n_sf, d_rxdataF, d_pil, d_llr, unscramble, stream, 1);
+  return rx_batch(cfg, n_sf, RX_TM56, k_not_tm56, nullptr, d_rxdataF, d_pil, 1, d_llr, nullptr, unscramble, stream);
 }
 
 /* The rx_pdsch drop-ins' configurations, cached per calling thread (the UE calls rx_pdsch once per
@@ -4427,9 +4378,8 @@ namespace {
 struct rx_key_t {
   oai4g_frame_parms_t fp;
   uint32_t rb_alloc[4];
-  uint8_t Qm, Qm1, mcs0, npdcch, subframe, tm3, nb_rx, pad;
-  uint16_t pmi_alloc;             /* tm3 == 3 (TM4-6): the precoder word, mode and dl_power_off */
-  uint8_t mimo_mode, dl_power_off;
+  rx_parms_t mp;
+  uint8_t Qm, npdcch, subframe, mode;
 };
 struct rx_cache_t {
   rx_key_t key[32];
@@ -4438,26 +4388,21 @@ struct rx_cache_t {
 };
 thread_local rx_cache_t t_rx_cache;
 
-oai4g_rx_config_t *rx_cached(const oai4g_frame_parms_t *fp, const uint32_t rb_alloc[4], uint8_t Qm, uint8_t Qm1,
-                             uint8_t mcs0, uint8_t npdcch, uint8_t subframe, int tm3, int nb_rx, uint8_t mimo_mode = 0,
-                             uint16_t pmi_alloc = 0, uint8_t dl_power_off = 0)
+oai4g_rx_config_t *rx_cached(const oai4g_frame_parms_t *fp, const uint32_t rb_alloc[4], uint8_t Qm, uint8_t npdcch,
+                             uint8_t subframe, rx_mode_t mode, int nb_rx, uint8_t Qm1 = 0, uint8_t mcs0 = 0,
+                             uint8_t mimo_mode = 0, uint16_t pmi_alloc = 0, uint8_t dl_power_off = 0)
 {
   rx_key_t k;
   memset(&k, 0, sizeof(k));
   k.fp = *fp;
   memcpy(k.rb_alloc, rb_alloc, sizeof(k.rb_alloc));
-  k.Qm = Qm; k.Qm1 = Qm1; k.mcs0 = mcs0; k.npdcch = npdcch; k.subframe = subframe;
-  k.tm3 = (uint8_t)tm3; k.nb_rx = (uint8_t)nb_rx;
-  k.pmi_alloc = pmi_alloc; k.mimo_mode = mimo_mode; k.dl_power_off = dl_power_off;
+  k.Qm = Qm; k.npdcch = npdcch; k.subframe = subframe; k.mode = (uint8_t)mode;
+  k.mp.nb_rx = (uint8_t)nb_rx; k.mp.Qm1 = Qm1; k.mp.mcs0 = mcs0;
+  k.mp.pmi_rule = OAI4G_RX_PMI_UE; k.mp.pmi_alloc = pmi_alloc; k.mp.mimo_mode = mimo_mode; k.mp.dl_power_off = dl_power_off;
   rx_cache_t &c = t_rx_cache;
   for (int i = 0; i < 32; i++)
     if (c.cfg[i] && memcmp(&c.key[i], &k, sizeof(k)) == 0) return c.cfg[i];
-  oai4g_rx_config_t *cfg = tm3 == 3 ? oai4g_rx_config_create_tm56(fp, rb_alloc, Qm, mimo_mode, pmi_alloc, OAI4G_RX_PMI_UE,
-                                                                  dl_power_off, npdcch, 0, subframe, 1, (uint8_t)nb_rx)
-                          : tm3 == 2 ? oai4g_rx_config_create_tm2(fp, rb_alloc, Qm, npdcch, 0, subframe, 1, (uint8_t)nb_rx)
-                          : tm3 ? oai4g_rx_config_create_tm3(fp, rb_alloc, Qm, Qm1, mcs0, npdcch, 0, subframe, 1,
-                                                             (uint8_t)nb_rx)
-                                : oai4g_rx_config_create(fp, rb_alloc, Qm, npdcch, 0, subframe, 1);
+  oai4g_rx_config_t *cfg = rx_config_build(fp, rb_alloc, Qm, npdcch, 0, subframe, 1, mode, k.mp);
   if (!cfg) return nullptr;
   const int slot = c.next;
   c.next = (c.next + 1) % 32;
@@ -4469,6 +4414,36 @@ oai4g_rx_config_t *rx_cached(const oai4g_frame_parms_t *fp, const uint32_t rb_al
   c.key[slot] = k;
   return cfg;
 }
+
+/* rx_pdsch over the PDSCH symbols of one subframe (dlsim.c:3188-3260) on host buffers, the body of every
+ * drop-in: rxdataF[a] and est[p * 2 + a] = [nsymb][N] of the subframe (n_planes 1: TM1's one estimate, 4:
+ * ports 0 / 1 per antenna) go up, batch(dy, de, dl0, dl1) runs on g_scr.s, the n_out LLR streams (not
+ * unscrambled) and log2_maxh come back; returns the stream length or -1 */
+template <class Batch>
+int rx_pdsch_run(oai4g_rx_config_t *cfg, const char *who, uint8_t subframe, int nb_rx, const int32_t *const *rxdataF,
+                 int n_planes, const int32_t *const *est, int n_out, int16_t *const *llr, uint8_t *log2_maxh, Batch batch)
+{
+  if (!cfg) return -1;
+  if (rx_check_batch(cfg, 1) != 0) return -1;
+  const size_t gb = (size_t)cfg->h.nsymb * cfg->h.N * 4, gs = (gb + 255) & ~(size_t)255, ny = n_planes == 1 ? 1 : 2;
+  const int n = (int)cfg->llr_count[subframe % 10];
+  uint8_t *buf = scratch((ny + n_planes) * gs + (size_t)cfg->h.llr_stride * 2 * n_out + 256);
+  if (!buf) return -1;
+  uint8_t *dy = buf, *de = buf + ny * gs;                         /* [nb_rx][grid], planes [p * 2 + a] */
+  int16_t *dl = (int16_t *)(buf + (ny + n_planes) * gs);
+  bool ok = true;
+  for (int a = 0; a < nb_rx && ok; a++) ok = hipMemcpyAsync(dy + a * gb, rxdataF[a], gb, hipMemcpyHostToDevice, g_scr.s) == hipSuccess;
+  for (int pa = 0; pa < n_planes && ok; pa++)
+    if ((pa & 1) < nb_rx) ok = hipMemcpyAsync(de + pa * gb, est[pa], gb, hipMemcpyHostToDevice, g_scr.s) == hipSuccess;
+  ok = ok && batch((const int32_t *)dy, (const int32_t *)de, dl, dl + cfg->h.llr_stride) == 0;
+  for (int i = 0; i < n_out && ok; i++)
+    ok = hipMemcpyAsync(llr[i], dl + i * cfg->h.llr_stride, (size_t)n * 2, hipMemcpyDeviceToHost, g_scr.s) == hipSuccess;
+  if (ok && (!log2_maxh || hipMemcpyAsync(log2_maxh, cfg->d_shift, 1, hipMemcpyDeviceToHost, g_scr.s) == hipSuccess) &&
+      hipStreamSynchronize(g_scr.s) == hipSuccess)
+    return n;
+  set_err("%s: HIP error", who);
+  return -1;
+}
 }  // namespace
 
 extern "C" int oai4g_rx_pdsch_tm3(const oai4g_frame_parms_t *fp, int nb_rx, const int32_t *const *rxdataF,
@@ -4477,29 +4452,11 @@ extern "C" int oai4g_rx_pdsch_tm3(const oai4g_frame_parms_t *fp, int nb_rx, cons
                                   uint8_t *log2_maxh)
 {
   NEED_INIT(-1);
-  oai4g_rx_config_t *cfg = rx_cached(fp, rb_alloc, Qm0, Qm1, mcs0, num_pdcch_symbols, subframe, 1, nb_rx);
-  if (!cfg) return -1;
-  if (rx_check_batch(cfg, 1) != 0) return -1;
-  const size_t gb = (size_t)cfg->h.nsymb * cfg->h.N * 4, gs = (gb + 255) & ~(size_t)255;
-  const int n = (int)cfg->llr_count[subframe % 10];
-  uint8_t *buf = scratch(6 * gs + (size_t)cfg->h.llr_stride * 2 + 256);
-  if (!buf) return -1;
-  int32_t *dy = (int32_t *)buf, *de = (int32_t *)(buf + 2 * gs);   /* [nb_rx][grid], planes [p * 2 + a] */
-  int16_t *dl = (int16_t *)(buf + 6 * gs);
-  bool ok = true;
-  for (int a = 0; a < nb_rx && ok; a++) ok = hipMemcpyAsync((uint8_t *)dy + a * gb, rxdataF[a], gb, hipMemcpyHostToDevice, g_scr.s) == hipSuccess;
-  for (int pa = 0; pa < 4 && ok; pa++)
-    if ((pa & 1) < nb_rx)
-      ok = hipMemcpyAsync((uint8_t *)de + pa * gb, dl_ch_estimates[pa], gb, hipMemcpyHostToDevice, g_scr.s) == hipSuccess;
-  int rc = -1;
-  if (ok && oai4g_rx_batch_tm3(cfg, 1, dy, de, dl, 0, g_scr.s) == 0 &&
-      hipMemcpyAsync(llr, dl, (size_t)n * 2, hipMemcpyDeviceToHost, g_scr.s) == hipSuccess &&
-      (!log2_maxh || hipMemcpyAsync(log2_maxh, cfg->d_shift, 1, hipMemcpyDeviceToHost, g_scr.s) == hipSuccess) &&
-      hipStreamSynchronize(g_scr.s) == hipSuccess)
-    rc = n;
-  else
-    set_err("rx_pdsch_tm3: HIP error");
-  return rc;
+  oai4g_rx_config_t *cfg = rx_cached(fp, rb_alloc, Qm0, num_pdcch_symbols, subframe, RX_TM3, nb_rx, Qm1, mcs0);
+  return rx_pdsch_run(cfg, "rx_pdsch_tm3", subframe, nb_rx, rxdataF, 4, dl_ch_estimates, 1, &llr, log2_maxh,
+                      [&](const int32_t *dy, const int32_t *de, int16_t *dl, int16_t *) {
+                        return oai4g_rx_batch_tm3(cfg, 1, dy, de, dl, 0, g_scr.s);
+                      });
 }
 
 extern "C" int oai4g_rx_pdsch_tm3_2cw(const oai4g_frame_parms_t *fp, int nb_rx, const int32_t *const *rxdataF,
@@ -4508,30 +4465,12 @@ extern "C" int oai4g_rx_pdsch_tm3_2cw(const oai4g_frame_parms_t *fp, int nb_rx, 
                                       uint8_t *log2_maxh)
 {
   NEED_INIT(-1);
-  oai4g_rx_config_t *cfg = rx_cached(fp, rb_alloc, 2, 2, mcs0, num_pdcch_symbols, subframe, 1, nb_rx);
-  if (!cfg) return -1;
-  if (rx_check_batch(cfg, 1) != 0) return -1;
-  const size_t gb = (size_t)cfg->h.nsymb * cfg->h.N * 4, gs = (gb + 255) & ~(size_t)255;
-  const int n = (int)cfg->llr_count[subframe % 10];
-  uint8_t *buf = scratch(6 * gs + (size_t)cfg->h.llr_stride * 4 + 256);
-  if (!buf) return -1;
-  int32_t *dy = (int32_t *)buf, *de = (int32_t *)(buf + 2 * gs);   /* [nb_rx][grid], planes [p * 2 + a] */
-  int16_t *dl = (int16_t *)(buf + 6 * gs), *dl1 = dl + cfg->h.llr_stride;
-  bool ok = true;
-  for (int a = 0; a < nb_rx && ok; a++) ok = hipMemcpyAsync((uint8_t *)dy + a * gb, rxdataF[a], gb, hipMemcpyHostToDevice, g_scr.s) == hipSuccess;
-  for (int pa = 0; pa < 4 && ok; pa++)
-    if ((pa & 1) < nb_rx)
-      ok = hipMemcpyAsync((uint8_t *)de + pa * gb, dl_ch_estimates[pa], gb, hipMemcpyHostToDevice, g_scr.s) == hipSuccess;
-  int rc = -1;
-  if (ok && oai4g_rx_batch_tm3_2cw(cfg, 1, dy, de, dl, dl1, 0, g_scr.s) == 0 &&
-      hipMemcpyAsync(llr0, dl, (size_t)n * 2, hipMemcpyDeviceToHost, g_scr.s) == hipSuccess &&
-      hipMemcpyAsync(llr1, dl1, (size_t)n * 2, hipMemcpyDeviceToHost, g_scr.s) == hipSuccess &&
-      (!log2_maxh || hipMemcpyAsync(log2_maxh, cfg->d_shift, 1, hipMemcpyDeviceToHost, g_scr.s) == hipSuccess) &&
-      hipStreamSynchronize(g_scr.s) == hipSuccess)
-    rc = n;
-  else
-    set_err("rx_pdsch_tm3_2cw: HIP error");
-  return rc;
+  oai4g_rx_config_t *cfg = rx_cached(fp, rb_alloc, 2, num_pdcch_symbols, subframe, RX_TM3, nb_rx, 2, mcs0);
+  int16_t *const llr[2] = {llr0, llr1};
+  return rx_pdsch_run(cfg, "rx_pdsch_tm3_2cw", subframe, nb_rx, rxdataF, 4, dl_ch_estimates, 2, llr, log2_maxh,
+                      [&](const int32_t *dy, const int32_t *de, int16_t *dl, int16_t *dl1) {
+                        return oai4g_rx_batch_tm3_2cw(cfg, 1, dy, de, dl, dl1, 0, g_scr.s);
+                      });
 }
 
 extern "C" int oai4g_rx_pdsch_tm2(const oai4g_frame_parms_t *fp, int nb_rx, const int32_t *const *rxdataF,
@@ -4539,29 +4478,11 @@ extern "C" int oai4g_rx_pdsch_tm2(const oai4g_frame_parms_t *fp, int nb_rx, cons
                                   uint8_t num_pdcch_symbols, uint8_t subframe, int16_t *llr, uint8_t *log2_maxh)
 {
   NEED_INIT(-1);
-  oai4g_rx_config_t *cfg = rx_cached(fp, rb_alloc, Qm, 0, 0, num_pdcch_symbols, subframe, 2, nb_rx);
-  if (!cfg) return -1;
-  if (rx_check_batch(cfg, 1) != 0) return -1;
-  const size_t gb = (size_t)cfg->h.nsymb * cfg->h.N * 4, gs = (gb + 255) & ~(size_t)255;
-  const int n = (int)cfg->llr_count[subframe % 10];
-  uint8_t *buf = scratch(6 * gs + (size_t)cfg->h.llr_stride * 2 + 256);
-  if (!buf) return -1;
-  int32_t *dy = (int32_t *)buf, *de = (int32_t *)(buf + 2 * gs);   /* [nb_rx][grid], planes [p * 2 + a] */
-  int16_t *dl = (int16_t *)(buf + 6 * gs);
-  bool ok = true;
-  for (int a = 0; a < nb_rx && ok; a++) ok = hipMemcpyAsync((uint8_t *)dy + a * gb, rxdataF[a], gb, hipMemcpyHostToDevice, g_scr.s) == hipSuccess;
-  for (int pa = 0; pa < 4 && ok; pa++)
-    if ((pa & 1) < nb_rx)
-      ok = hipMemcpyAsync((uint8_t *)de + pa * gb, dl_ch_estimates[pa], gb, hipMemcpyHostToDevice, g_scr.s) == hipSuccess;
-  int rc = -1;
-  if (ok && oai4g_rx_batch_tm2(cfg, 1, dy, de, dl, 0, g_scr.s) == 0 &&
-      hipMemcpyAsync(llr, dl, (size_t)n * 2, hipMemcpyDeviceToHost, g_scr.s) == hipSuccess &&
-      (!log2_maxh || hipMemcpyAsync(log2_maxh, cfg->d_shift, 1, hipMemcpyDeviceToHost, g_scr.s) == hipSuccess) &&
-      hipStreamSynchronize(g_scr.s) == hipSuccess)
-    rc = n;
-  else
-    set_err("rx_pdsch_tm2: HIP error");
-  return rc;
+  oai4g_rx_config_t *cfg = rx_cached(fp, rb_alloc, Qm, num_pdcch_symbols, subframe, RX_TM2, nb_rx);
+  return rx_pdsch_run(cfg, "rx_pdsch_tm2", subframe, nb_rx, rxdataF, 4, dl_ch_estimates, 1, &llr, log2_maxh,
+                      [&](const int32_t *dy, const int32_t *de, int16_t *dl, int16_t *) {
+                        return oai4g_rx_batch_tm2(cfg, 1, dy, de, dl, 0, g_scr.s);
+                      });
 }
 
 /* rx_pdsch for the single-layer precoding modes 3..7 (dual_stream_flag 0), the reference UE's subband
@@ -4572,30 +4493,12 @@ extern "C" int oai4g_rx_pdsch_tm56(const oai4g_frame_parms_t *fp, int nb_rx, con
                                    uint8_t num_pdcch_symbols, uint8_t subframe, int16_t *llr, uint8_t *log2_maxh)
 {
   NEED_INIT(-1);
-  oai4g_rx_config_t *cfg = rx_cached(fp, rb_alloc, Qm, 0, 0, num_pdcch_symbols, subframe, 3, nb_rx, mimo_mode, pmi_alloc,
-                                     dl_power_off);
-  if (!cfg) return -1;
-  if (rx_check_batch(cfg, 1) != 0) return -1;
-  const size_t gb = (size_t)cfg->h.nsymb * cfg->h.N * 4, gs = (gb + 255) & ~(size_t)255;
-  const int n = (int)cfg->llr_count[subframe % 10];
-  uint8_t *buf = scratch(6 * gs + (size_t)cfg->h.llr_stride * 2 + 256);
-  if (!buf) return -1;
-  int32_t *dy = (int32_t *)buf, *de = (int32_t *)(buf + 2 * gs);   /* [nb_rx][grid], planes [p * 2 + a] */
-  int16_t *dl = (int16_t *)(buf + 6 * gs);
-  bool ok = true;
-  for (int a = 0; a < nb_rx && ok; a++) ok = hipMemcpyAsync((uint8_t *)dy + a * gb, rxdataF[a], gb, hipMemcpyHostToDevice, g_scr.s) == hipSuccess;
-  for (int pa = 0; pa < 4 && ok; pa++)
-    if ((pa & 1) < nb_rx)
-      ok = hipMemcpyAsync((uint8_t *)de + pa * gb, dl_ch_estimates[pa], gb, hipMemcpyHostToDevice, g_scr.s) == hipSuccess;
-  int rc = -1;
-  if (ok && oai4g_rx_batch_tm56(cfg, 1, dy, de, dl, 0, g_scr.s) == 0 &&
-      hipMemcpyAsync(llr, dl, (size_t)n * 2, hipMemcpyDeviceToHost, g_scr.s) == hipSuccess &&
-      (!log2_maxh || hipMemcpyAsync(log2_maxh, cfg->d_shift, 1, hipMemcpyDeviceToHost, g_scr.s) == hipSuccess) &&
-      hipStreamSynchronize(g_scr.s) == hipSuccess)
-    rc = n;
-  else
-    set_err("rx_pdsch_tm56: HIP error");
-  return rc;
+  oai4g_rx_config_t *cfg = rx_cached(fp, rb_alloc, Qm, num_pdcch_symbols, subframe, RX_TM56, nb_rx, 0, 0, mimo_mode,
+                                     pmi_alloc, dl_power_off);
+  return rx_pdsch_run(cfg, "rx_pdsch_tm56", subframe, nb_rx, rxdataF, 4, dl_ch_estimates, 1, &llr, log2_maxh,
+                      [&](const int32_t *dy, const int32_t *de, int16_t *dl, int16_t *) {
+                        return oai4g_rx_batch_tm56(cfg, 1, dy, de, dl, 0, g_scr.s);
+                      });
 }
 
 extern "C" int oai4g_rx_pdsch_siso(const oai4g_frame_parms_t *fp, const int32_t *rxdataF, const int32_t *dl_ch_estimates,
@@ -4603,26 +4506,11 @@ extern "C" int oai4g_rx_pdsch_siso(const oai4g_frame_parms_t *fp, const int32_t 
                                    int16_t *llr, uint8_t *log2_maxh)
 {
   NEED_INIT(-1);
-  oai4g_rx_config_t *cfg = rx_cached(fp, rb_alloc, Qm, 0, 0, num_pdcch_symbols, subframe, 0, 1);
-  if (!cfg) return -1;
-  if (rx_check_batch(cfg, 1) != 0) return -1;
-  const size_t gb = (size_t)cfg->h.nsymb * cfg->h.N * 4, gs = (gb + 255) & ~(size_t)255;
-  const int n = (int)cfg->llr_count[subframe % 10];
-  uint8_t *buf = scratch(2 * gs + (size_t)cfg->h.llr_stride * 2 + 256);
-  if (!buf) return -1;
-  int32_t *dy = (int32_t *)buf, *dh = (int32_t *)(buf + gs);
-  int16_t *dl = (int16_t *)(buf + 2 * gs);
-  int rc = -1;
-  if (hipMemcpyAsync(dy, rxdataF, gb, hipMemcpyHostToDevice, g_scr.s) == hipSuccess &&
-      hipMemcpyAsync(dh, dl_ch_estimates, gb, hipMemcpyHostToDevice, g_scr.s) == hipSuccess &&
-      oai4g_rx_batch(cfg, 1, dy, dh, dl, 0, g_scr.s) == 0 &&
-      hipMemcpyAsync(llr, dl, (size_t)n * 2, hipMemcpyDeviceToHost, g_scr.s) == hipSuccess &&
-      (!log2_maxh || hipMemcpyAsync(log2_maxh, cfg->d_shift, 1, hipMemcpyDeviceToHost, g_scr.s) == hipSuccess) &&
-      hipStreamSynchronize(g_scr.s) == hipSuccess)
-    rc = n;
-  else
-    set_err("rx_pdsch_siso: HIP error");
-  return rc;
+  oai4g_rx_config_t *cfg = rx_cached(fp, rb_alloc, Qm, num_pdcch_symbols, subframe, RX_SISO, 1);
+  return rx_pdsch_run(cfg, "rx_pdsch_siso", subframe, 1, &rxdataF, 1, &dl_ch_estimates, 1, &llr, log2_maxh,
+                      [&](const int32_t *dy, const int32_t *dh, int16_t *dl, int16_t *) {
+                        return oai4g_rx_batch(cfg, 1, dy, dh, dl, 0, g_scr.s);
+                      });
 }
 
 /* dlsch_unscrambling (dlsch_scrambling.c:99-137): llr[k] *= 2 c(k) - 1 for k < 32 (1 + G / 32),
@@ -4812,17 +4700,13 @@ extern "C" int oai4g_rx_batch_estimated(oai4g_rx_config_t *rx, oai4g_chest_confi
 {
   NEED_INIT(-1);
   if (!rx || !ce || n_sf < 0) { set_err("rx_batch_estimated: bad arguments"); return -1; }
-  if (rx_check_batch(rx, n_sf) != 0) return -1;
   if (rx->h.N != ce->h.N || rx->h.nsymb != ce->h.nsymb || rx->h.first_sf != ce->h.first_sf ||
       rx->h.sf_step != ce->h.sf_step || ce->h.p != 0 || ce->h.N_RB > 100) {
     set_err("rx_batch_estimated: the demodulation and estimation configurations differ (frame, subframes, port 0)");
     return -1;
   }
-  if (n_sf > rx->shift_cap) {
-    if (rx->d_shift) hipFree(rx->d_shift);
-    HCK(hipMalloc(&rx->d_shift, (size_t)n_sf), -1);
-    rx->shift_cap = n_sf;
-  }
+  const int go = rx_prepare(rx, n_sf, RX_SISO, "rx_batch_estimated: not a TM1 configuration (oai4g_rx_config_create)");
+  if (go <= 0) return go;
   HCK(oai4g_launch_rx_chest(ce->d, rx->d, &rx->h, n_sf, d_rxdataF, d_llr, rx->d_shift, unscramble,
                             (hipStream_t)stream), -1);
   return 0;

@@ -509,51 +509,39 @@ hipError_t oai4g_launch_chest_pilots(const chest_dev_t *d_cfg, const chest_dev_t
 hipError_t oai4g_launch_chest_symbol(const chest_dev_t *d_cfg, const chest_dev_t *h_cfg, const int32_t *d_rxF_sym,
                                      int32_t *d_est, int Ns, int l, int symbol, hipStream_t s);
 
+/* what a PDSCH receive configuration demodulates: TM1, TM2 (ALAMOUTI), TM3 (LARGE_CDD) or the
+ * single-layer precoding of TM4-6; all but the first use the dual extraction and nb_rx antennas */
+enum rx_mode_t { RX_SISO, RX_TM2, RX_TM3, RX_TM56 };
+
 struct rx_dev_t {
   uint32_t N, nsymb, Qm, npdcch;
   uint32_t llr_stride;            /* LLRs per batch element */
   uint32_t n_sym;                 /* PDSCH symbols per subframe (nsymb - npdcch) */
-  /* per subframe index and PDSCH symbol: extraction map offset, extracted REs, demodulated REs,
-   * LLR offset; level REs and divisor for the first symbol */
-  uint32_t map_off[10][14], n_ext[10][14], len[10][14], llr_off[10][14];
+  /* per subframe index and PDSCH symbol: extraction map offset, demodulated REs, LLR offset; level
+   * REs and divisor for the first symbol */
+  uint32_t map_off[10][14], len[10][14], llr_off[10][14];
   uint32_t lvl_n[10], lvl_div[10];
   uint32_t gold_words;            /* scrambling words per subframe index */
   uint32_t first_sf, sf_step;
   int16_t a1, a2;                 /* QAM_n1 / QAM_n2 of the channel magnitude (0 for QPSK) */
-  const uint32_t *map;            /* extracted RE j: FFT bin | (estimate index within the symbol) << 16 */
+  /* extracted RE j: FFT bin (< 2^11) | (estimate index within the symbol, < 2^11) << 16; a TM4-6
+   * configuration's own copy carries the RE's precoder in bits 30-31 */
+  const uint32_t *map;
   const uint32_t *gold;           /* [10][gold_words] */
-  /* TM3 (LARGE_CDD, dual extraction; rx_pdsch with dual_stream_flag = 0): receive antennas, the
-   * channel_level_TM3 RE count per RB of the first PDSCH symbol, offset_mumimo_llr_drange */
-  uint32_t tm3, nb_rx, lvl_nre;
-  int32_t mu_off;
-  /* TM2 (ALAMOUTI, dual extraction): dlsch_channel_level over both ports, dlsch_alamouti */
-  uint32_t tm2;
+  uint32_t nb_rx;                 /* receive antennas (1 for TM1) */
+  int32_t mu_off;                 /* TM3: offset_mumimo_llr_drange */
   uint32_t qm1;                   /* TM3: codeword 1's modulation order (Qm = 2 picks qpsk_qpsk / _qam16 / _qam64) */
+  uint32_t lvl_inc;               /* TM4-6: 1 when dl_power_off == 1 (log2_maxh++, dlsch_demodulation.c:289-292) */
   /* estimate row l from the 5 pilot rows (lte_dl_channel_estimation.c:639-698): pilot row ea[l]
-   * when ewa[l] == 0, else mulhi(P[ea], ewa) << 1 +sat mulhi(P[eb], ewb) << 1 */
-  uint8_t ea[14], eb[14];
+   * when ewa[l] == 0, else mulhi(P[ea], ewa) << 1 +sat mulhi(P[ea + 1], ewb) << 1 */
+  uint8_t ea[14];
   int16_t ewa[14], ewb[14];
-  /* TM4-6 (single-layer precoding, dual extraction; appended so the fields above keep their
-   * offsets): the map is the configuration's own copy with the RE's precoder in bits 30-31
-   * (FFT bin < 2^11 in bits 0-15, estimate column < 2^11 in bits 16-29); lvl_inc = 1 when
-   * dl_power_off == 1 (log2_maxh++, dlsch_demodulation.c:289-292) */
-  uint32_t tm56, lvl_inc;
 };
 hipError_t oai4g_launch_rx_chest(const chest_dev_t *d_ce, const rx_dev_t *d_rx, const rx_dev_t *h_rx, int n_sf,
                                  const int32_t *d_rxF, int16_t *d_llr, uint8_t *d_shift, int unscramble, hipStream_t s);
-hipError_t oai4g_launch_rx_tm3(const rx_dev_t *d_cfg, const rx_dev_t *h_cfg, int n_sf, const int32_t *d_rxF,
-                               const int32_t *d_est, size_t plane, int16_t *d_llr, uint8_t *d_shift, int unscramble,
-                               hipStream_t s, int pil = 0);
-/* TM3 with codeword 0 QPSK: Qm1 = 2 both codewords (d_llr1 may be null), Qm1 = 4 / 6 codeword 0 */
-hipError_t oai4g_launch_rx_tm3qq(const rx_dev_t *d_cfg, const rx_dev_t *h_cfg, int n_sf, const int32_t *d_rxF,
-                                 const int32_t *d_est, size_t plane, int16_t *d_llr0, int16_t *d_llr1,
-                                 uint8_t *d_shift, int unscramble, hipStream_t s, int pil = 0);
-hipError_t oai4g_launch_rx_tm2(const rx_dev_t *d_cfg, const rx_dev_t *h_cfg, int n_sf, const int32_t *d_rxF,
-                               const int32_t *d_est, size_t plane, int16_t *d_llr, uint8_t *d_shift, int unscramble,
-                               hipStream_t s);
-/* TM4-6 single-layer precoding (a configuration of oai4g_rx_config_create_tm56) */
-hipError_t oai4g_launch_rx_tm56(const rx_dev_t *d_cfg, const rx_dev_t *h_cfg, int n_sf, const int32_t *d_rxF,
-                                const int32_t *d_est, size_t plane, int16_t *d_llr, uint8_t *d_shift, int unscramble,
-                                hipStream_t s, int pil = 0);
-hipError_t oai4g_launch_rx(const rx_dev_t *d_cfg, const rx_dev_t *h_cfg, int n_sf, const int32_t *d_rxF,
-                           const int32_t *d_ch, int16_t *d_llr, uint8_t *d_shift, int unscramble, hipStream_t s);
+/* level + LLR kernels of one mode.  d_est: TM1's estimate grid [n_sf][nsymb][N], else the planes
+ * [p * 2 + a] of `plane` words, or (pil; TM3 and TM4-6) the pilot-row pairs.  d_llr1: codeword 1 of a
+ * TM3 configuration with both codewords QPSK, or null. */
+hipError_t oai4g_launch_rx(rx_mode_t mode, const rx_dev_t *d_cfg, const rx_dev_t *h_cfg, int n_sf, const int32_t *d_rxF,
+                           const int32_t *d_est, size_t plane, int16_t *d_llr, int16_t *d_llr1, uint8_t *d_shift,
+                           int unscramble, hipStream_t s, int pil);

@@ -153,11 +153,17 @@ __global__ void __launch_bounds__(256) k_rx_level_tm3(const rx_dev_t *__restrict
   }
 }
 
-template <int QM, bool PIL>
-__global__ void __launch_bounds__(256) k_rx_llr_tm3(const rx_dev_t *__restrict__ c, const int32_t *__restrict__ rxF,
-                                                    const int32_t *__restrict__ est, size_t plane,
-                                                    int16_t *__restrict__ llr, const uint8_t *__restrict__ shift,
-                                                    int unscramble)
+/* One thread per RE for the two modes that demodulate one precoded stream: MODE = RX_TM3 takes
+ * prec2A_TM3_128's stream 0 (s alternates per slot), RX_TM56 prec2A_TM56_128 with the RE's precoder from
+ * bits 30-31 of its map word (the estimate column is then masked).  TM3 is never instantiated with
+ * QM == 2: that is k_rx_llr_tm3qq. */
+constexpr uint32_t RX_COL_MASK = 0x3FFFu;                     /* estimate column of a TM4-6 map word >> 16 */
+
+template <int QM, bool PIL, rx_mode_t MODE>
+__global__ void __launch_bounds__(256) k_rx_llr_prec(const rx_dev_t *__restrict__ c, const int32_t *__restrict__ rxF,
+                                                     const int32_t *__restrict__ est, size_t plane,
+                                                     int16_t *__restrict__ llr, const uint8_t *__restrict__ shift,
+                                                     int unscramble)
 {
   const uint32_t sf = blockIdx.y, k = blockIdx.x, sfi = (c->first_sf + sf * c->sf_step) % 10;
   const uint32_t l = c->npdcch + k, len = c->len[sfi][k], nb_rx = c->nb_rx, NS = c->nsymb * c->N;
@@ -177,27 +183,27 @@ __global__ void __launch_bounds__(256) k_rx_llr_tm3(const rx_dev_t *__restrict__
   for (uint32_t a = 0; a < 2; a++)
 #pragma unroll
     for (int r = 0; r < RX_R; r++) {
-      const uint32_t aa = a < nb_rx ? a : 0u;
+      const uint32_t aa = a < nb_rx ? a : 0u, col = MODE == RX_TM56 ? (mw[r] >> 16) & RX_COL_MASK : mw[r] >> 16;
       const size_t yo = ((size_t)sf * nb_rx + aa) * NS + (size_t)l * c->N;
       yv[a][r] = (uint32_t)rxF[yo + (mw[r] & 0xFFFFu)];
-      h0[a][r] = rx_est<PIL>(c, est, plane, aa, sf, l, mw[r] >> 16);
-      h1[a][r] = rx_est<PIL>(c, est, plane, 2 + aa, sf, l, mw[r] >> 16);
+      h0[a][r] = rx_est<PIL>(c, est, plane, aa, sf, l, col);
+      h1[a][r] = rx_est<PIL>(c, est, plane, 2 + aa, sf, l, col);
     }
 #pragma unroll
   for (int r = 0; r < RX_R; r++) {
     const uint32_t j = threadIdx.x + 256 * r;
     if (j >= len) break;
-    int16_t cr[2], ci[2], mg[2], mgb[2];
+    int16_t cr[2], ci[2], mg[2] = {0, 0}, mgb[2] = {0, 0};
 #pragma unroll
     for (uint32_t a = 0; a < 2; a++) {
-      const uint32_t p = rx_prec_tm3(h0[a][r], h1[a][r], (j & 1u) != 0);
-      const int16_t hr = (int16_t)p, hi = (int16_t)(p >> 16), yr = (int16_t)yv[a][r], yi = (int16_t)(yv[a][r] >> 16);
-      const int16_t nhi = (int16_t)(-(int32_t)hi);
-      cr[a] = rx_sat16(rx_madd(hr, yr, hi, yi) >> sh);
-      ci[a] = rx_sat16(rx_madd(nhi, yr, hr, yi) >> sh);
-      const int16_t m = rx_sat16(rx_madd(hr, hr, hi, hi) >> sh);
-      mg[a] = (int16_t)((((int32_t)m * a1) >> 16) << 1);
-      mgb[a] = (int16_t)((((int32_t)m * a2) >> 16) << 1);
+      const uint32_t p = MODE == RX_TM56 ? rx_prec_tm56(h0[a][r], h1[a][r], mw[r] >> 30)
+                                         : rx_prec_tm3(h0[a][r], h1[a][r], (j & 1u) != 0);
+      rx_conj_mul(p, yv[a][r], sh, cr[a], ci[a]);
+      if (QM > 2) {
+        const int16_t m = rx_sat16((int32_t)rx_h2(p) >> sh);
+        mg[a] = (int16_t)((((int32_t)m * a1) >> 16) << 1);
+        mgb[a] = (int16_t)((((int32_t)m * a2) >> 16) << 1);
+      }
     }
     if (nb_rx > 1) {                                          /* dlsch_detection_mrc */
       cr[0] = rx_sat16((cr[0] >> 1) + (cr[1] >> 1));
@@ -269,54 +275,6 @@ __global__ void __launch_bounds__(256) k_rx_llr_tm3qq(const rx_dev_t *__restrict
   }
 }
 
-template <bool PIL>
-static hipError_t launch_rx_tm3qq(const rx_dev_t *d_cfg, const rx_dev_t *h_cfg, int n_sf, const int32_t *d_rxF,
-                                  const int32_t *d_est, size_t plane, int16_t *d_llr0, int16_t *d_llr1, uint8_t *d_shift,
-                                  int unscramble, hipStream_t s)
-{
-  hipLaunchKernelGGL(k_rx_level_tm3<PIL>, dim3(n_sf), dim3(256), 0, s, d_cfg, d_est, plane, d_shift);
-  const dim3 g(h_cfg->n_sym, n_sf), b(256);
-  if (h_cfg->qm1 == 4)
-    hipLaunchKernelGGL((k_rx_llr_tm3qq<4, PIL>), g, b, 0, s, d_cfg, d_rxF, d_est, plane, d_llr0, nullptr, d_shift, unscramble);
-  else if (h_cfg->qm1 == 6)
-    hipLaunchKernelGGL((k_rx_llr_tm3qq<6, PIL>), g, b, 0, s, d_cfg, d_rxF, d_est, plane, d_llr0, nullptr, d_shift, unscramble);
-  else
-    hipLaunchKernelGGL((k_rx_llr_tm3qq<2, PIL>), g, b, 0, s, d_cfg, d_rxF, d_est, plane, d_llr0, d_llr1, d_shift, unscramble);
-  return hipGetLastError();
-}
-
-hipError_t oai4g_launch_rx_tm3qq(const rx_dev_t *d_cfg, const rx_dev_t *h_cfg, int n_sf, const int32_t *d_rxF,
-                                 const int32_t *d_est, size_t plane, int16_t *d_llr0, int16_t *d_llr1,
-                                 uint8_t *d_shift, int unscramble, hipStream_t s, int pil)
-{
-  if (n_sf <= 0) return hipSuccess;
-  return pil ? launch_rx_tm3qq<true>(d_cfg, h_cfg, n_sf, d_rxF, d_est, plane, d_llr0, d_llr1, d_shift, unscramble, s)
-             : launch_rx_tm3qq<false>(d_cfg, h_cfg, n_sf, d_rxF, d_est, plane, d_llr0, d_llr1, d_shift, unscramble, s);
-}
-
-template <bool PIL>
-static hipError_t launch_rx_tm3(const rx_dev_t *d_cfg, const rx_dev_t *h_cfg, int n_sf, const int32_t *d_rxF,
-                                const int32_t *d_est, size_t plane, int16_t *d_llr, uint8_t *d_shift, int unscramble,
-                                hipStream_t s)
-{
-  hipLaunchKernelGGL(k_rx_level_tm3<PIL>, dim3(n_sf), dim3(256), 0, s, d_cfg, d_est, plane, d_shift);
-  const dim3 g(h_cfg->n_sym, n_sf), b(256);
-  if (h_cfg->Qm == 4)
-    hipLaunchKernelGGL((k_rx_llr_tm3<4, PIL>), g, b, 0, s, d_cfg, d_rxF, d_est, plane, d_llr, d_shift, unscramble);
-  else
-    hipLaunchKernelGGL((k_rx_llr_tm3<6, PIL>), g, b, 0, s, d_cfg, d_rxF, d_est, plane, d_llr, d_shift, unscramble);
-  return hipGetLastError();
-}
-
-hipError_t oai4g_launch_rx_tm3(const rx_dev_t *d_cfg, const rx_dev_t *h_cfg, int n_sf, const int32_t *d_rxF,
-                               const int32_t *d_est, size_t plane, int16_t *d_llr, uint8_t *d_shift, int unscramble,
-                               hipStream_t s, int pil)
-{
-  if (n_sf <= 0) return hipSuccess;
-  return pil ? launch_rx_tm3<true>(d_cfg, h_cfg, n_sf, d_rxF, d_est, plane, d_llr, d_shift, unscramble, s)
-             : launch_rx_tm3<false>(d_cfg, h_cfg, n_sf, d_rxF, d_est, plane, d_llr, d_shift, unscramble, s);
-}
-
 /* ======================================================================================
  * TM2 (ALAMOUTI, two TX ports) with dlsim's UE (rx_pdsch, dual_stream_flag = 0):
  *   dlsch_extract_rbs_dual      (the TM3 map)
@@ -329,21 +287,28 @@ hipError_t oai4g_launch_rx_tm3(const rx_dev_t *d_cfg, const rx_dev_t *h_cfg, int
  *   dlsch_qpsk / 16qam / 64qam_llr, unscrambled
  * One thread per RE pair; planes and layouts as for TM3.
  * ==================================================================================== */
-__global__ void __launch_bounds__(256) k_rx_level_tm2(const rx_dev_t *__restrict__ c, const int32_t *__restrict__ est,
-                                                      size_t plane, uint8_t *__restrict__ shift)
+/* The level of TM2 and, with PREC, of TM4-6: its map words carry the precoder above the estimate column,
+ * it reads through rx_est (planes or pilot rows) and adds lvl_inc.  TM2 has planes only and takes the
+ * symbol's row offset outside the loop, which the compiler does not do for rx_est: 44 instructions fewer
+ * for TM2, but two VGPRs more where TM4-6 does the same, so each keeps its spelling. */
+template <bool PIL, bool PREC>
+__global__ void __launch_bounds__(256) k_rx_level_dual(const rx_dev_t *__restrict__ c, const int32_t *__restrict__ est,
+                                                       size_t plane, uint8_t *__restrict__ shift)
 {
   __shared__ uint32_t tot[4];
   const uint32_t sf = blockIdx.x, sfi = (c->first_sf + sf * c->sf_step) % 10, l = c->npdcch;
   if (threadIdx.x < 4) tot[threadIdx.x] = 0;
   __syncthreads();
   rg32_t *map = (rg32_t *)(c->map + c->map_off[sfi][0]);
-  const size_t so = ((size_t)sf * c->nsymb + l) * c->N;
+  static_assert(PREC || !PIL, "TM2 demodulates from the estimate planes only");
+  const size_t so = PREC ? 0 : ((size_t)sf * c->nsymb + l) * c->N;
   uint32_t part[4] = {0, 0, 0, 0};
   for (uint32_t j = threadIdx.x; j < c->lvl_n[sfi]; j += blockDim.x) {
-    const uint32_t col = map[j] >> 16;
+    const uint32_t col = PREC ? (map[j] >> 16) & RX_COL_MASK : map[j] >> 16;
 #pragma unroll
     for (uint32_t pa = 0; pa < 4; pa++)
-      if ((pa & 1u) < c->nb_rx) part[pa] += rx_h2((uint32_t)est[pa * plane + so + col]);
+      if ((pa & 1u) < c->nb_rx)
+        part[pa] += rx_h2(PREC ? rx_est<PIL>(c, est, plane, pa, sf, l, col) : (uint32_t)est[pa * plane + so + col]);
   }
 #pragma unroll
   for (int pa = 0; pa < 4; pa++)
@@ -356,7 +321,7 @@ __global__ void __launch_bounds__(256) k_rx_level_tm2(const rx_dev_t *__restrict
         const uint8_t v = rx_shift_of((int32_t)tot[pa], c->lvl_div[sfi]);   /* log2 monotone: max of shifts */
         m = v > m ? v : m;
       }
-    shift[sf] = m;
+    shift[sf] = PREC ? (uint8_t)(m + c->lvl_inc) : m;
   }
 }
 
@@ -432,22 +397,6 @@ __global__ void __launch_bounds__(256) k_rx_llr_tm2(const rx_dev_t *__restrict__
   }
 }
 
-hipError_t oai4g_launch_rx_tm2(const rx_dev_t *d_cfg, const rx_dev_t *h_cfg, int n_sf, const int32_t *d_rxF,
-                               const int32_t *d_est, size_t plane, int16_t *d_llr, uint8_t *d_shift, int unscramble,
-                               hipStream_t s)
-{
-  if (n_sf <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_rx_level_tm2, dim3(n_sf), dim3(256), 0, s, d_cfg, d_est, plane, d_shift);
-  const dim3 g(h_cfg->n_sym, n_sf), b(256);
-  if (h_cfg->Qm == 2)
-    hipLaunchKernelGGL(k_rx_llr_tm2<2>, g, b, 0, s, d_cfg, d_rxF, d_est, plane, d_llr, d_shift, unscramble);
-  else if (h_cfg->Qm == 4)
-    hipLaunchKernelGGL(k_rx_llr_tm2<4>, g, b, 0, s, d_cfg, d_rxF, d_est, plane, d_llr, d_shift, unscramble);
-  else
-    hipLaunchKernelGGL(k_rx_llr_tm2<6>, g, b, 0, s, d_cfg, d_rxF, d_est, plane, d_llr, d_shift, unscramble);
-  return hipGetLastError();
-}
-
 /* ======================================================================================
  * TM4-6 (MIMO modes 3..7: one codeword precoded onto two ports) with dlsim's UE (rx_pdsch,
  * dual_stream_flag = 0, the branch at dlsch_demodulation.c:518-533):
@@ -459,122 +408,9 @@ hipError_t oai4g_launch_rx_tm2(const rx_dev_t *d_cfg, const rx_dev_t *h_cfg, int
  *   dlsch_channel_compensation_TM56 :1466-1669 with prec2A_TM56_128 per antenna
  *   dlsch_detection_mrc         :2583-2621
  *   dlsch_qpsk / 16qam / 64qam_llr, unscrambled
- * One thread per RE, the shape of k_rx_llr_tm3; planes and layouts as for TM3 (PIL: pilot rows).
+ * k_rx_level_dual<PIL, true> and k_rx_llr_prec<QM, PIL, RX_TM56>; planes and layouts as for TM3 (PIL:
+ * pilot rows).
  * ==================================================================================== */
-constexpr uint32_t RX_COL_MASK = 0x3FFFu;                     /* estimate column of a TM4-6 map word >> 16 */
-
-template <bool PIL>
-__global__ void __launch_bounds__(256) k_rx_level_tm56(const rx_dev_t *__restrict__ c, const int32_t *__restrict__ est,
-                                                       size_t plane, uint8_t *__restrict__ shift)
-{
-  __shared__ uint32_t tot[4];
-  const uint32_t sf = blockIdx.x, sfi = (c->first_sf + sf * c->sf_step) % 10, l = c->npdcch;
-  if (threadIdx.x < 4) tot[threadIdx.x] = 0;
-  __syncthreads();
-  rg32_t *map = (rg32_t *)(c->map + c->map_off[sfi][0]);
-  uint32_t part[4] = {0, 0, 0, 0};
-  for (uint32_t j = threadIdx.x; j < c->lvl_n[sfi]; j += blockDim.x) {
-    const uint32_t col = (map[j] >> 16) & RX_COL_MASK;
-#pragma unroll
-    for (uint32_t pa = 0; pa < 4; pa++)
-      if ((pa & 1u) < c->nb_rx) part[pa] += rx_h2(rx_est<PIL>(c, est, plane, pa, sf, l, col));
-  }
-#pragma unroll
-  for (int pa = 0; pa < 4; pa++)
-    if (part[pa]) atomicAdd(&tot[pa], part[pa]);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint8_t m = 0;
-    for (uint32_t pa = 0; pa < 4; pa++)
-      if ((pa & 1u) < c->nb_rx) {
-        const uint8_t v = rx_shift_of((int32_t)tot[pa], c->lvl_div[sfi]);   /* log2 monotone: max of shifts */
-        m = v > m ? v : m;
-      }
-    shift[sf] = (uint8_t)(m + c->lvl_inc);
-  }
-}
-
-template <int QM, bool PIL>
-__global__ void __launch_bounds__(256) k_rx_llr_tm56(const rx_dev_t *__restrict__ c, const int32_t *__restrict__ rxF,
-                                                     const int32_t *__restrict__ est, size_t plane,
-                                                     int16_t *__restrict__ llr, const uint8_t *__restrict__ shift,
-                                                     int unscramble)
-{
-  const uint32_t sf = blockIdx.y, k = blockIdx.x, sfi = (c->first_sf + sf * c->sf_step) % 10;
-  const uint32_t l = c->npdcch + k, len = c->len[sfi][k], nb_rx = c->nb_rx, NS = c->nsymb * c->N;
-  rg32_t *map = (rg32_t *)(c->map + c->map_off[sfi][k]);
-  int16_t *out = llr + (size_t)sf * c->llr_stride + c->llr_off[sfi][k];
-  const uint32_t sh = shift[sf], base = c->llr_off[sfi][k];
-  rg32_t *gold = (rg32_t *)(c->gold + (size_t)sfi * c->gold_words);
-  const int16_t a1 = c->a1, a2 = c->a2;
-  uint32_t mw[RX_R];
-#pragma unroll
-  for (int r = 0; r < RX_R; r++) {
-    const uint32_t j = threadIdx.x + 256 * r;
-    mw[r] = j < len ? map[j] : 0u;
-  }
-  uint32_t yv[2][RX_R], h0[2][RX_R], h1[2][RX_R];
-#pragma unroll
-  for (uint32_t a = 0; a < 2; a++)
-#pragma unroll
-    for (int r = 0; r < RX_R; r++) {
-      const uint32_t aa = a < nb_rx ? a : 0u, col = (mw[r] >> 16) & RX_COL_MASK;
-      const size_t yo = ((size_t)sf * nb_rx + aa) * NS + (size_t)l * c->N;
-      yv[a][r] = (uint32_t)rxF[yo + (mw[r] & 0xFFFFu)];
-      h0[a][r] = rx_est<PIL>(c, est, plane, aa, sf, l, col);
-      h1[a][r] = rx_est<PIL>(c, est, plane, 2 + aa, sf, l, col);
-    }
-#pragma unroll
-  for (int r = 0; r < RX_R; r++) {
-    const uint32_t j = threadIdx.x + 256 * r;
-    if (j >= len) break;
-    int16_t cr[2], ci[2], mg[2] = {0, 0}, mgb[2] = {0, 0};
-#pragma unroll
-    for (uint32_t a = 0; a < 2; a++) {
-      const uint32_t p = rx_prec_tm56(h0[a][r], h1[a][r], mw[r] >> 30);
-      rx_conj_mul(p, yv[a][r], sh, cr[a], ci[a]);
-      if (QM > 2) {
-        const int16_t m = rx_sat16((int32_t)rx_h2(p) >> sh);
-        mg[a] = (int16_t)((((int32_t)m * a1) >> 16) << 1);
-        mgb[a] = (int16_t)((((int32_t)m * a2) >> 16) << 1);
-      }
-    }
-    if (nb_rx > 1) {                                          /* dlsch_detection_mrc */
-      cr[0] = rx_sat16((cr[0] >> 1) + (cr[1] >> 1));
-      ci[0] = rx_sat16((ci[0] >> 1) + (ci[1] >> 1));
-      mg[0] = rx_sat16((mg[0] >> 1) + (mg[1] >> 1));
-      mgb[0] = rx_sat16((mgb[0] >> 1) + (mgb[1] >> 1));
-    }
-    int16_t v[6];
-    rx_llr_values<QM>(cr[0], ci[0], mg[0], mgb[0], v);
-    rx_llr_store<QM>(v, unscramble ? gold : nullptr, base + j * QM, out + QM * j);
-  }
-}
-
-template <bool PIL>
-static hipError_t launch_rx_tm56(const rx_dev_t *d_cfg, const rx_dev_t *h_cfg, int n_sf, const int32_t *d_rxF,
-                                 const int32_t *d_est, size_t plane, int16_t *d_llr, uint8_t *d_shift, int unscramble,
-                                 hipStream_t s)
-{
-  hipLaunchKernelGGL(k_rx_level_tm56<PIL>, dim3(n_sf), dim3(256), 0, s, d_cfg, d_est, plane, d_shift);
-  const dim3 g(h_cfg->n_sym, n_sf), b(256);
-  if (h_cfg->Qm == 2)
-    hipLaunchKernelGGL((k_rx_llr_tm56<2, PIL>), g, b, 0, s, d_cfg, d_rxF, d_est, plane, d_llr, d_shift, unscramble);
-  else if (h_cfg->Qm == 4)
-    hipLaunchKernelGGL((k_rx_llr_tm56<4, PIL>), g, b, 0, s, d_cfg, d_rxF, d_est, plane, d_llr, d_shift, unscramble);
-  else
-    hipLaunchKernelGGL((k_rx_llr_tm56<6, PIL>), g, b, 0, s, d_cfg, d_rxF, d_est, plane, d_llr, d_shift, unscramble);
-  return hipGetLastError();
-}
-
-hipError_t oai4g_launch_rx_tm56(const rx_dev_t *d_cfg, const rx_dev_t *h_cfg, int n_sf, const int32_t *d_rxF,
-                                const int32_t *d_est, size_t plane, int16_t *d_llr, uint8_t *d_shift, int unscramble,
-                                hipStream_t s, int pil)
-{
-  if (n_sf <= 0) return hipSuccess;
-  return pil ? launch_rx_tm56<true>(d_cfg, h_cfg, n_sf, d_rxF, d_est, plane, d_llr, d_shift, unscramble, s)
-             : launch_rx_tm56<false>(d_cfg, h_cfg, n_sf, d_rxF, d_est, plane, d_llr, d_shift, unscramble, s);
-}
 
 /* dlsch_unscrambling drop-in: llr[k] *= 2 c(k) - 1 (int16), c = the words of the Gold sequence */
 __global__ void __launch_bounds__(256) k_rx_unscramble(int16_t *__restrict__ llr, const uint32_t *__restrict__ c,
@@ -591,17 +427,55 @@ hipError_t oai4g_launch_unscramble(int16_t *d_llr, const uint32_t *d_c, int n, h
   return hipGetLastError();
 }
 
-hipError_t oai4g_launch_rx(const rx_dev_t *d_cfg, const rx_dev_t *h_cfg, int n_sf, const int32_t *d_rxF,
-                           const int32_t *d_ch, int16_t *d_llr, uint8_t *d_shift, int unscramble, hipStream_t s)
+template <class F>
+static void rx_dispatch_qm(uint32_t qm, F f)
+{
+  if (qm == 2) f(std::integral_constant<int, 2>());
+  else if (qm == 4) f(std::integral_constant<int, 4>());
+  else f(std::integral_constant<int, 6>());
+}
+
+template <class F>
+static void rx_dispatch_pil(int pil, F f)
+{
+  if (pil) f(std::true_type());
+  else f(std::false_type());
+}
+
+/* the level kernel and the LLR kernel of a configuration's mode; 256 x RX_R >= 1200 REs per symbol.
+ * TM3 with codeword 0 QPSK runs k_rx_llr_tm3qq on codeword 1's modulation (d_llr1 may be null); SISO
+ * takes its one estimate grid as d_est; pil is for TM3 and TM4-6 only. */
+hipError_t oai4g_launch_rx(rx_mode_t mode, const rx_dev_t *d_cfg, const rx_dev_t *h_cfg, int n_sf, const int32_t *d_rxF,
+                           const int32_t *d_est, size_t plane, int16_t *d_llr, int16_t *d_llr1, uint8_t *d_shift,
+                           int unscramble, hipStream_t s, int pil)
 {
   if (n_sf <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_rx_level, dim3(n_sf), dim3(256), 0, s, d_cfg, d_ch, d_shift);
-  const dim3 g(h_cfg->n_sym, n_sf), b(256);                  /* 256 x RX_R >= 1200 REs per symbol */
-  if (h_cfg->Qm == 2)
-    hipLaunchKernelGGL(k_rx_llr<2>, g, b, 0, s, d_cfg, d_rxF, d_ch, d_llr, d_shift, unscramble);
-  else if (h_cfg->Qm == 4)
-    hipLaunchKernelGGL(k_rx_llr<4>, g, b, 0, s, d_cfg, d_rxF, d_ch, d_llr, d_shift, unscramble);
-  else
-    hipLaunchKernelGGL(k_rx_llr<6>, g, b, 0, s, d_cfg, d_rxF, d_ch, d_llr, d_shift, unscramble);
+  const dim3 gl(n_sf), g(h_cfg->n_sym, n_sf), b(256);
+  const bool qq = mode == RX_TM3 && h_cfg->Qm == 2;
+  rx_dispatch_pil(pil, [&](auto pil_c) {
+    rx_dispatch_qm(qq ? h_cfg->qm1 : h_cfg->Qm, [&](auto qm_c) {
+      constexpr bool PIL = decltype(pil_c)::value;
+      constexpr int QM = decltype(qm_c)::value;
+      if (mode == RX_TM3) {
+        hipLaunchKernelGGL(k_rx_level_tm3<PIL>, gl, b, 0, s, d_cfg, d_est, plane, d_shift);
+        if (qq)
+          hipLaunchKernelGGL((k_rx_llr_tm3qq<QM, PIL>), g, b, 0, s, d_cfg, d_rxF, d_est, plane, d_llr,
+                             QM == 2 ? d_llr1 : nullptr, d_shift, unscramble);
+        else if constexpr (QM > 2)
+          hipLaunchKernelGGL((k_rx_llr_prec<QM, PIL, RX_TM3>), g, b, 0, s, d_cfg, d_rxF, d_est, plane, d_llr, d_shift, unscramble);
+      } else if (mode == RX_TM56) {
+        hipLaunchKernelGGL((k_rx_level_dual<PIL, true>), gl, b, 0, s, d_cfg, d_est, plane, d_shift);
+        hipLaunchKernelGGL((k_rx_llr_prec<QM, PIL, RX_TM56>), g, b, 0, s, d_cfg, d_rxF, d_est, plane, d_llr, d_shift, unscramble);
+      } else if constexpr (!PIL) {
+        if (mode == RX_TM2) {
+          hipLaunchKernelGGL((k_rx_level_dual<false, false>), gl, b, 0, s, d_cfg, d_est, plane, d_shift);
+          hipLaunchKernelGGL(k_rx_llr_tm2<QM>, g, b, 0, s, d_cfg, d_rxF, d_est, plane, d_llr, d_shift, unscramble);
+        } else {
+          hipLaunchKernelGGL(k_rx_level, gl, b, 0, s, d_cfg, d_est, d_shift);
+          hipLaunchKernelGGL(k_rx_llr<QM>, g, b, 0, s, d_cfg, d_rxF, d_est, d_llr, d_shift, unscramble);
+        }
+      }
+    });
+  });
   return hipGetLastError();
 }

@@ -1,6 +1,6 @@
 """GPU parity of the TM4-6 (single-layer precoding, MIMO modes 3..7) receive chain — the dual
 extraction with pmi_ext, dlsch_channel_level (+ 1 with dl_power_off), prec2A_TM56_128 inside
-dlsch_channel_compensation_TM56, dlsch_detection_mrc, the LLRs (k_rx_level_tm56 / k_rx_llr_tm56) —
+dlsch_channel_compensation_TM56, dlsch_detection_mrc, the LLRs (k_rx_level_dual / k_rx_llr_prec) —
 against the numpy restatement tests/rx_tm56_model.py (validated by tests/test_rx_tm56_cpu.py): the drop-in
 on full-range random grids and estimates, its refusals, the batch (estimate planes and pilot rows)
 against the drop-in, and receive loops on the GPU: TM4-6 TxPipeline with both ports' CRS -> channel ->

@@ -1,6 +1,6 @@
 """GPU parity of the TM2 (ALAMOUTI, 2 TX ports) receive chain — dlsch_extract_rbs_dual,
 dlsch_channel_level over both ports, dlsch_channel_compensation per (port, RX antenna),
-dlsch_detection_mrc, dlsch_alamouti, the LLRs (k_rx_level_tm2 / k_rx_llr_tm2) — against the oracle
+dlsch_detection_mrc, dlsch_alamouti, the LLRs (k_rx_level_dual / k_rx_llr_tm2) — against the oracle
 restatement (tests/test_rx_tm2_cpu.py pins it by the decoding loop): the drop-in on full-range random
 grids and estimates (saturation / wrap paths, QPSK / 16 / 64-QAM, 1 and 2 receive antennas, odd
 N_RB_DL, partial allocations), and a receive loop on the GPU: TM2 TxPipeline (both ports' CRS) ->

@@ -1,6 +1,6 @@
 """GPU parity of the TM3 (LARGE_CDD, 2 TX ports) receive chain — dlsch_extract_rbs_dual,
 dlsch_channel_level_TM3, prec2A_TM3 + dlsch_channel_compensation_TM3, dlsch_detection_mrc, the
-codeword-0 LLRs (k_rx_level_tm3 / k_rx_llr_tm3) — against the oracle restatement
+codeword-0 LLRs (k_rx_level_tm3 / k_rx_llr_prec) — against the oracle restatement
 (tests/test_rx_tm3_cpu.py pins it by the decoding loop): the drop-in on full-range random grids and
 estimates (saturation / wrap paths, 1 and 2 receive antennas, odd N_RB_DL with the PBCH / sync
 subframes), and the headline configuration's receive loop on the GPU: C3 TxPipeline (both ports'

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """A/B timing of the TM4-6 demodulator against the TM3 one at the UE3 bench shape (100 PRB, 2 RX
-antennas, 64-QAM, estimate planes): RxBatchTM56.launch (k_rx_level_tm56 + k_rx_llr_tm56<6, false>)
-and RxBatchTM3.launch (k_rx_level_tm3 + k_rx_llr_tm3<6, false>) alternate inside one process on the
-same FEP output and the same estimate planes, HIP events around each launch, medians printed as one
-JSON line.  Both kernels load the same words per RE (two estimate planes per RX antenna and one
-received word).  Run it in several processes to see the process-to-process spread.
+antennas, 64-QAM, estimate planes): RxBatchTM56.launch (k_rx_level_dual<false, true> +
+k_rx_llr_prec<6, false, RX_TM56>) and RxBatchTM3.launch (k_rx_level_tm3 + k_rx_llr_prec<6, false, RX_TM3>)
+alternate inside one process on the same FEP output and the same estimate planes, HIP events around each
+launch, medians printed as one JSON line.  Both kernels load the same words per RE (two estimate planes per RX antenna and one
+received word).  Run it in several processes to see the process-to-process spread; OAI4G_LIB selects the
+library build, so the same runs compare two builds.
 
     python tools/rx_tm56_ab.py [--batch 2048] [--reps 200]
 """

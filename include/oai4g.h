@@ -284,6 +284,109 @@ uint8_t oai4g_generate_dci_top(uint8_t num_ue_spec_dci, uint8_t num_common_dci, 
                                uint32_t n_rnti, int16_t amp, const oai4g_frame_parms_t *frame_parms,
                                int32_t **txdataF, uint32_t subframe);
 
+/* ---------------- UE control decoding: tail-biting Viterbi, DCI, PBCH ---------------- */
+/* phy_viterbi_lte_sse2 (PHY/CODING/viterbi_lte.c:140): n triples of soft bits y (bit 1 positive), two
+ * passes over them with 8-bit saturating metrics, ties to the predecessor k + 32, traceback from the
+ * first state with the largest metric; the decoded bits are ADDED into decoded_bytes (MSB first),
+ * so the caller zeroes it, as the reference's callers do.  The reference is defined for soft bits
+ * in [-8, 7] only (outside it reads past its tables); here every input is clamped to that range
+ * first.  Returns 0, 1 when an input had to be clamped, or -1 (n = 0, n > 512, no device). */
+int oai4g_phy_viterbi_lte(const int8_t *y, uint8_t *decoded_bytes, uint16_t n);
+/* the same decode with its final state exposed (tests): the 64 path metrics after the second pass
+ * and the state the traceback starts from; decoded (ceil(n / 8) bytes) is overwritten */
+int oai4g_diag_viterbi_lte(const int8_t *y, uint16_t n, uint8_t *decoded, uint8_t metrics[64], uint8_t *start_state);
+/* The receive plan of the convolutional code's rate matching for D trellis steps (D = payload + 16):
+ * plan[3 i + s] is the first index of e that lte_rate_matching_cc_rx (lte_rate_matching.c:834) sums
+ * into d^(s)_i after sub_block_deinterleaving_cc (:245); the repetitions follow every 3 D, below E.
+ * Derived from generate_dummy_w_cc's <NULL> set (:384).  Returns 3 D, or -1 (D = 0 or D > 512). */
+int oai4g_cc_rx_plan(uint32_t D, uint16_t *plan);
+/* dci_decoding (PHY/LTE_TRANSPORT/dci.c:2426): e holds the 72 << aggregation_level soft bits of the
+ * candidate's CCEs; rate-matching receive (sum of the repetitions, clamp to [-8, 7]), deinterleaving
+ * and the Viterbi over DCI_LENGTH + 16 steps into decoded_output, of which
+ * 2 + ((16 + DCI_LENGTH) >> 3) bytes are zeroed first.  Returns 0, or -1 for what the reference's
+ * buffers do not hold (aggregation_level > 3, DCI_LENGTH > 45) and without a device; crc, when not
+ * null, receives crc16(decoded, DCI_LENGTH) ^ the 16 bits that follow (the RNTI of a match). */
+int oai4g_dci_decoding(uint8_t DCI_LENGTH, uint8_t aggregation_level, const int8_t *e, uint8_t *decoded_output);
+int oai4g_dci_decoding_crc(uint8_t DCI_LENGTH, uint8_t aggregation_level, const int8_t *e, uint8_t *decoded_output,
+                           uint16_t *crc);
+/* rx_pbch from the quantised soft bits on (PHY/LTE_TRANSPORT/pbch.c:975-1043): llr holds pbch_E =
+ * 1920 (1728 with the extended prefix) soft bits, all of them read; quarter frame_mod4 is
+ * unscrambled (pbch_unscrambling :785, c_init = Nid_cell), then the rate-matching receive,
+ * deinterleaving, the Viterbi over 40 steps and the CRC16.  decoded_output receives the three MIB
+ * bytes, reversed as the reference returns them.  Returns the number of eNB antennas 1 / 2 / 4 the
+ * CRC mask names, or -1: the reference's -1 when the CRC matches none of them (oai4g_last_error()
+ * is then empty), and a refused call (frame_mod4 > 3, no device; oai4g_last_error() says which). */
+int oai4g_pbch_decode(const int8_t *llr, const oai4g_frame_parms_t *frame_parms, uint8_t frame_mod4,
+                      uint8_t decoded_output[3]);
+/* n PBCH decodes in one launch, device pointers: d_llr [n][pbch_E], d_frame_mod4 [n], d_out [n][4] =
+ * the three MIB bytes as above and the antenna count (1 / 2 / 4, 0xFF when the CRC matches none).
+ * Asynchronous on `stream`.  Returns 0 or -1. */
+int oai4g_pbch_decode_batch(const int8_t *d_llr, int n, const oai4g_frame_parms_t *frame_parms,
+                            const uint8_t *d_frame_mod4, uint8_t *d_out, void *stream);
+
+/* The soft bits of rx_pdcch after channel compensation (dci.c:1852-1897) as one fixed gather with a
+ * sign per (frame parameters, subframe, num_pdcch_symbols): pdcch_llr (:603, clip to [-32, 31], re
+ * before im), pdcch_demapping (:342, the REG walk around the PCFICH / PHICH REGs with its two RE
+ * counters), pdcch_deinterleaving (:449, the cell-id cyclic shift and the 32-column permutation on
+ * quadruplets) and pdcch_unscrambling (:1932, c_init = (subframe << 9) + Nid_cell, negation where the
+ * Gold bit is 0, over 72 nCCE soft bits).  table[i] for soft bit i of e_rx: the int16 index into
+ * rxdataF_comp (plane 0, symbol * 12 * N_RB_DL int32 per symbol; symbol 0 holds its 8 non-pilot REs
+ * per RB packed) | negate << 31, or 0xFFFFFFFF where nothing is mapped (the soft bit is 0).  Returns
+ * the number of soft bits 8 * Mquad (cap must hold them), or -1: 4 TX ports (the reference's demapping
+ * leaves them "LATER") and every geometry oai4g_generate_dci_top refuses. */
+int oai4g_pdcch_soft_bit_table(const oai4g_frame_parms_t *frame_parms, uint8_t subframe, uint8_t num_pdcch_symbols,
+                               uint32_t *table, uint32_t cap);
+/* the gather itself on host buffers: e_rx receives 8 * Mquad soft bits.  Returns their number or -1. */
+int oai4g_pdcch_soft_bits(const int32_t *rxdataF_comp, const oai4g_frame_parms_t *frame_parms, uint8_t subframe,
+                          uint8_t num_pdcch_symbols, int8_t *e_rx);
+/* CCEind of every candidate of one dci_decoding_procedure0 call (dci.c:2576-2624), in its order: the
+ * common space from CCE 0, the UE-specific space from Yk of the C-RNTI and subframe; returns their
+ * number (0 when nCCE < 2^L), or -1. */
+int oai4g_pdcch_candidates(const oai4g_frame_parms_t *frame_parms, uint8_t num_pdcch_symbols, uint8_t subframe,
+                           uint16_t crnti, int do_common, uint8_t L, uint16_t *cce, int cap);
+/* dci_decoding_procedure0 (dci.c:2547) with the reference's argument list; lte_ue_pdcch_vars is
+ * spelled out as e_rx, num_pdcch_symbols, crnti and nCCE (the nCCE[subframe] slot).  Every candidate
+ * of the call is decoded in one launch; the skip / match / acceptance rules then run in candidate
+ * order, so the result is the reference's (a skipped candidate's decode is ignored; the decode has no
+ * side effects).  dci_alloc must have room for *dci_cnt + 1 entries.  Returns 0, or -1. */
+int oai4g_dci_decoding_procedure0(const int8_t *e_rx, uint8_t num_pdcch_symbols, uint16_t crnti, uint8_t *nCCE,
+                                  int do_common, uint8_t subframe, oai4g_dci_alloc_t *dci_alloc,
+                                  const oai4g_frame_parms_t *frame_parms, uint8_t mi, uint16_t si_rnti, uint16_t ra_rnti,
+                                  uint8_t L, uint8_t format_si, uint8_t format_ra, uint8_t format_c, uint8_t sizeof_bits,
+                                  uint8_t sizeof_bytes, uint8_t *dci_cnt, uint8_t *format0_found, uint8_t *format_c_found,
+                                  uint32_t *CCEmap0, uint32_t *CCEmap1, uint32_t *CCEmap2);
+
+/* Batched, device-resident DCI search.  A plan entry is one dci_decoding_procedure0 call of
+ * dci_decoding_procedure (dci.c:2788); between entries the search ends when CCEmap0 == 0xffff or both
+ * found flags are set, and after an entry with stop_if_found when it advanced dci_cnt (:3266). */
+typedef struct {
+  uint8_t do_common, L, sizeof_bits, sizeof_bytes, format_si, format_ra, format_c, stop_if_found;
+} oai4g_pdcch_plan_t;
+#define OAI4G_PDCCH_MAX_DCI 8
+typedef struct {
+  uint8_t dci_cnt, format0_found, format_c_found;
+  uint8_t overflow;                          /* 1: more than OAI4G_PDCCH_MAX_DCI matches; the further ones only marked their CCEs */
+  int32_t nCCE;                              /* nCCE[subframe] where an accepted DCI stored it, else -1 */
+  uint32_t CCEmap[3];
+  oai4g_dci_alloc_t dci[OAI4G_PDCCH_MAX_DCI];   /* the first dci_cnt are the found DCIs */
+} oai4g_pdcch_rx_result_t;
+typedef struct oai4g_pdcch_rx_config oai4g_pdcch_rx_config_t;
+/* derives, per subframe index 0..9, the soft-bit gather table and the candidate list in plan order */
+oai4g_pdcch_rx_config_t *oai4g_pdcch_rx_config_create(const oai4g_frame_parms_t *frame_parms, uint8_t num_pdcch_symbols,
+                                                      uint16_t crnti, uint16_t si_rnti, uint16_t ra_rnti,
+                                                      const oai4g_pdcch_plan_t *plan, int n_plan);
+void oai4g_pdcch_rx_config_destroy(oai4g_pdcch_rx_config_t *cfg);
+/* the candidates of subframe index `subframe` in plan order (tests): cce[i], plan_entry[i]; returns their
+ * number (cap entries are written at most) */
+int oai4g_pdcch_rx_candidates(const oai4g_pdcch_rx_config_t *cfg, uint8_t subframe, uint16_t *cce, uint8_t *plan_entry,
+                              int cap);
+/* d_comp [n_sf][num_pdcch_symbols * 12 * N_RB_DL] int32 (device), subframe i of the batch has subframe
+ * index (first_subframe + i) mod 10; one launch decodes every candidate of every subframe, a second
+ * stage (one lane per subframe) walks them in plan order; d_out [n_sf] (device).  Asynchronous on
+ * `stream`.  Returns 0 or -1. */
+int oai4g_pdcch_rx_batch(oai4g_pdcch_rx_config_t *cfg, const int32_t *d_comp, int n_sf, int first_subframe,
+                         oai4g_pdcch_rx_result_t *d_out, void *stream);
+
 /* ---------------- UE PDSCH demodulation (second half) ---------------- */
 /* rx_pdsch (PHY/LTE_TRANSPORT/dlsch_demodulation.c:82) over the PDSCH symbols of one subframe as
  * dlsim runs it (dlsim.c:3188-3260): dlsch_extract_rbs_single (:3167), dlsch_channel_level (:2777)

@@ -370,6 +370,33 @@ _SIGS = {
     "oai4g_ul_decode_batch_harq_tb": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
                                                      ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
                                                      ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    "oai4g_phy_viterbi_lte": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint16]),
+    "oai4g_diag_viterbi_lte": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint16, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p]),
+    "oai4g_cc_rx_plan": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_void_p]),
+    "oai4g_dci_decoding": (ctypes.c_int, [ctypes.c_uint8, ctypes.c_uint8, ctypes.c_void_p, ctypes.c_void_p]),
+    "oai4g_dci_decoding_crc": (ctypes.c_int, [ctypes.c_uint8, ctypes.c_uint8, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.POINTER(ctypes.c_uint16)]),
+    "oai4g_pbch_decode": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(FrameParms), ctypes.c_uint8, ctypes.c_void_p]),
+    "oai4g_pbch_decode_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(FrameParms),
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "oai4g_pdcch_soft_bit_table": (ctypes.c_int, [ctypes.POINTER(FrameParms), ctypes.c_uint8, ctypes.c_uint8,
+                                                  ctypes.c_void_p, ctypes.c_uint32]),
+    "oai4g_pdcch_soft_bits": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(FrameParms), ctypes.c_uint8, ctypes.c_uint8,
+                                             ctypes.c_void_p]),
+    "oai4g_dci_decoding_procedure0": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint8, ctypes.c_uint16, ctypes.c_void_p,
+                                                     ctypes.c_int, ctypes.c_uint8, ctypes.c_void_p,
+                                                     ctypes.POINTER(FrameParms), ctypes.c_uint8, ctypes.c_uint16,
+                                                     ctypes.c_uint16] + [ctypes.c_uint8] * 6 + [ctypes.c_void_p] * 6),
+    "oai4g_pdcch_candidates": (ctypes.c_int, [ctypes.POINTER(FrameParms), ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint16,
+                                              ctypes.c_int, ctypes.c_uint8, ctypes.c_void_p, ctypes.c_int]),
+    "oai4g_pdcch_rx_config_create": (ctypes.c_void_p, [ctypes.POINTER(FrameParms), ctypes.c_uint8, ctypes.c_uint16,
+                                                       ctypes.c_uint16, ctypes.c_uint16, ctypes.c_void_p, ctypes.c_int]),
+    "oai4g_pdcch_rx_config_destroy": (None, [ctypes.c_void_p]),
+    "oai4g_pdcch_rx_candidates": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint8, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_int]),
+    "oai4g_pdcch_rx_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                            ctypes.c_void_p]),
 }
 
 
@@ -1077,6 +1104,196 @@ def turbo_decoder8(y, n, max_iterations=8, crc_type=0, F=0):
     it = lib().oai4g_phy_threegpplte_turbo_decoder8(_ptr(y), _ptr(out), n, 0, 0, max_iterations, crc_type, F)
     _check(it != 255)
     return it, out
+
+
+def viterbi_lte(y, n, decoded=None):
+    """phy_viterbi_lte_sse2 drop-in: y = 3n int8 soft bits, the decoded bits are added into `decoded`
+    (zeros when not given).  Returns (1 if an input had to be clamped to [-8, 7] else 0, decoded bytes)."""
+    y = np.ascontiguousarray(y, dtype=np.int8)
+    out = np.zeros((n + 7) >> 3, dtype=np.uint8) if decoded is None else decoded
+    r = lib().oai4g_phy_viterbi_lte(_ptr(y), _ptr(out), n)
+    _check(r >= 0)
+    return r, out
+
+
+def viterbi_lte_state(y, n):
+    """The same decode with its final state: (clamped, decoded bytes, 64 final metrics, start state)."""
+    y = np.ascontiguousarray(y, dtype=np.int8)
+    out = np.zeros((n + 7) >> 3, dtype=np.uint8)
+    met = np.zeros(64, dtype=np.uint8)
+    st = ctypes.c_uint8()
+    r = lib().oai4g_diag_viterbi_lte(_ptr(y), n, _ptr(out), _ptr(met), ctypes.byref(st))
+    _check(r >= 0)
+    return r, out, met, st.value
+
+
+def cc_rx_plan(D):
+    """oai4g_cc_rx_plan: uint16[3 D], the first e index summed into every Viterbi input."""
+    plan = np.zeros(3 * D, dtype=np.uint16)
+    _check(lib().oai4g_cc_rx_plan(D, _ptr(plan)) == 3 * D)
+    return plan
+
+
+def dci_decoding(dci_length, L, e):
+    """dci_decoding drop-in: e = 72 << L int8 soft bits.  Returns (the 2 + ((16 + dci_length) >> 3)
+    decoded bytes, crc16 ^ the received CRC: the RNTI of a match)."""
+    e = np.ascontiguousarray(e, dtype=np.int8)
+    out = np.full(2 + ((16 + dci_length) >> 3), 0xA5, dtype=np.uint8)
+    crc = ctypes.c_uint16()
+    _check(lib().oai4g_dci_decoding_crc(dci_length, L, _ptr(e), _ptr(out), ctypes.byref(crc)) == 0)
+    return out, crc.value
+
+
+def pbch_decode(llr, fp, frame_mod4):
+    """rx_pbch from the quantised soft bits on: llr = pbch_E int8.  Returns (1 / 2 / 4 eNB antennas or -1
+    when the CRC matches none, the three MIB bytes); a refused call raises."""
+    llr = np.ascontiguousarray(llr, dtype=np.int8)
+    out = np.zeros(3, dtype=np.uint8)
+    r = lib().oai4g_pbch_decode(_ptr(llr), ctypes.byref(fp), frame_mod4, _ptr(out))
+    _check(r >= 0 or not lib().oai4g_last_error())
+    return r, bytes(out)
+
+
+class PbchDecodeBatch:
+    """Device-resident batch of n PBCH decodes (oai4g_pbch_decode_batch)."""
+
+    def __init__(self, fp, n):
+        init()
+        self.L, self.fp, self.n = lib(), fp, n
+        self.E = 1920 if fp.Ncp == 0 else 1728
+        self.d_llr = self.L.oai4g_dev_alloc(n * self.E)
+        self.d_q = self.L.oai4g_dev_alloc(n)
+        self.d_out = self.L.oai4g_dev_alloc(4 * n)
+        _check(all(bool(p) for p in (self.d_llr, self.d_q, self.d_out)))
+
+    def upload(self, llr, frame_mod4):
+        llr = np.ascontiguousarray(llr, dtype=np.int8).reshape(self.n, self.E)
+        q = np.ascontiguousarray(frame_mod4, dtype=np.uint8).reshape(self.n)
+        _check(self.L.oai4g_memcpy_h2d(self.d_llr, _ptr(llr), llr.nbytes) == 0)
+        _check(self.L.oai4g_memcpy_h2d(self.d_q, _ptr(q), q.nbytes) == 0)
+
+    def launch(self, stream=None):
+        _check(self.L.oai4g_pbch_decode_batch(self.d_llr, self.n, ctypes.byref(self.fp), self.d_q, self.d_out,
+                                              stream) == 0)
+
+    def results(self):
+        """(antenna counts int16[n] with -1 for none, MIB bytes uint8[n][3])"""
+        _check(self.L.oai4g_sync() == 0)
+        out = np.empty((self.n, 4), dtype=np.uint8)
+        _check(self.L.oai4g_memcpy_d2h(_ptr(out), self.d_out, out.nbytes) == 0)
+        cnt = out[:, 3].astype(np.int16)
+        cnt[cnt == 0xFF] = -1
+        return cnt, out[:, :3].copy()
+
+    def close(self):
+        for p in (self.d_llr, self.d_q, self.d_out):
+            self.L.oai4g_dev_free(p)
+
+
+def pdcch_soft_bit_table(fp, subframe, num_pdcch):
+    """oai4g_pdcch_soft_bit_table: uint32 per soft bit of e_rx (int16 index into comp | negate << 31,
+    0xFFFFFFFF: nothing mapped)."""
+    tab = np.zeros(8 * 800, dtype=np.uint32)
+    n = lib().oai4g_pdcch_soft_bit_table(ctypes.byref(fp), subframe, num_pdcch, _ptr(tab), len(tab))
+    _check(n >= 0)
+    return tab[:n].copy()
+
+
+def pdcch_soft_bits(comp, fp, subframe, num_pdcch):
+    """rx_pdcch after compensation: comp = int32[num_pdcch * 12 * N_RB_DL] -> e_rx int8[8 * Mquad]."""
+    comp = np.ascontiguousarray(comp, dtype=np.int32)
+    e = np.zeros(8 * 800, dtype=np.int8)
+    n = lib().oai4g_pdcch_soft_bits(_ptr(comp), ctypes.byref(fp), subframe, num_pdcch, _ptr(e))
+    _check(n >= 0)
+    return e[:n].copy()
+
+
+def pdcch_candidates(fp, num_pdcch, subframe, crnti, do_common, L):
+    """CCEind of the candidates of one dci_decoding_procedure0 call, in its order."""
+    cce = np.zeros(16, dtype=np.uint16)
+    n = lib().oai4g_pdcch_candidates(ctypes.byref(fp), num_pdcch, subframe, crnti, do_common, L, _ptr(cce), 16)
+    _check(n >= 0)
+    return cce[:n].tolist()
+
+
+class PdcchPlan(ctypes.Structure):
+    """oai4g_pdcch_plan_t: one dci_decoding_procedure0 call"""
+    _fields_ = [(n, ctypes.c_uint8) for n in ("do_common", "L", "sizeof_bits", "sizeof_bytes", "format_si", "format_ra",
+                                              "format_c", "stop_if_found")]
+
+
+class PdcchRxResult(ctypes.Structure):
+    _fields_ = [("dci_cnt", ctypes.c_uint8), ("format0_found", ctypes.c_uint8), ("format_c_found", ctypes.c_uint8),
+                ("overflow", ctypes.c_uint8), ("nCCE", ctypes.c_int32), ("CCEmap", ctypes.c_uint32 * 3),
+                ("dci", DciAlloc * 8)]
+
+
+class DciSearchState:
+    """the caller state of dci_decoding_procedure0: CCE maps, found flags, dci_cnt, nCCE[subframe]"""
+
+    def __init__(self, n_alloc=16):
+        self.alloc = (DciAlloc * n_alloc)()
+        self.cnt, self.f0, self.fc, self.nCCE = ctypes.c_uint8(), ctypes.c_uint8(), ctypes.c_uint8(), ctypes.c_uint8(255)
+        self.maps = [ctypes.c_uint32() for _ in range(3)]
+
+    def found(self):
+        return [(a.dci_length, a.L, a.nCCE, a.rnti, a.format, bytes(a.dci_pdu)) for a in self.alloc[:self.cnt.value]]
+
+
+def dci_decoding_procedure0(state, e_rx, num_pdcch, crnti, do_common, subframe, fp, mi, si_rnti, ra_rnti, L, format_si,
+                            format_ra, format_c, sizeof_bits, sizeof_bytes):
+    """dci_decoding_procedure0 drop-in on a DciSearchState (updated in place)."""
+    e_rx = np.ascontiguousarray(e_rx, dtype=np.int8)
+    st = state
+    _check(lib().oai4g_dci_decoding_procedure0(
+        _ptr(e_rx), num_pdcch, crnti, ctypes.addressof(st.nCCE), do_common, subframe, ctypes.addressof(st.alloc),
+        ctypes.byref(fp), mi, si_rnti, ra_rnti, L, format_si, format_ra, format_c, sizeof_bits, sizeof_bytes,
+        ctypes.addressof(st.cnt), ctypes.addressof(st.f0), ctypes.addressof(st.fc), ctypes.addressof(st.maps[0]),
+        ctypes.addressof(st.maps[1]), ctypes.addressof(st.maps[2])) == 0)
+
+
+class PdcchRxBatch:
+    """Device-resident DCI search over n_sf subframes (oai4g_pdcch_rx_config_create / oai4g_pdcch_rx_batch).
+    plan: a list of (do_common, L, sizeof_bits, sizeof_bytes, format_si, format_ra, format_c, stop_if_found)."""
+
+    def __init__(self, fp, num_pdcch, crnti, si_rnti, ra_rnti, plan, n_sf):
+        init()
+        self.L, self.fp, self.n_sf, self.num_pdcch = lib(), fp, n_sf, num_pdcch
+        arr = (PdcchPlan * len(plan))(*[PdcchPlan(*p) for p in plan])
+        self.cfg = self.L.oai4g_pdcch_rx_config_create(ctypes.byref(fp), num_pdcch, crnti, si_rnti, ra_rnti, arr, len(plan))
+        _check(bool(self.cfg))
+        self.comp_words = num_pdcch * 12 * fp.N_RB_DL
+        self.d_comp = self.L.oai4g_dev_alloc(n_sf * self.comp_words * 4)
+        self.d_out = self.L.oai4g_dev_alloc(n_sf * ctypes.sizeof(PdcchRxResult))
+        _check(bool(self.d_comp) and bool(self.d_out))
+
+    def candidates(self, subframe):
+        """[(CCEind, plan entry)] of a subframe index, in plan order"""
+        cce = np.zeros(1024, dtype=np.uint16)
+        pe = np.zeros(1024, dtype=np.uint8)
+        n = self.L.oai4g_pdcch_rx_candidates(self.cfg, subframe, _ptr(cce), _ptr(pe), 1024)
+        _check(n >= 0)
+        return list(zip(cce[:n].tolist(), pe[:n].tolist()))
+
+    def upload(self, comp):
+        comp = np.ascontiguousarray(comp, dtype=np.int32).reshape(self.n_sf, self.comp_words)
+        _check(self.L.oai4g_memcpy_h2d(self.d_comp, _ptr(comp), comp.nbytes) == 0)
+
+    def launch(self, first_subframe=0, stream=None):
+        _check(self.L.oai4g_pdcch_rx_batch(self.cfg, self.d_comp, self.n_sf, first_subframe, self.d_out, stream) == 0)
+
+    def results(self):
+        _check(self.L.oai4g_sync() == 0)
+        out = (PdcchRxResult * self.n_sf)()
+        _check(self.L.oai4g_memcpy_d2h(ctypes.addressof(out), self.d_out, ctypes.sizeof(out)) == 0)
+        return out
+
+    def close(self):
+        if self.cfg:
+            self.L.oai4g_pdcch_rx_config_destroy(self.cfg)
+            self.L.oai4g_dev_free(self.d_comp)
+            self.L.oai4g_dev_free(self.d_out)
+            self.cfg = None
 
 
 def _upload_tiled(dec, base, chunk_bytes=64 << 20):

@@ -4870,3 +4870,620 @@ extern "C" int oai4g_dl_ch_estimates_time(const oai4g_frame_parms_t *fp, int nb_
   HCK(hipStreamSynchronize(g_scr.s), -1);
   return 0;
 }
+
+/* ------------------------------------------------------------------------------------------
+ * UE control decoding (oai4g_ctrl_rx.hip): the tail-biting Viterbi, dci_decoding (dci.c:2426-2489)
+ * and rx_pbch from the quantised soft bits on (pbch.c:975-1043).
+ * ---------------------------------------------------------------------------------------- */
+/* plan[3 i + s]: the k-th non-<NULL> entry of generate_dummy_w_cc's w (lte_rate_matching.c:384: stream s,
+ * then column, then row; <NULL> where bitrev_cc[col] < ND in row 0) is where lte_rate_matching_cc_rx
+ * (:834) accumulates e[k], e[k + 3 D], ..., and sub_block_deinterleaving_cc (:245) moves that entry to
+ * d[3 (32 row + bitrev_cc[col] - ND) + s] */
+static void cc_rx_plan_h(uint32_t D, uint16_t *plan)
+{
+  static const uint8_t bitrev_cc[32] = {1, 17, 9, 25, 5, 21, 13, 29, 3, 19, 11, 27, 7, 23, 15, 31,
+                                        0, 16, 8, 24, 4, 20, 12, 28, 2, 18, 10, 26, 6, 22, 14, 30};
+  const uint32_t R = (D + 31) >> 5, ND = 32 * R - D;
+  for (uint32_t s = 0; s < 3; s++) {
+    uint32_t j = 0;
+    for (uint32_t col = 0; col < 32; col++)
+      for (uint32_t row = 0; row < R; row++) {
+        const uint32_t idx = 32 * row + bitrev_cc[col];
+        if (idx < ND) continue;
+        plan[3 * (idx - ND) + s] = (uint16_t)(s * D + j++);
+      }
+  }
+}
+
+extern "C" int oai4g_cc_rx_plan(uint32_t D, uint16_t *plan)
+{
+  if (D == 0 || D > OAI4G_CC_NMAX || !plan) { set_err("cc_rx_plan: D %u (1..%d)", D, OAI4G_CC_NMAX); return -1; }
+  cc_rx_plan_h(D, plan);
+  return (int)(3 * D);
+}
+
+#define CC_REC 68u   /* drop-in record: 64 decoded bytes + the 4-byte trailer */
+/* one decode through the scratch buffer: e (e_bytes), the job, its plan, the PBCH Gold words */
+static int cc_decode_one(const char *who, const int8_t *e, size_t e_bytes, cc_job_t job, const uint16_t *plan,
+                         uint32_t n_plan, const uint32_t *gold, uint32_t n_gold, uint8_t quarter, bool raw,
+                         uint8_t rec[CC_REC], uint8_t *metrics)
+{
+  const size_t o_job = (e_bytes + 255) & ~(size_t)255, o_plan = o_job + 256, o_gold = o_plan + 2048, o_q = o_gold + 512,
+               o_rec = o_q + 256, o_met = o_rec + 256;
+  uint8_t *buf = scratch(o_met + 256);
+  if (!buf) { set_err("%s: scratch allocation failed", who); return -1; }
+  job.e_off = 0;
+  job.plan_off = 0;
+  HCK(hipMemcpyAsync(buf, e, e_bytes, hipMemcpyHostToDevice, g_scr.s), -1);
+  HCK(hipMemcpyAsync(buf + o_job, &job, sizeof(job), hipMemcpyHostToDevice, g_scr.s), -1);
+  if (n_plan) HCK(hipMemcpyAsync(buf + o_plan, plan, (size_t)n_plan * 2, hipMemcpyHostToDevice, g_scr.s), -1);
+  if (n_gold) HCK(hipMemcpyAsync(buf + o_gold, gold, (size_t)n_gold * 4, hipMemcpyHostToDevice, g_scr.s), -1);
+  HCK(hipMemcpyAsync(buf + o_q, &quarter, 1, hipMemcpyHostToDevice, g_scr.s), -1);
+  cc_args_t a;
+  memset(&a, 0, sizeof(a));
+  a.e = (const int8_t *)buf;
+  a.e_stride = 0;
+  a.jobs = (const cc_job_t *)(buf + o_job);
+  a.n_jobs = a.n_items = 1;
+  a.plan = (const uint16_t *)(buf + o_plan);
+  a.gold = n_gold ? (const uint32_t *)(buf + o_gold) : nullptr;
+  a.quarter = buf + o_q;
+  a.out = buf + o_rec;
+  a.out_stride = CC_REC;
+  a.metrics = metrics ? buf + o_met : nullptr;
+  a.raw = raw ? 1 : 0;
+  HCK(oai4g_launch_cc_decode(a, job.D, g_scr.s), -1);
+  HCK(hipMemcpyAsync(rec, buf + o_rec, CC_REC, hipMemcpyDeviceToHost, g_scr.s), -1);
+  if (metrics) HCK(hipMemcpyAsync(metrics, buf + o_met, 64, hipMemcpyDeviceToHost, g_scr.s), -1);
+  HCK(hipStreamSynchronize(g_scr.s), -1);
+  return 0;
+}
+
+static int viterbi_one(const char *who, const int8_t *y, uint16_t n, uint8_t rec[CC_REC], uint8_t *metrics)
+{
+  if (!y || n == 0 || n > OAI4G_CC_NMAX) { set_err("%s: n %u (1..%d)", who, n, OAI4G_CC_NMAX); return -1; }
+  NEED_INIT(-1);
+  cc_job_t job = {};
+  job.D = n;
+  return cc_decode_one(who, y, 3 * (size_t)n, job, nullptr, 0, nullptr, 0, 0, true, rec, metrics);
+}
+
+extern "C" int oai4g_phy_viterbi_lte(const int8_t *y, uint8_t *decoded_bytes, uint16_t n)
+{
+  uint8_t rec[CC_REC];
+  if (!decoded_bytes) { set_err("phy_viterbi_lte: null output"); return -1; }
+  if (viterbi_one("phy_viterbi_lte", y, n, rec, nullptr) != 0) return -1;
+  for (uint32_t i = 0; i < ((uint32_t)n + 7) >> 3; i++) decoded_bytes[i] = (uint8_t)(decoded_bytes[i] + rec[i]);   /* '+=' (:400) */
+  return rec[CC_REC - 2];
+}
+
+extern "C" int oai4g_diag_viterbi_lte(const int8_t *y, uint16_t n, uint8_t *decoded, uint8_t metrics[64],
+                                      uint8_t *start_state)
+{
+  uint8_t rec[CC_REC];
+  if (!decoded || !metrics || !start_state) { set_err("diag_viterbi_lte: null output"); return -1; }
+  if (viterbi_one("diag_viterbi_lte", y, n, rec, metrics) != 0) return -1;
+  memcpy(decoded, rec, ((size_t)n + 7) >> 3);
+  *start_state = rec[CC_REC - 1];
+  return rec[CC_REC - 2];
+}
+
+extern "C" int oai4g_dci_decoding_crc(uint8_t DCI_LENGTH, uint8_t aggregation_level, const int8_t *e,
+                                      uint8_t *decoded_output, uint16_t *crc)
+{
+  if (aggregation_level > 3) { set_err("dci_decoding: illegal aggregation_level %u", aggregation_level); return -1; }
+  if (DCI_LENGTH == 0 || DCI_LENGTH > 45) {   /* MAX_DCI_SIZE_BITS (dci.h:2979) sizes the reference's buffers */
+    set_err("dci_decoding: DCI_LENGTH %u (1..45)", DCI_LENGTH);
+    return -1;
+  }
+  if (!e || !decoded_output) { set_err("dci_decoding: null buffer"); return -1; }
+  NEED_INIT(-1);
+  const uint32_t D = (uint32_t)DCI_LENGTH + 16;
+  uint16_t plan[3 * 61];
+  cc_rx_plan_h(D, plan);
+  cc_job_t job = {};
+  job.E = (uint16_t)(72u << aggregation_level);
+  job.D = (uint16_t)D;
+  job.crc_bits = DCI_LENGTH;
+  uint8_t rec[CC_REC];
+  if (cc_decode_one("dci_decoding", e, job.E, job, plan, 3 * D, nullptr, 0, 0, false, rec, nullptr) != 0) return -1;
+  memset(decoded_output, 0, 2 + (D >> 3));                            /* :2477 */
+  for (uint32_t i = 0; i < (D + 7) >> 3; i++) decoded_output[i] = rec[i];
+  if (crc) *crc = (uint16_t)(rec[CC_REC - 4] | (rec[CC_REC - 3] << 8));
+  return 0;
+}
+
+extern "C" int oai4g_dci_decoding(uint8_t DCI_LENGTH, uint8_t aggregation_level, const int8_t *e, uint8_t *decoded_output)
+{
+  return oai4g_dci_decoding_crc(DCI_LENGTH, aggregation_level, e, decoded_output, nullptr);
+}
+
+/* lte_gold_generic words of c_init = Nid_cell over the PBCH's E soft bits (pbch_unscrambling, pbch.c:785) */
+static uint32_t pbch_gold_h(uint32_t Nid, uint32_t E, uint32_t w[60])
+{
+  uint32_t x1 = 1u + (1u << 31), x2 = Nid;
+  x2 = x2 ^ ((x2 ^ (x2 >> 1) ^ (x2 >> 2) ^ (x2 >> 3)) << 31);
+  for (int n = 1; n < 50; n++) gold_step_h(&x1, &x2);
+  const uint32_t nw = (E + 31) / 32;
+  for (uint32_t i = 0; i < nw; i++) {
+    gold_step_h(&x1, &x2);
+    w[i] = x1 ^ x2;
+  }
+  return nw;
+}
+
+extern "C" int oai4g_pbch_decode(const int8_t *llr, const oai4g_frame_parms_t *fp, uint8_t frame_mod4,
+                                 uint8_t decoded_output[3])
+{
+  if (!llr || !fp || !decoded_output || frame_mod4 > 3) { set_err("pbch_decode: frame_mod4 %u or a null argument", frame_mod4); return -1; }
+  NEED_INIT(-1);
+  const uint32_t E = fp->Ncp == 0 ? 1920 : 1728;
+  uint16_t plan[120];
+  uint32_t gold[60];
+  cc_rx_plan_h(40, plan);
+  const uint32_t nw = pbch_gold_h(fp->Nid_cell, E, gold);
+  cc_job_t job = {};
+  job.E = (uint16_t)E;
+  job.D = 40;
+  job.crc_bits = 24;
+  uint8_t rec[CC_REC];
+  if (cc_decode_one("pbch_decode", llr, E, job, plan, 120, gold, nw, frame_mod4, false, rec, nullptr) != 0) return -1;
+  for (int i = 0; i < 3; i++) decoded_output[2 - i] = rec[i];         /* pbch.c:1017 */
+  const uint32_t crc = rec[CC_REC - 4] | ((uint32_t)rec[CC_REC - 3] << 8);
+  set_err("");
+  return crc == 0 ? 1 : (crc == 0xFFFFu ? 2 : (crc == 0x5555u ? 4 : -1));
+}
+
+/* device constants of the batched PBCH decode, kept for the last (Nid_cell, E) */
+static std::mutex g_pbch_rx_mu;
+static uint8_t *g_pbch_rx_dev = nullptr;
+static uint32_t g_pbch_rx_key = 0xFFFFFFFFu;
+
+extern "C" int oai4g_pbch_decode_batch(const int8_t *d_llr, int n, const oai4g_frame_parms_t *fp,
+                                       const uint8_t *d_frame_mod4, uint8_t *d_out, void *stream)
+{
+  if (n < 0 || !fp || (n > 0 && (!d_llr || !d_frame_mod4 || !d_out))) { set_err("pbch_decode_batch: bad arguments"); return -1; }
+  NEED_INIT(-1);
+  if (n == 0) return 0;
+  const uint32_t E = fp->Ncp == 0 ? 1920 : 1728, key = ((uint32_t)fp->Nid_cell << 16) | E;
+  /* held until the launch is enqueued: another thread's cell may replace the constants only after a device
+   * synchronisation that then covers this launch */
+  std::lock_guard<std::mutex> lk(g_pbch_rx_mu);
+  {
+    if (!g_pbch_rx_dev) HCK(hipMalloc(&g_pbch_rx_dev, 1024), -1);
+    if (g_pbch_rx_key != key) {
+      uint8_t h[1024] = {};
+      cc_job_t job = {};
+      job.E = (uint16_t)E;
+      job.D = 40;
+      job.crc_bits = 24;
+      memcpy(h, &job, sizeof(job));
+      cc_rx_plan_h(40, (uint16_t *)(h + 256));
+      pbch_gold_h(fp->Nid_cell, E, (uint32_t *)(h + 512));
+      HCK(hipDeviceSynchronize(), -1);                                /* earlier launches may still read the old constants */
+      HCK(hipMemcpy(g_pbch_rx_dev, h, sizeof(h), hipMemcpyHostToDevice), -1);
+      g_pbch_rx_key = key;
+    }
+  }
+  cc_args_t a;
+  memset(&a, 0, sizeof(a));
+  a.e = d_llr;
+  a.e_stride = E;
+  a.jobs = (const cc_job_t *)g_pbch_rx_dev;
+  a.n_jobs = 1;
+  a.n_items = (uint32_t)n;
+  a.plan = (const uint16_t *)(g_pbch_rx_dev + 256);
+  a.gold = (const uint32_t *)(g_pbch_rx_dev + 512);
+  a.quarter = d_frame_mod4;
+  a.out = d_out;
+  a.out_stride = 4;
+  a.pbch_out = 1;
+  HCK(oai4g_launch_cc_decode(a, 40, (hipStream_t)stream), -1);
+  return 0;
+}
+
+/* ------------------------------------------------------------------------------------------
+ * PDCCH receive: the soft-bit gather of rx_pdcch after compensation (dci.c:1852-1897), the DCI
+ * search of dci_decoding_procedure0 (:2547-2786) and its batched form.
+ * ---------------------------------------------------------------------------------------- */
+static int pdcch_rx_geometry_ok(const char *who, const oai4g_frame_parms_t *fp, uint32_t subframe, uint8_t npd)
+{
+  if (!fp) { set_err("%s: null frame parameters", who); return 0; }
+  if (fp->nb_antennas_tx_eNB == 4) { set_err("%s: 4 TX ports are not defined by the reference's demapping (dci.c:420)", who); return 0; }
+  if (fp->phich_duration != 0 || fp->Ncp != 0) {
+    set_err("%s: only the normal cyclic prefix with normal PHICH duration is supported", who);
+    return 0;
+  }
+  if (subframe > 9 || npd < 1 || npd > 3 || oai4g_get_nquad(npd, fp, 1) == 0) {
+    set_err("%s: subframe %u / num_pdcch_symbols %u / no PDCCH geometry for N_RB_DL %u", who, subframe, npd, fp->N_RB_DL);
+    return 0;
+  }
+  return 1;
+}
+
+/* tab[i], soft bit i of e_rx: int16 index into rxdataF_comp | negate << 31, or OAI4G_PDCCH_NONE */
+static int pdcch_soft_table_h(const oai4g_frame_parms_t *fp, uint8_t subframe, uint8_t npd, std::vector<uint32_t> &tab)
+{
+  static const uint8_t bitrev_cc[32] = {1, 17, 9, 25, 5, 21, 13, 29, 3, 19, 11, 27, 7, 23, 15, 31,
+                                        0, 16, 8, 24, 4, 20, 12, 28, 2, 18, 10, 26, 6, 22, 14, 30};
+  const uint8_t mi = oai4g_get_mi(fp, subframe);
+  const uint32_t Mquad = oai4g_get_nquad(npd, fp, mi), NRE = (uint32_t)fp->N_RB_DL * 12;
+  const int Msymb = ((2 * 33 + 22) * 72) / 2;
+  int Msymb2;
+  switch (fp->N_RB_DL) {
+  case 100: Msymb2 = Msymb; break;
+  case 50: Msymb2 = Msymb >> 1; break;
+  case 6: Msymb2 = Msymb * 6 / 100; break;
+  default: Msymb2 = Msymb >> 2; break;
+  }
+  uint16_t pcf[4], phr[56][3];
+  uint8_t fi;
+  memset(phr, 0, sizeof(phr));
+  pcfich_regs(fp, pcf, &fi);
+  oai4g_generate_phich_reg_mapping(fp, phr);
+  const uint32_t ng = phich_ngroup(fp);
+  auto taken = [&](uint32_t kp, uint32_t lp) {           /* check_phich_reg (:62-121), normal prefix */
+    if (lp > 0) return false;
+    const uint32_t m = kp / 6;
+    if (m == pcf[0] || m == pcf[1] || m == pcf[2] || m == pcf[3]) return true;
+    if (mi > 0)
+      for (uint32_t i = 0; i < ng && i < 56; i++)
+        if (m == phr[i][0] || m == phr[i][1] || m == phr[i][2]) return true;
+    return false;
+  };
+  /* pdcch_demapping (:342-446): wbar[mprime] <- llr RE index; its break leaves the inner loop only */
+  std::vector<uint32_t> wbar;
+  uint32_t re_offset = 0, re_offset0 = 0;
+  for (uint32_t kp = 0; kp < NRE; kp++) {
+    for (uint32_t lp = 0; lp < npd; lp++) {
+      const uint32_t so = NRE * lp;
+      if (taken(kp, lp)) {
+        if (lp == 0 && kp % 6 == 0) re_offset0 += 4;
+      } else if (lp == 0) {
+        if (kp % 12 == 0 || kp % 12 == 6)
+          for (uint32_t i = 0; i < 4; i++) wbar.push_back(so + re_offset0++);
+      } else if (kp % 12 == 0 || kp % 12 == 4 || kp % 12 == 8) {
+        for (uint32_t i = 0; i < 4; i++) wbar.push_back(so + re_offset + i);
+      }
+      if (wbar.size() >= (size_t)Msymb2) break;
+    }
+    re_offset++;
+  }
+  /* pdcch_deinterleaving (:449-549): wtemp[(i + Nid) % Mquad] = wbar[i]; z[perm[k]] = wtemp[k] */
+  std::vector<uint32_t> z((size_t)4 * Mquad, OAI4G_PDCCH_NONE);
+  const uint32_t RCC = (Mquad + 31) >> 5, ND = (RCC << 5) - Mquad;
+  uint32_t k = 0;
+  for (uint32_t col = 0; col < 32; col++)
+    for (uint32_t row = 0, idx = bitrev_cc[col]; row < RCC; row++, idx += 32)
+      if (idx >= ND) {
+        const uint32_t i = (k + Mquad - fp->Nid_cell % Mquad) % Mquad;   /* the wbar quadruplet behind wtemp[k] */
+        for (uint32_t j = 0; j < 4; j++)
+          if ((size_t)4 * i + j < wbar.size()) z[(size_t)4 * (idx - ND) + j] = wbar[(size_t)4 * i + j];
+        k++;
+      }
+  /* pdcch_unscrambling (:1932-1961) over 72 nCCE soft bits */
+  const uint32_t n = 8 * Mquad, nuns = 72u * (Mquad / 9);
+  uint32_t x1 = 1u + (1u << 31), x2 = ((uint32_t)subframe << 9) + fp->Nid_cell, sw = 0;
+  x2 = x2 ^ ((x2 ^ (x2 >> 1) ^ (x2 >> 2) ^ (x2 >> 3)) << 31);
+  for (int q = 1; q < 50; q++) gold_step_h(&x1, &x2);
+  tab.assign(n, OAI4G_PDCCH_NONE);
+  for (uint32_t i = 0; i < n; i++) {
+    if ((i & 31) == 0) {
+      gold_step_h(&x1, &x2);
+      sw = x1 ^ x2;
+    }
+    const uint32_t re = z[i >> 1];
+    if (re == OAI4G_PDCCH_NONE) continue;
+    const uint32_t neg = (i < nuns && ((sw >> (i & 31)) & 1u) == 0) ? 1u : 0u;
+    tab[i] = (2 * re + (i & 1)) | (neg << 31);
+  }
+  return (int)n;
+}
+
+extern "C" int oai4g_pdcch_soft_bit_table(const oai4g_frame_parms_t *fp, uint8_t subframe, uint8_t npd, uint32_t *table,
+                                          uint32_t cap)
+{
+  if (!pdcch_rx_geometry_ok("pdcch_soft_bit_table", fp, subframe, npd)) return -1;
+  std::vector<uint32_t> tab;
+  const int n = pdcch_soft_table_h(fp, subframe, npd, tab);
+  if (!table || (uint32_t)n > cap) { set_err("pdcch_soft_bit_table: room for %u of %d entries", cap, n); return -1; }
+  memcpy(table, tab.data(), (size_t)n * 4);
+  return n;
+}
+
+extern "C" int oai4g_pdcch_soft_bits(const int32_t *rxdataF_comp, const oai4g_frame_parms_t *fp, uint8_t subframe,
+                                     uint8_t npd, int8_t *e_rx)
+{
+  if (!pdcch_rx_geometry_ok("pdcch_soft_bits", fp, subframe, npd)) return -1;
+  if (!rxdataF_comp || !e_rx) { set_err("pdcch_soft_bits: null buffer"); return -1; }
+  NEED_INIT(-1);
+  std::vector<uint32_t> tab;
+  const int n = pdcch_soft_table_h(fp, subframe, npd, tab);
+  const size_t cb = (size_t)npd * fp->N_RB_DL * 12 * 4, o_tab = (cb + 255) & ~(size_t)255,
+               o_e = o_tab + (((size_t)n * 4 + 255) & ~(size_t)255);
+  uint8_t *buf = scratch(o_e + (size_t)n + 256);
+  if (!buf) { set_err("pdcch_soft_bits: scratch allocation failed"); return -1; }
+  HCK(hipMemcpyAsync(buf, rxdataF_comp, cb, hipMemcpyHostToDevice, g_scr.s), -1);
+  HCK(hipMemcpyAsync(buf + o_tab, tab.data(), (size_t)n * 4, hipMemcpyHostToDevice, g_scr.s), -1);
+  HCK(oai4g_launch_pdcch_soft((const int16_t *)buf, (const uint32_t *)(buf + o_tab), (uint32_t)n, (int8_t *)(buf + o_e), g_scr.s), -1);
+  HCK(hipMemcpyAsync(e_rx, buf + o_e, (size_t)n, hipMemcpyDeviceToHost, g_scr.s), -1);
+  HCK(hipStreamSynchronize(g_scr.s), -1);
+  return n;
+}
+
+/* the candidates of one dci_decoding_procedure0 call (:2576-2624) */
+static void pdcch_candidates_h(const oai4g_frame_parms_t *fp, uint8_t npd, uint8_t mi, uint8_t subframe, uint16_t crnti,
+                               int do_common, uint8_t L, std::vector<uint16_t> &cce)
+{
+  const uint32_t nCCE = oai4g_get_nCCE(npd, fp, mi), L2 = 1u << L;
+  if (nCCE > oai4g_get_nCCE(3, fp, 1) || nCCE < L2) return;
+  uint32_t Yk = 0, nb;
+  if (do_common == 1) {
+    nb = L2 == 4 ? 4 : 2;
+  } else {
+    Yk = crnti;
+    for (uint32_t i = 0; i <= subframe; i++) Yk = (Yk * 39827u) % 65537u;
+    Yk %= nCCE / L2;
+    nb = L2 <= 2 ? 6 : 2;
+  }
+  if (nb * L2 > nCCE) nb = nCCE / L2;
+  for (uint32_t m = 0; m < nb; m++) cce.push_back((uint16_t)(((Yk + m) % (nCCE / L2)) * L2));
+}
+
+extern "C" int oai4g_pdcch_candidates(const oai4g_frame_parms_t *fp, uint8_t npd, uint8_t subframe, uint16_t crnti,
+                                      int do_common, uint8_t L, uint16_t *cce, int cap)
+{
+  if (!pdcch_rx_geometry_ok("pdcch_candidates", fp, subframe, npd)) return -1;
+  if (L > 3) { set_err("pdcch_candidates: illegal aggregation level L %u", L); return -1; }
+  std::vector<uint16_t> v;
+  pdcch_candidates_h(fp, npd, oai4g_get_mi(fp, subframe), subframe, crnti, do_common, L, v);
+  for (int i = 0; i < cap && i < (int)v.size() && cce; i++) cce[i] = v[i];
+  return (int)v.size();
+}
+
+static int pdcch_plan_ok(const char *who, uint8_t L, uint8_t sizeof_bits, uint8_t sizeof_bytes)
+{
+  if (L > 3) { set_err("%s: illegal aggregation level L %u", who, L); return 0; }
+  if (sizeof_bits == 0 || sizeof_bits > 45 || sizeof_bytes == 0 || sizeof_bytes > 8) {
+    set_err("%s: DCI_LENGTH %u (1..45), %u bytes (1..8)", who, sizeof_bits, sizeof_bytes);
+    return 0;
+  }
+  return 1;
+}
+
+extern "C" int oai4g_dci_decoding_procedure0(const int8_t *e_rx, uint8_t npd, uint16_t crnti, uint8_t *nCCE, int do_common,
+                                             uint8_t subframe, oai4g_dci_alloc_t *dci_alloc, const oai4g_frame_parms_t *fp,
+                                             uint8_t mi, uint16_t si_rnti, uint16_t ra_rnti, uint8_t L, uint8_t format_si,
+                                             uint8_t format_ra, uint8_t format_c, uint8_t sizeof_bits, uint8_t sizeof_bytes,
+                                             uint8_t *dci_cnt, uint8_t *format0_found, uint8_t *format_c_found,
+                                             uint32_t *CCEmap0, uint32_t *CCEmap1, uint32_t *CCEmap2)
+{
+  if (!pdcch_plan_ok("dci_decoding_procedure0", L, sizeof_bits, sizeof_bytes)) return -1;
+  if (!pdcch_rx_geometry_ok("dci_decoding_procedure0", fp, subframe, npd)) return -1;
+  if (!e_rx || !dci_alloc || !dci_cnt || !format0_found || !format_c_found || !CCEmap0 || !CCEmap1 || !CCEmap2) {
+    set_err("dci_decoding_procedure0: null argument");
+    return -1;
+  }
+  NEED_INIT(-1);
+  std::vector<uint16_t> cce;
+  pdcch_candidates_h(fp, npd, mi, subframe, crnti, do_common, L, cce);
+  const uint32_t nc = (uint32_t)cce.size(), D = (uint32_t)sizeof_bits + 16;
+  if (nc == 0) return 0;
+  const size_t eb = (size_t)72 * oai4g_get_nCCE(npd, fp, mi);
+  std::vector<cc_job_t> jobs(nc);
+  for (uint32_t c = 0; c < nc; c++) {
+    jobs[c] = cc_job_t{};
+    jobs[c].e_off = 72u * cce[c];
+    jobs[c].E = (uint16_t)(72u << L);
+    jobs[c].D = (uint16_t)D;
+    jobs[c].crc_bits = sizeof_bits;
+  }
+  uint16_t plan[3 * 61];
+  cc_rx_plan_h(D, plan);
+  const size_t o_job = (eb + 255) & ~(size_t)255, o_plan = o_job + 1024, o_rec = o_plan + 512;
+  uint8_t *buf = scratch(o_rec + 1024);
+  if (!buf) { set_err("dci_decoding_procedure0: scratch allocation failed"); return -1; }
+  uint8_t rec[16 * OAI4G_PDCCH_REC];
+  HCK(hipMemcpyAsync(buf, e_rx, eb, hipMemcpyHostToDevice, g_scr.s), -1);
+  HCK(hipMemcpyAsync(buf + o_job, jobs.data(), nc * sizeof(cc_job_t), hipMemcpyHostToDevice, g_scr.s), -1);
+  HCK(hipMemcpyAsync(buf + o_plan, plan, (size_t)3 * D * 2, hipMemcpyHostToDevice, g_scr.s), -1);
+  cc_args_t a;
+  memset(&a, 0, sizeof(a));
+  a.e = (const int8_t *)buf;
+  a.jobs = (const cc_job_t *)(buf + o_job);
+  a.n_jobs = nc;
+  a.n_items = 1;
+  a.plan = (const uint16_t *)(buf + o_plan);
+  a.out = buf + o_rec;
+  a.out_stride = OAI4G_PDCCH_REC;
+  HCK(oai4g_launch_cc_decode(a, D, g_scr.s), -1);
+  HCK(hipMemcpyAsync(rec, buf + o_rec, (size_t)nc * OAI4G_PDCCH_REC, hipMemcpyDeviceToHost, g_scr.s), -1);
+  HCK(hipStreamSynchronize(g_scr.s), -1);
+  pdcch_state_t st = {};
+  st.map[0] = *CCEmap0;
+  st.map[1] = *CCEmap1;
+  st.map[2] = *CCEmap2;
+  st.dci_cnt = *dci_cnt;
+  st.format0_found = *format0_found;
+  st.format_c_found = *format_c_found;
+  st.nCCE = -1;
+  const oai4g_pdcch_plan_t pl = {(uint8_t)do_common, L, sizeof_bits, sizeof_bytes, format_si, format_ra, format_c, 0};
+  for (uint32_t c = 0; c < nc; c++) {
+    const uint8_t *r = rec + (size_t)c * OAI4G_PDCCH_REC;
+    oai4g_pdcch_resolve(st, pl, cce[c], r, r[OAI4G_PDCCH_REC - 4] | ((uint32_t)r[OAI4G_PDCCH_REC - 3] << 8), crnti, si_rnti,
+                        ra_rnti, dci_alloc, 255);
+  }
+  *CCEmap0 = st.map[0];
+  *CCEmap1 = st.map[1];
+  *CCEmap2 = st.map[2];
+  *dci_cnt = st.dci_cnt;
+  *format0_found = st.format0_found;
+  *format_c_found = st.format_c_found;
+  if (st.nCCE >= 0 && nCCE) *nCCE = (uint8_t)st.nCCE;
+  return 0;
+}
+
+struct oai4g_pdcch_rx_config {
+  oai4g_frame_parms_t fp;
+  uint8_t npd;
+  uint16_t crnti, si_rnti, ra_rnti;
+  std::vector<oai4g_pdcch_plan_t> plan;
+  std::vector<pdcch_cand_t> cands[10];
+  uint32_t n_jobs = 0, tab_stride = 0;
+  uint8_t *dev = nullptr;            /* tables, jobs, candidates, counts, plans, receive plans */
+  size_t o_jobs = 0, o_cands = 0, o_ncand = 0, o_plans = 0, o_ccplan = 0;
+  uint8_t *d_rec = nullptr;
+  size_t rec_cap = 0;
+};
+
+extern "C" void oai4g_pdcch_rx_config_destroy(oai4g_pdcch_rx_config_t *cfg)
+{
+  if (!cfg) return;
+  if (cfg->dev) hipFree(cfg->dev);
+  if (cfg->d_rec) hipFree(cfg->d_rec);
+  delete cfg;
+}
+
+extern "C" oai4g_pdcch_rx_config_t *oai4g_pdcch_rx_config_create(const oai4g_frame_parms_t *fp, uint8_t npd, uint16_t crnti,
+                                                                 uint16_t si_rnti, uint16_t ra_rnti,
+                                                                 const oai4g_pdcch_plan_t *plan, int n_plan)
+{
+  if (!pdcch_rx_geometry_ok("pdcch_rx_config_create", fp, 0, npd)) return nullptr;
+  if (!plan || n_plan < 1 || n_plan > 64) { set_err("pdcch_rx_config_create: %d plan entries (1..64)", n_plan); return nullptr; }
+  for (int i = 0; i < n_plan; i++)
+    if (!pdcch_plan_ok("pdcch_rx_config_create", plan[i].L, plan[i].sizeof_bits, plan[i].sizeof_bytes)) return nullptr;
+  NEED_INIT(nullptr);
+  std::unique_ptr<oai4g_pdcch_rx_config_t, void (*)(oai4g_pdcch_rx_config_t *)> cfg(new oai4g_pdcch_rx_config_t,
+                                                                                    oai4g_pdcch_rx_config_destroy);
+  cfg->fp = *fp;
+  cfg->npd = npd;
+  cfg->crnti = crnti;
+  cfg->si_rnti = si_rnti;
+  cfg->ra_rnti = ra_rnti;
+  cfg->plan.assign(plan, plan + n_plan);
+  /* one receive plan per distinct D, in order of first use */
+  std::vector<uint32_t> Ds;
+  std::vector<uint16_t> ccplan;
+  std::vector<uint32_t> ccoff(n_plan);
+  for (int i = 0; i < n_plan; i++) {
+    const uint32_t D = (uint32_t)plan[i].sizeof_bits + 16;
+    size_t j = 0, off = 0;
+    for (; j < Ds.size() && Ds[j] != D; j++) off += 3 * Ds[j];
+    if (j == Ds.size()) {
+      Ds.push_back(D);
+      ccplan.resize(off + 3 * D);
+      cc_rx_plan_h(D, ccplan.data() + off);
+    }
+    ccoff[i] = (uint32_t)off;
+  }
+  if (ccplan.size() > 0xFFFF) { set_err("pdcch_rx_config_create: too many distinct DCI sizes"); return nullptr; }
+  std::vector<uint32_t> tabs[10];
+  for (uint8_t sf = 0; sf < 10; sf++) {
+    pdcch_soft_table_h(fp, sf, npd, tabs[sf]);
+    if (tabs[sf].size() > cfg->tab_stride) cfg->tab_stride = (uint32_t)tabs[sf].size();
+    const uint8_t mi = oai4g_get_mi(fp, sf);
+    for (int i = 0; i < n_plan; i++) {
+      std::vector<uint16_t> cce;
+      pdcch_candidates_h(fp, npd, mi, sf, crnti, plan[i].do_common, plan[i].L, cce);
+      for (size_t c = 0; c < cce.size(); c++) cfg->cands[sf].push_back(pdcch_cand_t{cce[c], (uint8_t)i, (uint8_t)(c == 0)});
+    }
+    if (cfg->cands[sf].size() > cfg->n_jobs) cfg->n_jobs = (uint32_t)cfg->cands[sf].size();
+  }
+  if (cfg->n_jobs == 0) cfg->n_jobs = 1;
+  const uint32_t nj = cfg->n_jobs;
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  cfg->o_jobs = up((size_t)10 * cfg->tab_stride * 4);
+  cfg->o_cands = cfg->o_jobs + up((size_t)10 * nj * sizeof(cc_job_t));
+  cfg->o_ncand = cfg->o_cands + up((size_t)10 * nj * sizeof(pdcch_cand_t));
+  cfg->o_plans = cfg->o_ncand + 256;
+  cfg->o_ccplan = cfg->o_plans + up((size_t)n_plan * sizeof(oai4g_pdcch_plan_t));
+  const size_t total = cfg->o_ccplan + up(ccplan.size() * 2);
+  std::vector<uint8_t> h(total, 0);
+  for (uint32_t sf = 0; sf < 10; sf++) {
+    uint32_t *t = (uint32_t *)h.data() + (size_t)sf * cfg->tab_stride;
+    for (uint32_t i = 0; i < cfg->tab_stride; i++) t[i] = i < tabs[sf].size() ? tabs[sf][i] : OAI4G_PDCCH_NONE;
+    cc_job_t *jobs = (cc_job_t *)(h.data() + cfg->o_jobs) + (size_t)sf * nj;
+    pdcch_cand_t *cd = (pdcch_cand_t *)(h.data() + cfg->o_cands) + (size_t)sf * nj;
+    for (uint32_t c = 0; c < cfg->cands[sf].size(); c++) {
+      const pdcch_cand_t &k = cfg->cands[sf][c];
+      const oai4g_pdcch_plan_t &pl = plan[k.plan];
+      if (72u * (k.cce + (1u << pl.L)) > tabs[sf].size()) { set_err("pdcch_rx_config_create: candidate outside the soft bits"); return nullptr; }
+      jobs[c].e_off = 72u * k.cce;
+      jobs[c].E = (uint16_t)(72u << pl.L);
+      jobs[c].D = (uint16_t)(pl.sizeof_bits + 16);
+      jobs[c].plan_off = (uint16_t)ccoff[k.plan];
+      jobs[c].crc_bits = pl.sizeof_bits;
+      cd[c] = k;
+    }
+    ((uint32_t *)(h.data() + cfg->o_ncand))[sf] = (uint32_t)cfg->cands[sf].size();   /* the other jobs have D = 0: no decode */
+  }
+  memcpy(h.data() + cfg->o_plans, plan, (size_t)n_plan * sizeof(oai4g_pdcch_plan_t));
+  memcpy(h.data() + cfg->o_ccplan, ccplan.data(), ccplan.size() * 2);
+  HCK(hipMalloc(&cfg->dev, total), nullptr);
+  HCK(hipMemcpy(cfg->dev, h.data(), total, hipMemcpyHostToDevice), nullptr);
+  return cfg.release();
+}
+
+extern "C" int oai4g_pdcch_rx_candidates(const oai4g_pdcch_rx_config_t *cfg, uint8_t subframe, uint16_t *cce,
+                                         uint8_t *plan_entry, int cap)
+{
+  if (!cfg || subframe > 9) { set_err("pdcch_rx_candidates: bad arguments"); return -1; }
+  const auto &v = cfg->cands[subframe];
+  for (int i = 0; i < cap && i < (int)v.size(); i++) {
+    if (cce) cce[i] = v[i].cce;
+    if (plan_entry) plan_entry[i] = v[i].plan;
+  }
+  return (int)v.size();
+}
+
+extern "C" int oai4g_pdcch_rx_batch(oai4g_pdcch_rx_config_t *cfg, const int32_t *d_comp, int n_sf, int first_subframe,
+                                    oai4g_pdcch_rx_result_t *d_out, void *stream)
+{
+  if (!cfg || n_sf < 0 || first_subframe < 0 || first_subframe > 9 || (n_sf > 0 && (!d_comp || !d_out))) {
+    set_err("pdcch_rx_batch: bad arguments");
+    return -1;
+  }
+  NEED_INIT(-1);
+  if (n_sf == 0) return 0;
+  const size_t need = (size_t)n_sf * cfg->n_jobs * OAI4G_PDCCH_REC;
+  if (need > cfg->rec_cap) {
+    HCK(hipDeviceSynchronize(), -1);
+    if (cfg->d_rec) hipFree(cfg->d_rec);
+    cfg->d_rec = nullptr;
+    cfg->rec_cap = 0;
+    HCK(hipMalloc(&cfg->d_rec, need), -1);
+    cfg->rec_cap = need;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  HCK(hipMemsetAsync(cfg->d_rec, 0, need, s), -1);
+  HCK(hipMemsetAsync(d_out, 0, (size_t)n_sf * sizeof(oai4g_pdcch_rx_result_t), s), -1);   /* unwritten fields and slots read as 0 */
+  cc_args_t a;
+  memset(&a, 0, sizeof(a));
+  a.jobs = (const cc_job_t *)(cfg->dev + cfg->o_jobs);
+  a.n_jobs = cfg->n_jobs;
+  a.n_items = (uint32_t)n_sf;
+  a.plan = (const uint16_t *)(cfg->dev + cfg->o_ccplan);
+  a.out = cfg->d_rec;
+  a.out_stride = OAI4G_PDCCH_REC;
+  a.tab = (const uint32_t *)cfg->dev;
+  a.tab_stride = cfg->tab_stride;
+  a.comp = (const int16_t *)d_comp;
+  a.comp_stride = (size_t)cfg->npd * cfg->fp.N_RB_DL * 12 * 2;
+  a.first_row = (uint32_t)first_subframe;
+  HCK(oai4g_launch_cc_decode(a, 61, s), -1);
+  pdcch_resolve_args_t r;
+  memset(&r, 0, sizeof(r));
+  r.rec = cfg->d_rec;
+  r.cands = (const pdcch_cand_t *)(cfg->dev + cfg->o_cands);
+  r.n_cand = (const uint32_t *)(cfg->dev + cfg->o_ncand);
+  r.plans = (const oai4g_pdcch_plan_t *)(cfg->dev + cfg->o_plans);
+  r.n_jobs = cfg->n_jobs;
+  r.n_sf = (uint32_t)n_sf;
+  r.first_row = (uint32_t)first_subframe;
+  r.crnti = cfg->crnti;
+  r.si_rnti = cfg->si_rnti;
+  r.ra_rnti = cfg->ra_rnti;
+  r.out = d_out;
+  HCK(oai4g_launch_pdcch_resolve(r, s), -1);
+  return 0;
+}

@@ -479,6 +479,124 @@ struct chest_dev_t {
   int16_t filt[2][8][24];         /* fl, f2l2, f, f2, fr, f2r2, f_dc, f2_dc (filt96_32.h) for k[0] / k[1] */
   uint32_t gold[20][2][14];       /* lte_gold_table */
 };
+/* UE control decoding (oai4g_ctrl_rx.hip: k_cc_decode), one wave per tail-biting decode.  A launch
+ * decodes n_items x n_jobs: batch item i (a subframe, a PBCH) has its soft bits at e + i e_stride, job j
+ * (a DCI candidate) starts e_off into them. */
+struct cc_job_t {
+  uint32_t e_off;
+  uint16_t E;           /* soft bits summed: 72 << L, pbch_E (unused in raw mode) */
+  uint16_t D;           /* trellis steps */
+  uint16_t plan_off;    /* plan[plan_off + 3 i + s]: first e index of d^(s)_i (oai4g_cc_rx_plan) */
+  uint16_t crc_bits;    /* payload bits in front of the CRC16; 0: no CRC */
+};
+struct cc_args_t {
+  const int8_t *e;
+  size_t e_stride;
+  const cc_job_t *jobs;
+  uint32_t n_jobs, n_items;
+  const uint16_t *plan;
+  const uint32_t *gold;     /* PBCH: Gold words of c_init = Nid_cell, else null */
+  const uint8_t *quarter;   /* PBCH: frame_mod4 of every item */
+  uint8_t *out;             /* per decode out_stride bytes: the decoded bytes, and in the last four
+                               crc16 ^ received CRC (little endian), the clamp flag, the start state */
+  uint32_t out_stride;
+  uint8_t *metrics;         /* null, or 64 final path metrics per decode */
+  uint32_t raw;             /* 1: e holds the 3 D Viterbi inputs themselves (phy_viterbi_lte) */
+  uint32_t pbch_out;        /* 1: the record is 4 bytes, the reversed MIB and the antenna count (0xFF: none) */
+  /* PDCCH batch: the soft bits come straight from the compensated symbols through the gather table of
+   * the item's subframe index (first_row + item) mod 10, and the jobs are that row's candidates */
+  const uint32_t *tab;      /* null, or [10][tab_stride]: per soft bit the int16 index into the item's comp | negate << 31 */
+  uint32_t tab_stride;
+  const int16_t *comp;      /* [n_items][comp_stride] */
+  size_t comp_stride;
+  uint32_t first_row;
+};
+#define OAI4G_PDCCH_NONE 0xFFFFFFFFu
+/* pdcch_llr (dci.c:603) + pdcch_unscrambling (:1932) of one soft bit: clip to [-32, 31], negate where the Gold bit is 0 */
+static inline __host__ __device__ int8_t oai4g_pdcch_soft(const int16_t *comp, uint32_t t)
+{
+  if (t == OAI4G_PDCCH_NONE) return 0;
+  const int v = comp[t & 0x7FFFFFFFu];
+  const int c = v > 31 ? 31 : (v < -32 ? -32 : v);
+  return (int8_t)((t >> 31) ? -c : c);
+}
+hipError_t oai4g_launch_pdcch_soft(const int16_t *d_comp, const uint32_t *d_tab, uint32_t n, int8_t *d_e, hipStream_t s);
+
+/* dci_decoding_procedure0's rules (dci.c:2661-2784) on one decoded candidate, shared by the host drop-in
+ * and the batch's second stage */
+typedef oai4g_pdcch_plan_t pdcch_plan_t;   /* one dci_decoding_procedure0 call */
+struct pdcch_cand_t {
+  uint16_t cce;           /* CCEind */
+  uint8_t plan;           /* its plan entry */
+  uint8_t first;          /* 1: the first candidate of its plan entry */
+};
+struct pdcch_state_t {
+  uint32_t map[3];        /* CCEmap0..2 */
+  uint8_t dci_cnt, format0_found, format_c_found;
+  uint8_t overflow;       /* 1: a match found no room in dci_alloc and was dropped */
+  int32_t nCCE;           /* lte_ue_pdcch_vars->nCCE[subframe]; untouched when nothing stores it */
+};
+#define OAI4G_PDCCH_REC 16u   /* batch record: 8 decoded bytes, 4 spare, the 4-byte trailer */
+static inline __host__ __device__ void oai4g_pdcch_resolve(pdcch_state_t &st, const pdcch_plan_t &pl, uint32_t cce,
+                                                           const uint8_t *out, uint32_t crc, uint32_t crnti, uint32_t si_rnti,
+                                                           uint32_t ra_rnti, oai4g_dci_alloc_t *alloc, uint32_t cap)
+{
+  const uint32_t mask = ((1u << (1u << pl.L)) - 1u) << (cce & 31u);
+  uint32_t &m = st.map[cce >> 5];
+  if (m & mask) return;                                                /* a CCE is taken: skipped (:2665) */
+  if (!((pl.L > 1 && (crc == si_rnti || crc == ra_rnti)) || crc == crnti)) return;
+  if (st.dci_cnt >= cap) {                                             /* no room left: the match only marks its CCEs */
+    st.overflow = 1;
+    m |= mask;
+    return;
+  }
+  oai4g_dci_alloc_t &d = alloc[st.dci_cnt];                            /* filled before acceptance is known */
+  d.dci_length = pl.sizeof_bits;
+  d.rnti = (uint16_t)crc;
+  d.L = pl.L;
+  d.nCCE = (int32_t)cce;
+  const int nb = pl.sizeof_bytes <= 4 ? 4 : 8;
+  for (int i = 0; i < nb; i++) d.dci_pdu[nb - 1 - i] = out[i];
+  if (crc == si_rnti) {
+    d.format = pl.format_si;
+    st.dci_cnt++;
+  } else if (crc == ra_rnti) {
+    d.format = pl.format_ra;
+    st.nCCE = (int32_t)cce;
+    st.dci_cnt++;
+  } else if (crc == crnti) {
+    if (pl.format_c == 0 && (out[0] & 0x80) == 0) {                    /* format 0 or 1A by the first bit (:2730) */
+      if (st.format0_found == 0) {
+        d.format = 0;
+        st.format0_found = 1;
+        st.dci_cnt++;
+        st.nCCE = (int32_t)cce;
+      }
+    } else if (pl.format_c == 0) {
+      d.format = 2;                                                    /* format1A */
+      st.dci_cnt++;
+      st.nCCE = (int32_t)cce;
+    } else if (st.format_c_found == 0) {
+      d.format = pl.format_c;
+      st.dci_cnt++;
+      st.format_c_found = 1;
+      st.nCCE = (int32_t)cce;
+    }
+  }
+  m |= mask;                                                           /* also when the counter did not advance */
+}
+struct pdcch_resolve_args_t {
+  const uint8_t *rec;          /* [n_sf][n_jobs][OAI4G_PDCCH_REC] */
+  const pdcch_cand_t *cands;   /* [10][n_jobs] */
+  const uint32_t *n_cand;      /* [10] */
+  const pdcch_plan_t *plans;
+  uint32_t n_jobs, n_sf, first_row;
+  uint32_t crnti, si_rnti, ra_rnti;
+  oai4g_pdcch_rx_result_t *out;
+};
+hipError_t oai4g_launch_pdcch_resolve(const pdcch_resolve_args_t &a, hipStream_t s);
+#define OAI4G_CC_NMAX 512
+hipError_t oai4g_launch_cc_decode(const cc_args_t &a, uint32_t nmax, hipStream_t s);
 void oai4g_set_error(const char *fmt, ...);
 /* binds the calling thread to the device the library was initialised on (hipSetDevice is per thread) */
 int oai4g_bind_thread(void);

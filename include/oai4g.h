@@ -386,6 +386,55 @@ int oai4g_pdcch_rx_candidates(const oai4g_pdcch_rx_config_t *cfg, uint8_t subfra
  * `stream`.  Returns 0 or -1. */
 int oai4g_pdcch_rx_batch(oai4g_pdcch_rx_config_t *cfg, const int32_t *d_comp, int n_sf, int first_subframe,
                          oai4g_pdcch_rx_result_t *d_out, void *stream);
+/* The same search behind oai4g_pdcch_front_batch: d_comp [n_sf][3 * 12 * N_RB_DL], d_cfi [n_sf] the count
+ * rx_pcfich found for each subframe (device; it never visits the host).  cfg[n - 1] is the configuration of
+ * n symbols (same frame, RNTIs and plan); subframe i, of index (first_subframe + i * subframe_step) mod 10,
+ * gets what oai4g_pdcch_rx_batch gives with cfg[d_cfi[i] - 1] on its first d_cfi[i] * 12 * N_RB_DL words (a
+ * count outside 1..3 finds nothing).  The records live in cfg[2].  Asynchronous on `stream`.  Returns 0 or -1. */
+int oai4g_pdcch_rx_batch_detected(oai4g_pdcch_rx_config_t *const cfg[3], const int32_t *d_comp, const uint8_t *d_cfi,
+                                  int n_sf, int first_subframe, int subframe_step, oai4g_pdcch_rx_result_t *d_out,
+                                  void *stream);
+
+/* ---------------- UE control receive front end: IQ and estimates to the compensated symbols ---------------- */
+/* rx_pdcch up to pdcch_llr (PHY/LTE_TRANSPORT/dci.c:1689-1830, is_secondary_ue = 0, MU_RECEIVER off) and
+ * rx_pcfich (pcfich.c:231) for one subframe, always over three control symbols (dci.c:1704):
+ * pdcch_extract_rbs_single / _dual (:903, 1120), pdcch_channel_level (:643), the log2_maxh rule (:1751-1757,
+ * with its transposed read of avgP: 2 TX x 1 RX looks at port 0 only, 1 TX x 2 RX at antenna 0 only),
+ * pdcch_channel_compensation (:1371), pdcch_detection_mrc (:1591), pdcch_siso / pdcch_alamouti (:1632, 1654).
+ * rxdataF[a]: the FEP rows [nsymb][N] of receive antenna a; dl_ch_estimates[(p << 1) + a]: the estimate rows
+ * [nsymb][N] of port p at antenna a (rows 0..2 are read, row 0 alone unless high_speed_flag == 1).  Outputs:
+ * rxdataF_comp, plane 0, 3 * 12 * N_RB_DL words in the layout oai4g_pdcch_soft_bit_table documents (words
+ * 8 N_RB_DL .. 12 N_RB_DL - 1, which the reference never defines, are 0); log2_maxh; num_pdcch_symbols as
+ * rx_pcfich finds it (1..3).  diag_planes, when not null, receives the four compensated planes
+ * [(p << 1) + a][3 * 12 * N_RB_DL] before MRC (planes of absent ports / antennas are 0).  rho is not
+ * computed.  Returns 0, or -1: 4 TX ports, the extended prefix, more than 2 receive antennas, a mimo_mode
+ * other than SISO / ALAMOUTI, ALAMOUTI with one port. */
+int oai4g_rx_pdcch_front(int32_t *const *rxdataF, int32_t *const *dl_ch_estimates, const oai4g_frame_parms_t *frame_parms,
+                         uint8_t nb_antennas_rx, uint8_t subframe, uint8_t mimo_mode, uint32_t high_speed_flag,
+                         int32_t *rxdataF_comp, uint8_t *log2_maxh, uint8_t *num_pdcch_symbols, int32_t *diag_planes);
+/* rx_pcfich (pcfich.c:231) on plane 0 of rxdataF_comp (the packed symbol 0, 8 * N_RB_DL words are read): the
+ * 16 REs at pcfich_reg * 4, pcfich_unscrambling, the three correlations; the first strictly larger metric
+ * from -16384 on wins, 3 when none exceeds it.  mimo_mode is the reference's argument and, as there (its
+ * ALAMOUTI branch is commented out, pcfich.c:270-295), has no effect on the result: plane 0 is already combined.
+ * Returns 1..3, or -1 (refused as above). */
+int oai4g_rx_pcfich(const oai4g_frame_parms_t *frame_parms, uint8_t subframe, const int32_t *rxdataF_comp, uint8_t mimo_mode);
+/* rx_pdcch whole (dci.c:1689): the front end, then oai4g_pdcch_soft_bits with the detected count.  e_rx
+ * receives the soft bits, *num_pdcch_symbols the count.  Returns the number of soft bits, or -1. */
+int oai4g_rx_pdcch(int32_t *const *rxdataF, int32_t *const *dl_ch_estimates, const oai4g_frame_parms_t *frame_parms,
+                   uint8_t nb_antennas_rx, uint8_t subframe, uint8_t mimo_mode, uint32_t high_speed_flag, int8_t *e_rx,
+                   uint8_t *num_pdcch_symbols);
+/* The batched front end, device pointers, one launch: d_rxdataF [n_sf][nb_antennas_rx][nsymb][N] as
+ * oai4g_fep_batch writes it, d_est[(p << 1) + a] [n_sf][nsymb][N] as oai4g_chest_batch writes the plane of
+ * port p at antenna a, subframe i of index (first_subframe + i * subframe_step) mod 10 -> d_comp
+ * [n_sf][3 * 12 * N_RB_DL], d_cfi [n_sf], d_log2_maxh [n_sf].  Asynchronous on `stream`.  Returns 0 or -1. */
+typedef struct oai4g_pdcch_front_config oai4g_pdcch_front_config_t;
+oai4g_pdcch_front_config_t *oai4g_pdcch_front_config_create(const oai4g_frame_parms_t *frame_parms, uint8_t nb_antennas_rx,
+                                                            uint8_t mimo_mode, uint32_t high_speed_flag,
+                                                            uint8_t first_subframe, uint8_t subframe_step);
+void oai4g_pdcch_front_config_destroy(oai4g_pdcch_front_config_t *cfg);
+int oai4g_pdcch_front_batch(const oai4g_pdcch_front_config_t *cfg, int n_sf, const int32_t *d_rxdataF,
+                            const int32_t *const d_est[4], int32_t *d_comp, uint8_t *d_cfi, uint8_t *d_log2_maxh,
+                            void *stream);
 
 /* ---------------- UE PDSCH demodulation (second half) ---------------- */
 /* rx_pdsch (PHY/LTE_TRANSPORT/dlsch_demodulation.c:82) over the PDSCH symbols of one subframe as

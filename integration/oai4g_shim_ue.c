@@ -1,6 +1,6 @@
 /* oai4g_shim_ue.c — reference-side bindings that take PHY_VARS_UE / PHY_VARS_eNB.
  * Replaces: slot_fep.c:40 slot_fep, pilots.c:43 generate_pilots, lte_dl_channel_estimation.c:37,
- * dlsch_demodulation.c:82 rx_pdsch (TM1/TM2/TM3, TM4-6 single-layer precoding).
+ * dlsch_demodulation.c:82 rx_pdsch (TM1/TM2/TM3, TM4-6 single-layer precoding), dci.c:1689 rx_pdcch.
  * PHY_VARS_UE / PHY_VARS_eNB are defined in PHY/defs.h, whose include chain needs the asn1c-generated
  * RRC headers (PHY/INIT/defs.h:35-42), so this file compiles only inside a full reference build
  * (cmake_targets), next to oai4g_shim.c. */
@@ -139,5 +139,26 @@ int rx_pdsch(PHY_VARS_UE *ue, PDSCH_t type, unsigned char eNB_id, unsigned char 
   }
   if (n < 0) return -1;
   ue->lte_ue_pdsch_vars[eNB_id]->log2_maxh = log2_maxh;
+  return 0;
+}
+
+/* rx_pdcch (dci.c:1689) with is_secondary_ue = 0: extraction, channel level, compensation, MRC, SISO / Alamouti
+ * combining over three control symbols, rx_pcfich, then the soft bits of the detected count.  CONTRACT: e_rx and
+ * num_pdcch_symbols of lte_ue_pdcch_vars[eNB_id] become the reference's; the intermediates (rxdataF_ext,
+ * dl_ch_estimates_ext, rxdataF_comp, rho, llr, wbar) are NOT filled.  4 TX ports, the extended prefix and more
+ * than 2 receive antennas return -1. */
+int32_t rx_pdcch(LTE_UE_COMMON *lte_ue_common_vars, LTE_UE_PDCCH **lte_ue_pdcch_vars, LTE_DL_FRAME_PARMS *frame_parms,
+                 uint8_t subframe, uint8_t eNB_id, MIMO_mode_t mimo_mode, uint32_t high_speed_flag,
+                 uint8_t is_secondary_ue)
+{
+  if (is_secondary_ue) return -1;
+  oai4g_frame_parms_t fp;
+  fp_to(frame_parms, &fp);
+  uint8_t n = 0;
+  if (oai4g_rx_pdcch((int32_t *const *)lte_ue_common_vars->rxdataF, (int32_t *const *)lte_ue_common_vars->dl_ch_estimates[eNB_id],
+                     &fp, frame_parms->nb_antennas_rx, subframe, (uint8_t)mimo_mode, high_speed_flag,
+                     (int8_t *)lte_ue_pdcch_vars[eNB_id]->e_rx, &n) < 0)
+    return -1;
+  lte_ue_pdcch_vars[eNB_id]->num_pdcch_symbols = n;
   return 0;
 }

@@ -397,6 +397,23 @@ _SIGS = {
                                                  ctypes.c_int]),
     "oai4g_pdcch_rx_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                             ctypes.c_void_p]),
+    "oai4g_pdcch_rx_batch_detected": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                     ctypes.c_void_p]),
+    "oai4g_rx_pdcch_front": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+                                            ctypes.POINTER(FrameParms), ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint8,
+                                            ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8),
+                                            ctypes.POINTER(ctypes.c_uint8), ctypes.c_void_p]),
+    "oai4g_rx_pcfich": (ctypes.c_int, [ctypes.POINTER(FrameParms), ctypes.c_uint8, ctypes.c_void_p, ctypes.c_uint8]),
+    "oai4g_rx_pdcch": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+                                      ctypes.POINTER(FrameParms), ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint8,
+                                      ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8)]),
+    "oai4g_pdcch_front_config_create": (ctypes.c_void_p, [ctypes.POINTER(FrameParms), ctypes.c_uint8, ctypes.c_uint8,
+                                                          ctypes.c_uint32, ctypes.c_uint8, ctypes.c_uint8]),
+    "oai4g_pdcch_front_config_destroy": (None, [ctypes.c_void_p]),
+    "oai4g_pdcch_front_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                               ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 
@@ -1294,6 +1311,154 @@ class PdcchRxBatch:
             self.L.oai4g_dev_free(self.d_comp)
             self.L.oai4g_dev_free(self.d_out)
             self.cfg = None
+
+
+def _front_planes(fp, nb_rx, rxdataF, est):
+    """the plane pointer arrays of the front-end drop-ins: rxdataF[a], est[(p, a)] -> (keep-alive, rx, est)"""
+    keep = [np.ascontiguousarray(rxdataF[a], dtype=np.int32).ravel() for a in range(nb_rx)]
+    rx = (ctypes.c_void_p * 2)(*[k.ctypes.data for k in keep])
+    ep = (ctypes.c_void_p * 4)()
+    for p in range(fp.nb_antennas_tx_eNB):
+        for a in range(nb_rx):
+            keep.append(np.ascontiguousarray(est[(p, a)], dtype=np.int32).ravel())
+            ep[2 * p + a] = keep[-1].ctypes.data
+    return keep, rx, ep
+
+
+def rx_pdcch_front(fp, rxdataF, est, subframe, mimo_mode, high_speed_flag=1, diag=False):
+    """oai4g_rx_pdcch_front: rxdataF[a] and est[(p, a)] (rows [nsymb][N]) -> (plane 0 of rxdataF_comp
+    int32[36 N_RB_DL], log2_maxh, num_pdcch_symbols), and with diag the four planes before MRC [4][36 N_RB_DL]."""
+    nb_rx = len(rxdataF)
+    comp = np.zeros(36 * fp.N_RB_DL, dtype=np.int32)
+    planes = np.zeros((4, 36 * fp.N_RB_DL), dtype=np.int32) if diag else None
+    l2, n = ctypes.c_uint8(), ctypes.c_uint8()
+    keep, rx, ep = _front_planes(fp, min(nb_rx, 2), rxdataF, est)
+    _check(lib().oai4g_rx_pdcch_front(rx, ep, ctypes.byref(fp), nb_rx, subframe, mimo_mode, high_speed_flag, _ptr(comp),
+                                      ctypes.byref(l2), ctypes.byref(n), _ptr(planes) if diag else None) == 0)
+    return (comp, l2.value, n.value) + ((planes,) if diag else ())
+
+
+def rx_pcfich(fp, subframe, comp, mimo_mode=0):
+    """oai4g_rx_pcfich on plane 0 of rxdataF_comp: num_pdcch_symbols 1..3 (mimo_mode, as in the reference, does
+    not enter the result)"""
+    comp = np.ascontiguousarray(comp, dtype=np.int32)
+    assert comp.size >= 8 * fp.N_RB_DL
+    n = lib().oai4g_rx_pcfich(ctypes.byref(fp), subframe, _ptr(comp), mimo_mode)
+    _check(n >= 0)
+    return n
+
+
+def rx_pdcch(fp, rxdataF, est, subframe, mimo_mode, high_speed_flag=1):
+    """oai4g_rx_pdcch: (e_rx int8[8 Mquad], num_pdcch_symbols)"""
+    nb_rx = len(rxdataF)
+    e = np.zeros(8 * 800, dtype=np.int8)
+    n = ctypes.c_uint8()
+    keep, rx, ep = _front_planes(fp, min(nb_rx, 2), rxdataF, est)
+    cnt = lib().oai4g_rx_pdcch(rx, ep, ctypes.byref(fp), nb_rx, subframe, mimo_mode, high_speed_flag, _ptr(e), ctypes.byref(n))
+    _check(cnt >= 0)
+    return e[:cnt].copy(), n.value
+
+
+class PdcchFrontBatch:
+    """Device-resident control front end of n_sf subframes (oai4g_pdcch_front_batch): the FEP output
+    [n_sf (+ 1)][nb_rx][nsymb][N] and the estimate planes of ports x antennas -> d_comp [n_sf][36 N_RB_DL],
+    d_cfi [n_sf], d_log2_maxh [n_sf].  estimate() runs the oai4g_chest_batch of every plane into the object's
+    own buffers; launch() takes them or the caller's."""
+
+    def __init__(self, fp, n_sf, nb_rx, mimo_mode, high_speed_flag=1, first_subframe=0, subframe_step=1):
+        init()
+        self.L, self.fp, self.n_sf, self.nb_rx = lib(), fp, n_sf, nb_rx
+        self.first, self.step = first_subframe, subframe_step
+        self.cfg = self.L.oai4g_pdcch_front_config_create(ctypes.byref(fp), nb_rx, mimo_mode, high_speed_flag,
+                                                          first_subframe, subframe_step)
+        _check(bool(self.cfg))
+        self.words = 36 * fp.N_RB_DL
+        self.plane = n_sf * fp.symbols_per_tti * fp.ofdm_symbol_size
+        self.d_est = self.L.oai4g_dev_alloc(4 * self.plane * 4)
+        self.d_comp = self.L.oai4g_dev_alloc(n_sf * self.words * 4)
+        self.d_cfi = self.L.oai4g_dev_alloc(max(4, n_sf))
+        self.d_log2 = self.L.oai4g_dev_alloc(max(4, n_sf))
+        _check(bool(self.d_est) and bool(self.d_comp) and bool(self.d_cfi) and bool(self.d_log2))
+        self._chest = []
+
+    def est_plane(self, p, a):
+        return ctypes.c_void_p(self.d_est + (2 * p + a) * self.plane * 4)
+
+    def upload_estimates(self, est):
+        """est[(p, a)] = int32 [n_sf][nsymb * N]"""
+        for (p, a), v in est.items():
+            v = np.ascontiguousarray(v, dtype=np.int32)
+            assert v.size == self.plane
+            _check(self.L.oai4g_memcpy_h2d(self.est_plane(p, a), _ptr(v), v.nbytes) == 0)
+
+    def estimate(self, d_rxF, stream=None):
+        """oai4g_chest_batch per (port, antenna) over the FEP output [n_sf + 1][nb_rx][nsymb][N]"""
+        if not self._chest:
+            for p in range(self.fp.nb_antennas_tx_eNB):
+                cfg = self.L.oai4g_chest_config_create(ctypes.byref(self.fp), p, self.first, self.step)
+                _check(bool(cfg))
+                self._chest.append(cfg)
+                _check(self.L.oai4g_chest_config_set_stride(cfg, self.nb_rx, self.nb_rx) == 0)
+        grid = self.fp.symbols_per_tti * self.fp.ofdm_symbol_size
+        for p, cfg in enumerate(self._chest):
+            for a in range(self.nb_rx):
+                _check(self.L.oai4g_chest_batch(cfg, self.n_sf, ctypes.c_void_p(d_rxF + a * grid * 4), self.est_plane(p, a),
+                                                stream) == 0)
+
+    def launch(self, d_rxF, stream=None):
+        ep = (ctypes.c_void_p * 4)(*[self.est_plane(i >> 1, i & 1).value for i in range(4)])
+        _check(self.L.oai4g_pdcch_front_batch(self.cfg, self.n_sf, d_rxF, ep, self.d_comp, self.d_cfi, self.d_log2,
+                                              stream) == 0)
+
+    def results(self):
+        """(comp int32 [n_sf][36 N_RB_DL], cfi uint8 [n_sf], log2_maxh uint8 [n_sf])"""
+        _check(self.L.oai4g_sync() == 0)
+        comp = np.empty((self.n_sf, self.words), dtype=np.int32)
+        cfi, l2 = np.empty(self.n_sf, dtype=np.uint8), np.empty(self.n_sf, dtype=np.uint8)
+        _check(self.L.oai4g_memcpy_d2h(_ptr(comp), self.d_comp, comp.nbytes) == 0)
+        _check(self.L.oai4g_memcpy_d2h(_ptr(cfi), self.d_cfi, cfi.nbytes) == 0)
+        _check(self.L.oai4g_memcpy_d2h(_ptr(l2), self.d_log2, l2.nbytes) == 0)
+        return comp, cfi, l2
+
+    def close(self):
+        if self.cfg:
+            self.L.oai4g_sync()
+            for cfg in self._chest:
+                self.L.oai4g_chest_config_destroy(cfg)
+            for ptr in (self.d_est, self.d_comp, self.d_cfi, self.d_log2):
+                self.L.oai4g_dev_free(ptr)
+            self.L.oai4g_pdcch_front_config_destroy(self.cfg)
+            self.cfg = None
+
+
+class PdcchRxBatchDetected:
+    """The DCI search behind PdcchFrontBatch (oai4g_pdcch_rx_batch_detected): the three configurations of 1, 2
+    and 3 control symbols; every subframe is searched under the one its device-resident count selects."""
+
+    def __init__(self, fp, crnti, si_rnti, ra_rnti, plan, n_sf):
+        self.by_count = [PdcchRxBatch(fp, n, crnti, si_rnti, ra_rnti, plan, 1) for n in (1, 2, 3)]
+        self.L, self.fp, self.n_sf = lib(), fp, n_sf
+        self.d_out = self.L.oai4g_dev_alloc(n_sf * ctypes.sizeof(PdcchRxResult))
+        _check(bool(self.d_out))
+
+    def launch(self, d_comp, d_cfi, first_subframe=0, subframe_step=1, stream=None):
+        cfgs = (ctypes.c_void_p * 3)(*[b.cfg for b in self.by_count])
+        _check(self.L.oai4g_pdcch_rx_batch_detected(cfgs, d_comp, d_cfi, self.n_sf, first_subframe, subframe_step,
+                                                    self.d_out, stream) == 0)
+
+    def results(self):
+        _check(self.L.oai4g_sync() == 0)
+        out = (PdcchRxResult * self.n_sf)()
+        _check(self.L.oai4g_memcpy_d2h(ctypes.addressof(out), self.d_out, ctypes.sizeof(out)) == 0)
+        return out
+
+    def close(self):
+        if self.d_out:
+            self.L.oai4g_sync()
+            for b in self.by_count:
+                b.close()
+            self.L.oai4g_dev_free(self.d_out)
+            self.d_out = None
 
 
 def _upload_tiled(dec, base, chunk_bytes=64 << 20):

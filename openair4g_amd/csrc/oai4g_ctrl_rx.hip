@@ -21,6 +21,8 @@
  * Nothing between the steps touches HBM.  NMAX = 64 serves every DCI and the PBCH (D <= 61),
  * NMAX = 512 the phy_viterbi_lte drop-in.
  */
+#include <type_traits>
+
 #include "oai4g_internal.h"
 
 static __device__ __forceinline__ uint32_t dpp_min(uint32_t v, uint32_t t) { return t < v ? t : v; }
@@ -46,15 +48,33 @@ static __device__ __forceinline__ uint32_t cc_rev(uint32_t i)
   return (__popc(i & 0155u) & 1u) | ((__popc(i & 0117u) & 1u) << 1) | ((__popc(i & 0127u) & 1u) << 2);
 }
 
-template <int NMAX>
-__global__ void __launch_bounds__(64) k_cc_decode(cc_args_t a)
+/* ARGS = cc_det_args_t: the PDCCH batch whose subframes carry a detected num_pdcch_symbols each; the jobs, the
+ * gather table and the receive plans are then those of the subframe's own count */
+template <int NMAX, typename ARGS = cc_args_t>
+__global__ void __launch_bounds__(64) k_cc_decode(ARGS a)
 {
+  constexpr bool DET = !std::is_same<ARGS, cc_args_t>::value;
   __shared__ int8_t s_d[3 * NMAX];
   __shared__ uint64_t s_tb[NMAX];
   __shared__ uint8_t s_out[NMAX / 8 + 8];
   const uint32_t lane = threadIdx.x, dec = blockIdx.x, item = dec / a.n_jobs;
-  const uint32_t row = a.tab ? (a.first_row + item) % 10u : 0u;        /* PDCCH batch: the subframe index */
-  const cc_job_t job = a.jobs[row * a.n_jobs + (dec - item * a.n_jobs)];
+  uint32_t row = a.tab ? (a.first_row + item) % 10u : 0u;              /* PDCCH batch: the subframe index */
+  uint32_t jrow = row * a.n_jobs + (dec - item * a.n_jobs);
+  if constexpr (DET) {
+    const uint32_t n = (uint32_t)a.cfi[item] - 1u, j = dec - item * a.n_jobs;
+    if (n > 2u) return;
+    pdcch_det_set_t st = a.set[0];
+    if (n == 1u) st = a.set[1];
+    if (n == 2u) st = a.set[2];
+    if (j >= st.n_jobs) return;
+    row = (a.first_row + item * a.sf_step) % 10u;
+    jrow = row * st.n_jobs + j;
+    a.jobs = st.jobs;
+    a.tab = st.tab;
+    a.tab_stride = st.tab_stride;
+    a.plan = st.plan;
+  }
+  const cc_job_t job = a.jobs[jrow];
   const uint32_t D = job.D, D3 = 3u * D, E = job.E;
   if (D == 0 || D > (uint32_t)NMAX) return;
   const int8_t *__restrict__ e = a.e + (size_t)item * a.e_stride + job.e_off;
@@ -167,17 +187,33 @@ hipError_t oai4g_launch_pdcch_soft(const int16_t *d_comp, const uint32_t *d_tab,
 
 /* second stage of the batched DCI search: one lane per subframe walks its decoded candidates in plan
  * order under dci_decoding_procedure0's rules and dci_decoding_procedure's stops between calls */
-__global__ void __launch_bounds__(64) k_pdcch_resolve(pdcch_resolve_args_t a)
+/* ARGS = pdcch_resolve_det_args_t: the candidates are those of the subframe's detected count; the records stay
+ * a.n_jobs apart */
+template <typename ARGS = pdcch_resolve_args_t>
+__global__ void __launch_bounds__(64) k_pdcch_resolve(ARGS a)
 {
+  constexpr bool DET = !std::is_same<ARGS, pdcch_resolve_args_t>::value;
   const uint32_t sf = blockIdx.x * 64u + threadIdx.x;
   if (sf >= a.n_sf) return;
-  const uint32_t row = (a.first_row + sf) % 10u, nc = a.n_cand[row];
+  uint32_t row = (a.first_row + sf) % 10u, cstride = a.n_jobs;
+  if constexpr (DET) {
+    const uint32_t n = (uint32_t)a.cfi[sf] - 1u;
+    pdcch_det_set_t s = a.set[0];
+    if (n == 1u) s = a.set[1];
+    if (n == 2u) s = a.set[2];
+    row = (a.first_row + sf * a.sf_step) % 10u;
+    a.cands = s.cands;
+    a.n_cand = s.n_cand;
+    cstride = s.n_jobs;
+    if (n > 2u) cstride = 0u;                                           /* no count, no candidates */
+  }
+  const uint32_t nc = DET && cstride == 0u ? 0u : a.n_cand[row];
   oai4g_pdcch_rx_result_t &o = a.out[sf];
   pdcch_state_t st = {};
   st.nCCE = -1;
   uint32_t old_cnt = 0, prev_plan = 0;
   for (uint32_t c = 0; c < nc; c++) {
-    const pdcch_cand_t cd = a.cands[row * a.n_jobs + c];
+    const pdcch_cand_t cd = a.cands[row * cstride + c];
     if (cd.first) {
       if (c > 0) {
         if (st.map[0] == 0xFFFFu || (st.format0_found && st.format_c_found)) break;
@@ -201,7 +237,14 @@ __global__ void __launch_bounds__(64) k_pdcch_resolve(pdcch_resolve_args_t a)
 hipError_t oai4g_launch_pdcch_resolve(const pdcch_resolve_args_t &a, hipStream_t s)
 {
   if (a.n_sf == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_pdcch_resolve, dim3((a.n_sf + 63) / 64), dim3(64), 0, s, a);
+  hipLaunchKernelGGL(k_pdcch_resolve<>, dim3((a.n_sf + 63) / 64), dim3(64), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t oai4g_launch_pdcch_resolve_detected(const pdcch_resolve_det_args_t &a, hipStream_t s)
+{
+  if (a.n_sf == 0) return hipSuccess;
+  hipLaunchKernelGGL((k_pdcch_resolve<pdcch_resolve_det_args_t>), dim3((a.n_sf + 63) / 64), dim3(64), 0, s, a);
   return hipGetLastError();
 }
 
@@ -213,5 +256,14 @@ hipError_t oai4g_launch_cc_decode(const cc_args_t &a, uint32_t nmax, hipStream_t
     hipLaunchKernelGGL(k_cc_decode<64>, dim3(n), dim3(64), 0, s, a);
   else
     hipLaunchKernelGGL(k_cc_decode<512>, dim3(n), dim3(64), 0, s, a);
+  return hipGetLastError();
+}
+
+/* every DCI fits 64 trellis steps; a.n_jobs is the largest job count of the three sets */
+hipError_t oai4g_launch_cc_decode_detected(const cc_det_args_t &a, hipStream_t s)
+{
+  const uint32_t n = a.n_items * a.n_jobs;
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL((k_cc_decode<64, cc_det_args_t>), dim3(n), dim3(64), 0, s, a);
   return hipGetLastError();
 }

@@ -5487,3 +5487,266 @@ extern "C" int oai4g_pdcch_rx_batch(oai4g_pdcch_rx_config_t *cfg, const int32_t 
   HCK(oai4g_launch_pdcch_resolve(r, s), -1);
   return 0;
 }
+
+/* The search over subframes whose count was detected on the device: one launch decodes, per subframe, the
+ * candidates of its own count's configuration; the count stays in d_cfi. */
+extern "C" int oai4g_pdcch_rx_batch_detected(oai4g_pdcch_rx_config_t *const cfg[3], const int32_t *d_comp, const uint8_t *d_cfi,
+                                             int n_sf, int first_subframe, int subframe_step, oai4g_pdcch_rx_result_t *d_out,
+                                             void *stream)
+{
+  if (!cfg || !cfg[0] || !cfg[1] || !cfg[2] || n_sf < 0 || first_subframe < 0 || first_subframe > 9 || subframe_step < 0 ||
+      subframe_step > 9 || (n_sf > 0 && (!d_comp || !d_cfi || !d_out))) {
+    set_err("pdcch_rx_batch_detected: bad arguments");
+    return -1;
+  }
+  for (int i = 0; i < 3; i++) {
+    const oai4g_pdcch_rx_config_t *c = cfg[i], *c0 = cfg[0];
+    if (c->npd != i + 1 || memcmp(&c->fp, &c0->fp, sizeof(c->fp)) != 0 || c->crnti != c0->crnti || c->si_rnti != c0->si_rnti ||
+        c->ra_rnti != c0->ra_rnti || c->plan.size() != c0->plan.size() ||
+        memcmp(c->plan.data(), c0->plan.data(), c->plan.size() * sizeof(oai4g_pdcch_plan_t)) != 0) {
+      set_err("pdcch_rx_batch_detected: configuration %d must be the one of %d symbols for the same frame, RNTIs and plan", i, i + 1);
+      return -1;
+    }
+  }
+  NEED_INIT(-1);
+  if (n_sf == 0) return 0;
+  uint32_t nj = 0;
+  for (int i = 0; i < 3; i++) nj = std::max(nj, cfg[i]->n_jobs);
+  oai4g_pdcch_rx_config_t *own = cfg[2];
+  const size_t need = (size_t)n_sf * nj * OAI4G_PDCCH_REC;
+  if (need > own->rec_cap) {
+    HCK(hipDeviceSynchronize(), -1);
+    if (own->d_rec) hipFree(own->d_rec);
+    own->d_rec = nullptr;
+    own->rec_cap = 0;
+    HCK(hipMalloc(&own->d_rec, need), -1);
+    own->rec_cap = need;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  HCK(hipMemsetAsync(own->d_rec, 0, need, s), -1);
+  HCK(hipMemsetAsync(d_out, 0, (size_t)n_sf * sizeof(oai4g_pdcch_rx_result_t), s), -1);
+  cc_det_args_t a;
+  pdcch_resolve_det_args_t r;
+  memset(&a, 0, sizeof(a));
+  memset(&r, 0, sizeof(r));
+  for (int i = 0; i < 3; i++) {
+    const oai4g_pdcch_rx_config_t *c = cfg[i];
+    pdcch_det_set_t &t = a.set[i];
+    t.jobs = (const cc_job_t *)(c->dev + c->o_jobs);
+    t.tab = (const uint32_t *)c->dev;
+    t.cands = (const pdcch_cand_t *)(c->dev + c->o_cands);
+    t.n_cand = (const uint32_t *)(c->dev + c->o_ncand);
+    t.plan = (const uint16_t *)(c->dev + c->o_ccplan);
+    t.n_jobs = c->n_jobs;
+    t.tab_stride = c->tab_stride;
+    r.set[i] = t;
+  }
+  a.jobs = a.set[2].jobs;
+  a.tab = a.set[2].tab;
+  a.plan = a.set[2].plan;
+  a.n_jobs = nj;
+  a.n_items = (uint32_t)n_sf;
+  a.out = own->d_rec;
+  a.out_stride = OAI4G_PDCCH_REC;
+  a.comp = (const int16_t *)d_comp;
+  a.comp_stride = (size_t)3 * own->fp.N_RB_DL * 12 * 2;
+  a.first_row = (uint32_t)first_subframe;
+  a.cfi = d_cfi;
+  a.sf_step = (uint32_t)subframe_step;
+  HCK(oai4g_launch_cc_decode_detected(a, s), -1);
+  r.rec = own->d_rec;
+  r.cands = r.set[2].cands;
+  r.n_cand = r.set[2].n_cand;
+  r.plans = (const oai4g_pdcch_plan_t *)(own->dev + own->o_plans);
+  r.n_jobs = nj;
+  r.n_sf = (uint32_t)n_sf;
+  r.first_row = (uint32_t)first_subframe;
+  r.crnti = own->crnti;
+  r.si_rnti = own->si_rnti;
+  r.ra_rnti = own->ra_rnti;
+  r.out = d_out;
+  r.cfi = d_cfi;
+  r.sf_step = (uint32_t)subframe_step;
+  HCK(oai4g_launch_pdcch_resolve_detected(r, s), -1);
+  return 0;
+}
+
+/* ------------------------------------------------------------------------------------------
+ * PDCCH / PCFICH receive front end: rx_pdcch up to the compensated symbols (dci.c:1689-1830) and
+ * rx_pcfich (pcfich.c:231), k_pdcch_front.
+ * ---------------------------------------------------------------------------------------- */
+static int pdcch_front_ok(const char *who, const oai4g_frame_parms_t *fp, int nb_rx, uint8_t mimo_mode)
+{
+  if (!fp) { set_err("%s: null frame parameters", who); return 0; }
+  if (fp->nb_antennas_tx_eNB == 4) { set_err("%s: 4 TX ports are not defined by the reference's demapping (dci.c:420)", who); return 0; }
+  if (fp->Ncp != 0) { set_err("%s: only the normal cyclic prefix is supported", who); return 0; }
+  if (nb_rx < 1 || nb_rx > 2) { set_err("%s: %d receive antennas (1 or 2)", who, nb_rx); return 0; }
+  if (fp->nb_antennas_tx_eNB < 1 || fp->nb_antennas_tx_eNB > 2) { set_err("%s: %u TX ports (1 or 2)", who, fp->nb_antennas_tx_eNB); return 0; }
+  if (mimo_mode != OAI4G_SISO && mimo_mode != OAI4G_ALAMOUTI) { set_err("%s: mimo_mode %u (SISO or ALAMOUTI)", who, mimo_mode); return 0; }
+  if (mimo_mode == OAI4G_ALAMOUTI && fp->nb_antennas_tx_eNB != 2) { set_err("%s: ALAMOUTI combining needs 2 TX ports", who); return 0; }
+  const uint32_t N = fp->ofdm_symbol_size, NRE = 12u * fp->N_RB_DL;
+  if (fp->N_RB_DL == 0 || 5u + NRE > N || fp->first_carrier_offset + NRE / 2 > N || 13u + NRE / 2 > N) {
+    set_err("%s: N_RB_DL %u does not fit the symbol size %u", who, fp->N_RB_DL, N);
+    return 0;
+  }
+  return 1;
+}
+
+/* the first Gold word of pcfich_unscrambling (pcfich.c:122) */
+static uint32_t pcfich_gold_h(const oai4g_frame_parms_t *fp, uint32_t subframe)
+{
+  uint32_t x1 = 1u + (1u << 31), x2 = ((((2u * fp->Nid_cell) + 1u) * (1u + subframe)) << 9) + fp->Nid_cell;
+  x2 = x2 ^ ((x2 ^ (x2 >> 1) ^ (x2 >> 2) ^ (x2 >> 3)) << 31);
+  for (int q = 1; q < 50; q++) gold_step_h(&x1, &x2);
+  gold_step_h(&x1, &x2);
+  return x1 ^ x2;
+}
+
+static void pdcch_front_fill(pdcch_front_args_t &a, const oai4g_frame_parms_t *fp, int nb_rx, uint8_t mimo_mode,
+                             uint32_t high_speed_flag, uint32_t first_sf, uint32_t sf_step)
+{
+  memset(&a, 0, sizeof(a));
+  a.N = fp->ofdm_symbol_size;
+  a.N_RB = fp->N_RB_DL;
+  a.fco = fp->first_carrier_offset;
+  a.nushift3 = fp->nushift % 3u;
+  a.nb_tx = fp->nb_antennas_tx_eNB;
+  a.nb_rx = (uint32_t)nb_rx;
+  a.alamouti = mimo_mode == OAI4G_ALAMOUTI;
+  a.high_speed = high_speed_flag == 1;
+  a.first_sf = first_sf;
+  a.sf_step = sf_step;
+  uint16_t reg[4];
+  uint8_t fi;
+  pcfich_regs(fp, reg, &fi);
+  for (int q = 0; q < 4; q++) a.pcf_word[q] = (uint32_t)reg[q] * 4u;
+  for (uint32_t sf = 0; sf < 10; sf++) a.pcf_gold[sf] = pcfich_gold_h(fp, sf);
+}
+
+extern "C" int oai4g_rx_pdcch_front(int32_t *const *rxdataF, int32_t *const *dl_ch_estimates, const oai4g_frame_parms_t *fp,
+                                    uint8_t nb_antennas_rx, uint8_t subframe, uint8_t mimo_mode, uint32_t high_speed_flag,
+                                    int32_t *rxdataF_comp, uint8_t *log2_maxh, uint8_t *num_pdcch_symbols, int32_t *diag_planes)
+{
+  if (!pdcch_front_ok("rx_pdcch_front", fp, nb_antennas_rx, mimo_mode)) return -1;
+  if (subframe > 9 || !rxdataF || !dl_ch_estimates || !rxdataF_comp) { set_err("rx_pdcch_front: bad arguments"); return -1; }
+  const int nb_tx = fp->nb_antennas_tx_eNB;
+  for (int a = 0; a < nb_antennas_rx; a++)
+    for (int p = 0; p < nb_tx; p++)
+      if (!rxdataF[a] || !dl_ch_estimates[(p << 1) + a]) { set_err("rx_pdcch_front: null plane"); return -1; }
+  NEED_INIT(-1);
+  const size_t rows = (size_t)3 * fp->ofdm_symbol_size * 4, out_b = (size_t)36 * fp->N_RB_DL * 4;
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t o_est = 2 * up(rows), o_comp = o_est + 4 * up(rows), o_pl = o_comp + up(out_b), o_b = o_pl + 4 * up(out_b);
+  uint8_t *buf = scratch(o_b + 256);
+  if (!buf) { set_err("rx_pdcch_front: scratch allocation failed"); return -1; }
+  pdcch_front_args_t a;
+  pdcch_front_fill(a, fp, nb_antennas_rx, mimo_mode, high_speed_flag, subframe, 0);
+  a.n_sf = 1;
+  a.rxF = (const int32_t *)buf;
+  a.rx_ant_stride = up(rows) / 4;
+  for (int rx = 0; rx < nb_antennas_rx; rx++) {
+    HCK(hipMemcpyAsync(buf + rx * up(rows), rxdataF[rx], rows, hipMemcpyHostToDevice, g_scr.s), -1);
+    for (int p = 0; p < nb_tx; p++) {
+      const int pl = (p << 1) + rx;
+      HCK(hipMemcpyAsync(buf + o_est + pl * up(rows), dl_ch_estimates[pl], rows, hipMemcpyHostToDevice, g_scr.s), -1);
+      a.est[pl] = (const int32_t *)(buf + o_est + pl * up(rows));
+    }
+  }
+  a.comp = (int32_t *)(buf + o_comp);
+  a.planes = diag_planes ? (int32_t *)(buf + o_pl) : nullptr;
+  a.cfi = buf + o_b;
+  a.log2_maxh = buf + o_b + 1;
+  HCK(oai4g_launch_pdcch_front(a, g_scr.s), -1);
+  uint8_t two[2] = {0, 0};
+  HCK(hipMemcpyAsync(rxdataF_comp, a.comp, out_b, hipMemcpyDeviceToHost, g_scr.s), -1);
+  if (diag_planes) HCK(hipMemcpy2DAsync(diag_planes, out_b, a.planes, out_b, out_b, 4, hipMemcpyDeviceToHost, g_scr.s), -1);
+  HCK(hipMemcpyAsync(two, buf + o_b, 2, hipMemcpyDeviceToHost, g_scr.s), -1);
+  HCK(hipStreamSynchronize(g_scr.s), -1);
+  if (num_pdcch_symbols) *num_pdcch_symbols = two[0];
+  if (log2_maxh) *log2_maxh = two[1];
+  return 0;
+}
+
+extern "C" int oai4g_rx_pcfich(const oai4g_frame_parms_t *fp, uint8_t subframe, const int32_t *rxdataF_comp, uint8_t mimo_mode)
+{
+  if (!pdcch_front_ok("rx_pcfich", fp, 1, fp && fp->nb_antennas_tx_eNB == 2 ? mimo_mode : (uint8_t)OAI4G_SISO)) return -1;
+  if (subframe > 9 || !rxdataF_comp) { set_err("rx_pcfich: bad arguments"); return -1; }
+  NEED_INIT(-1);
+  const size_t cb = (size_t)8 * fp->N_RB_DL * 4;              /* the packed symbol 0 */
+  uint8_t *buf = scratch(cb + 512);
+  if (!buf) { set_err("rx_pcfich: scratch allocation failed"); return -1; }
+  uint16_t reg[4];
+  uint8_t fi, n = 0;
+  uint32_t w[4];
+  pcfich_regs(fp, reg, &fi);
+  for (int q = 0; q < 4; q++) w[q] = (uint32_t)reg[q] * 4u;
+  uint8_t *d_n = buf + ((cb + 255) & ~(size_t)255);
+  HCK(hipMemcpyAsync(buf, rxdataF_comp, cb, hipMemcpyHostToDevice, g_scr.s), -1);
+  HCK(oai4g_launch_rx_pcfich((const int32_t *)buf, w, pcfich_gold_h(fp, subframe), d_n, g_scr.s), -1);
+  HCK(hipMemcpyAsync(&n, d_n, 1, hipMemcpyDeviceToHost, g_scr.s), -1);
+  HCK(hipStreamSynchronize(g_scr.s), -1);
+  return n;
+}
+
+extern "C" int oai4g_rx_pdcch(int32_t *const *rxdataF, int32_t *const *dl_ch_estimates, const oai4g_frame_parms_t *fp,
+                              uint8_t nb_antennas_rx, uint8_t subframe, uint8_t mimo_mode, uint32_t high_speed_flag,
+                              int8_t *e_rx, uint8_t *num_pdcch_symbols)
+{
+  if (!pdcch_rx_geometry_ok("rx_pdcch", fp, subframe, 3)) return -1;
+  if (!e_rx) { set_err("rx_pdcch: null e_rx"); return -1; }
+  std::vector<int32_t> comp((size_t)36 * fp->N_RB_DL);
+  uint8_t n = 0;
+  if (oai4g_rx_pdcch_front(rxdataF, dl_ch_estimates, fp, nb_antennas_rx, subframe, mimo_mode, high_speed_flag, comp.data(),
+                           nullptr, &n, nullptr) != 0)
+    return -1;
+  if (num_pdcch_symbols) *num_pdcch_symbols = n;
+  return oai4g_pdcch_soft_bits(comp.data(), fp, subframe, n, e_rx);
+}
+
+struct oai4g_pdcch_front_config {
+  oai4g_frame_parms_t fp;
+  pdcch_front_args_t a;
+};
+
+extern "C" oai4g_pdcch_front_config_t *oai4g_pdcch_front_config_create(const oai4g_frame_parms_t *fp, uint8_t nb_antennas_rx,
+                                                                       uint8_t mimo_mode, uint32_t high_speed_flag,
+                                                                       uint8_t first_subframe, uint8_t subframe_step)
+{
+  if (!pdcch_front_ok("pdcch_front_config_create", fp, nb_antennas_rx, mimo_mode)) return nullptr;
+  if (first_subframe > 9 || subframe_step > 9) { set_err("pdcch_front_config_create: subframe %u / step %u", first_subframe, subframe_step); return nullptr; }
+  oai4g_pdcch_front_config_t *cfg = new oai4g_pdcch_front_config_t;
+  cfg->fp = *fp;
+  pdcch_front_fill(cfg->a, fp, nb_antennas_rx, mimo_mode, high_speed_flag, first_subframe, subframe_step);
+  return cfg;
+}
+
+extern "C" void oai4g_pdcch_front_config_destroy(oai4g_pdcch_front_config_t *cfg) { delete cfg; }
+
+extern "C" int oai4g_pdcch_front_batch(const oai4g_pdcch_front_config_t *cfg, int n_sf, const int32_t *d_rxdataF,
+                                       const int32_t *const d_est[4], int32_t *d_comp, uint8_t *d_cfi, uint8_t *d_log2_maxh,
+                                       void *stream)
+{
+  if (!cfg || n_sf < 0 || (n_sf > 0 && (!d_rxdataF || !d_est || !d_comp || !d_cfi || !d_log2_maxh))) {
+    set_err("pdcch_front_batch: bad arguments");
+    return -1;
+  }
+  pdcch_front_args_t a = cfg->a;
+  for (uint32_t p = 0; p < a.nb_tx; p++)
+    for (uint32_t rx = 0; rx < a.nb_rx; rx++) {
+      if (n_sf > 0 && !d_est[(p << 1) + rx]) { set_err("pdcch_front_batch: null estimate plane %u", (p << 1) + rx); return -1; }
+      a.est[(p << 1) + rx] = n_sf > 0 ? d_est[(p << 1) + rx] : nullptr;
+    }
+  NEED_INIT(-1);
+  if (n_sf == 0) return 0;
+  const size_t grid = (size_t)cfg->fp.symbols_per_tti * cfg->fp.ofdm_symbol_size;
+  a.n_sf = (uint32_t)n_sf;
+  a.rxF = d_rxdataF;
+  a.rx_ant_stride = grid;
+  a.rx_sf_stride = grid * a.nb_rx;
+  a.est_sf_stride = grid;
+  a.comp = d_comp;
+  a.cfi = d_cfi;
+  a.log2_maxh = d_log2_maxh;
+  HCK(oai4g_launch_pdcch_front(a, (hipStream_t)stream), -1);
+  return 0;
+}

@@ -597,6 +597,50 @@ struct pdcch_resolve_args_t {
 hipError_t oai4g_launch_pdcch_resolve(const pdcch_resolve_args_t &a, hipStream_t s);
 #define OAI4G_CC_NMAX 512
 hipError_t oai4g_launch_cc_decode(const cc_args_t &a, uint32_t nmax, hipStream_t s);
+
+/* The DCI search over subframes whose num_pdcch_symbols was detected on the device (k_pdcch_front): subframe
+ * i takes the jobs, gather table and candidates of the configuration built for cfi[i] (1..3, anything else
+ * decodes nothing), at subframe index (first_row + i sf_step) mod 10.  The records of a subframe lie n_jobs
+ * (the largest of the three) apart. */
+struct pdcch_det_set_t {
+  const cc_job_t *jobs;        /* [10][n_jobs] */
+  const uint32_t *tab;         /* [10][tab_stride] */
+  const pdcch_cand_t *cands;   /* [10][n_jobs] */
+  const uint32_t *n_cand;      /* [10] */
+  const uint16_t *plan;        /* the receive plans of the convolutional code */
+  uint32_t n_jobs, tab_stride;
+};
+struct cc_det_args_t : cc_args_t {
+  pdcch_det_set_t set[3];
+  const uint8_t *cfi;          /* [n_items] */
+  uint32_t sf_step;
+};
+struct pdcch_resolve_det_args_t : pdcch_resolve_args_t {
+  pdcch_det_set_t set[3];
+  const uint8_t *cfi;
+  uint32_t sf_step;
+};
+hipError_t oai4g_launch_cc_decode_detected(const cc_det_args_t &a, hipStream_t s);
+hipError_t oai4g_launch_pdcch_resolve_detected(const pdcch_resolve_det_args_t &a, hipStream_t s);
+
+/* The PDCCH / PCFICH receive front end (oai4g_pdcch_front.hip: k_pdcch_front), one workgroup per subframe */
+struct pdcch_front_args_t {
+  const int32_t *rxF;          /* [n_sf][nb_rx][nsymb][N] */
+  size_t rx_sf_stride, rx_ant_stride;   /* words */
+  const int32_t *est[4];       /* plane (p << 1) + a: [n_sf][nsymb][N] */
+  size_t est_sf_stride;        /* words */
+  uint32_t N, N_RB, fco, nushift3;
+  uint32_t nb_tx, nb_rx, alamouti, high_speed;
+  uint32_t first_sf, sf_step, n_sf;
+  uint32_t pcf_word[4];        /* pcfich_reg * 4: the REGs' first words in the packed symbol 0 */
+  uint32_t pcf_gold[10];       /* the PCFICH scrambling word of every subframe index */
+  int32_t *comp;               /* [n_sf][36 N_RB]: plane 0 of rxdataF_comp */
+  int32_t *planes;             /* null, or [n_sf][4][36 N_RB]: the compensated planes before MRC */
+  uint8_t *cfi, *log2_maxh;    /* [n_sf] */
+};
+hipError_t oai4g_launch_pdcch_front(const pdcch_front_args_t &a, hipStream_t s);
+/* rx_pcfich alone on a plane 0 in device memory: pcf_word as above, gold the subframe's scrambling word */
+hipError_t oai4g_launch_rx_pcfich(const int32_t *d_comp, const uint32_t pcf_word[4], uint32_t gold, uint8_t *d_out, hipStream_t s);
 void oai4g_set_error(const char *fmt, ...);
 /* binds the calling thread to the device the library was initialised on (hipSetDevice is per thread) */
 int oai4g_bind_thread(void);

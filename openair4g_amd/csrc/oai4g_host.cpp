@@ -99,20 +99,37 @@ static void gold_step_h(uint32_t *x1, uint32_t *x2)
   *x2 = *x2 ^ (*x2 << 31) ^ (*x2 << 30) ^ (*x2 << 29) ^ (*x2 << 28);
 }
 
+/* lte_gold_generic's reset (lte_gold.c:151-177): x1 = 1 + 2^31, bit 31 of x2 from c_init, and the
+ * 49 discarded word steps */
+static void gold_start_h(uint32_t c_init, uint32_t *x1, uint32_t *x2)
+{
+  *x1 = 1u + (1u << 31);
+  *x2 = c_init ^ ((c_init ^ (c_init >> 1) ^ (c_init >> 2) ^ (c_init >> 3)) << 31);
+  for (int n = 1; n < 50; n++) gold_step_h(x1, x2);
+}
+
+/* the first n Gold words of c_init */
+static void gold_seq_h(uint32_t c_init, uint32_t *w, size_t n)
+{
+  uint32_t x1, x2;
+  gold_start_h(c_init, &x1, &x2);
+  for (size_t i = 0; i < n; i++) {
+    gold_step_h(&x1, &x2);
+    w[i] = x1 ^ x2;
+  }
+}
+
+/* the column permutation of the convolutional code's sub-block interleaver (36.212 Table 5.1.4-2) */
+static const uint8_t bitrev_cc[32] = {1, 17, 9, 25, 5, 21, 13, 29, 3, 19, 11, 27, 7, 23, 15, 31,
+                                      0, 16, 8, 24, 4, 20, 12, 28, 2, 18, 10, 26, 6, 22, 14, 30};
+
 /* lte_gold (LTE_REFSIG/lte_gold.c:52-93): CRS Gold words [ns][pilot l][14] */
 /* 14 CRS Gold words of slot ns, symbol lsym of the slot: c_init = 2^10 (7(ns+1) + lsym + 1)
  * (2 Nid + 1) + 2 Nid + N_CP (lte_gold.c:52-93; lsym = 1 for the port-2/3 extension) */
 static void gold_words_h(const oai4g_frame_parms_t *fp, uint32_t ns, uint32_t lsym, uint32_t w[14])
 {
   const uint32_t Ncp = 1 - fp->Ncp, Nid = fp->Nid_cell;
-  uint32_t x1 = 1u + (1u << 31);
-  uint32_t x2 = Ncp + (Nid << 1) + (((1 + (Nid << 1)) * (1 + lsym + 7 * (1 + ns))) << 10);
-  x2 ^= (x2 ^ (x2 >> 1) ^ (x2 >> 2) ^ (x2 >> 3)) << 31;
-  for (int n = 1; n < 50; n++) gold_step_h(&x1, &x2);
-  for (int n = 0; n < 14; n++) {
-    gold_step_h(&x1, &x2);
-    w[n] = x1 ^ x2;
-  }
+  gold_seq_h(Ncp + (Nid << 1) + (((1 + (Nid << 1)) * (1 + lsym + 7 * (1 + ns))) << 10), w, 14);
 }
 
 static void lte_gold_table_h(const oai4g_frame_parms_t *fp, uint32_t t[20][2][14])
@@ -305,6 +322,66 @@ static uint8_t *scratch(size_t bytes)
   }
   return g_scr.buf;
 }
+
+static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+/* The staging of one drop-in call.  Regions of the thread's scratch buffer are declared in order: add(bytes,
+ * slack), where slack is what a kernel may touch past the payload (a comment names the access; where there is
+ * none, the slack is what the earlier hand-written layout left there and no reader is known).  Every region
+ * starts 256-byte aligned.  open() asks the thread scratch once for the total the declarations add up to, and
+ * every transfer is checked against the declared sizes before it is issued; it may run on from region r into
+ * the regions behind it, up to the end of region `last`.  Everything runs on g_scr.s. */
+namespace {
+struct stage_t {
+  enum { MAX_REGIONS = 12 };
+  const char *who;
+  size_t off[MAX_REGIONS + 1] = {0}, len[MAX_REGIONS] = {0};
+  int n = 0;
+  bool full = false;
+  uint8_t *buf = nullptr;
+
+  explicit stage_t(const char *w) : who(w) {}
+  int add(size_t bytes, size_t slack = 0)
+  {
+    if (n == MAX_REGIONS) { full = true; return 0; }        /* open() refuses */
+    len[n] = bytes + slack;
+    off[n + 1] = off[n] + up256(len[n]);
+    return n++;
+  }
+  bool open()
+  {
+    buf = full ? nullptr : scratch(off[n]);
+    if (!buf) set_err("%s: scratch allocation failed", who);
+    return buf != nullptr;
+  }
+  template <class T = uint8_t> T *ptr(int r, size_t at = 0) const { return (T *)(buf + off[r] + at); }
+  uint8_t *span(int r, size_t at, size_t bytes, int last) const      /* null (and the error set) outside the regions */
+  {
+    if (last < r) last = r;
+    const size_t room = r >= 0 && last < n ? off[last] + len[last] - off[r] : 0;
+    if (buf && at <= room && bytes <= room - at) return ptr(r, at);
+    set_err("%s: transfer of %zu bytes at %zu leaves staging region %d..%d (%zu bytes)", who, bytes, at, r, last, room);
+    fprintf(stderr, "[openair4g_amd] %s\n", g_err);
+    return nullptr;
+  }
+  hipError_t up(int r, const void *src, size_t bytes, size_t at = 0, int last = -1) const
+  {
+    uint8_t *d = span(r, at, bytes, last);
+    return d ? hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, g_scr.s) : hipErrorInvalidValue;
+  }
+  hipError_t down(void *dst, int r, size_t bytes, size_t at = 0, int last = -1) const
+  {
+    const uint8_t *d = span(r, at, bytes, last);
+    return d ? hipMemcpyAsync(dst, d, bytes, hipMemcpyDeviceToHost, g_scr.s) : hipErrorInvalidValue;
+  }
+  hipError_t zero(int r, size_t bytes, int last) const
+  {
+    uint8_t *d = span(r, 0, bytes, last);
+    return d ? hipMemsetAsync(d, 0, bytes, g_scr.s) : hipErrorInvalidValue;
+  }
+  hipError_t sync() const { return hipStreamSynchronize(g_scr.s); }
+};
+}  // namespace
 
 #define NEED_INIT(ret)                                          \
   do {                                                          \
@@ -1378,20 +1455,8 @@ static int upload_gold(oai4g_tx_config *cfg)
   for (uint32_t sf = 0; sf < 10; sf++)
     for (uint32_t cw = 0; cw < h.n_cw; cw++) {
       const uint32_t c_init = (h.rnti << 14) + (h.cw[cw].q << 13) + (sf << 9) + h.Nid_cell;
-      uint32_t x1 = 1u + (1u << 31), x2 = c_init ^ ((c_init ^ (c_init >> 1) ^ (c_init >> 2) ^ (c_init >> 3)) << 31);
-      auto step = [&]() {
-        x1 = (x1 >> 1) ^ (x1 >> 4);
-        x1 = x1 ^ (x1 << 31) ^ (x1 << 28);
-        x2 = (x2 >> 1) ^ (x2 >> 2) ^ (x2 >> 3) ^ (x2 >> 4);
-        x2 = x2 ^ (x2 << 31) ^ (x2 << 30) ^ (x2 << 29) ^ (x2 << 28);
-      };
-      for (int n = 1; n < 50; n++) step();
       const size_t nw = std::min(stride, (size_t)(h.cw[cw].G[sf] + 31) / 32);
-      uint32_t *o = g.data() + ((size_t)sf * h.n_cw + cw) * stride;
-      for (size_t w = 0; w < nw; w++) {
-        step();
-        o[w] = x1 ^ x2;
-      }
+      gold_seq_h(c_init, g.data() + ((size_t)sf * h.n_cw + cw) * stride, nw);
     }
   if (cfg->d_gold) hipFree(cfg->d_gold);
   cfg->d_gold = nullptr;
@@ -1436,6 +1501,16 @@ static void release_cfg(oai4g_tx_config *cfg)
   cfg->d = nullptr;
   cfg->d_remap = nullptr;
 }
+
+/* releases a drop-in's stack configuration on every path out of it.  Unless the caller has already
+ * synchronised (done), it waits for the scratch stream first: a launched kernel may still read it. */
+namespace {
+struct cfg_scope_t {
+  oai4g_tx_config *cfg;
+  bool done = false;
+  ~cfg_scope_t() { if (!done && g_scr.s) hipStreamSynchronize(g_scr.s); release_cfg(cfg); }
+};
+}  // namespace
 
 extern "C" oai4g_tx_config_t *oai4g_tx_config_create(const oai4g_tx_params_t *p)
 {
@@ -1759,15 +1834,13 @@ extern "C" int32_t oai4g_signal_energy(const int32_t *input, uint32_t length)
   NEED_INIT(-1);
   if (!input || length < 2) { set_err("signal_energy: bad arguments"); return -1; }
   int32_t e = -1;
-  uint8_t *buf = scratch((size_t)length * 4 + 256);
-  if (!buf) { set_err("signal_energy: scratch allocation failed"); return -1; }
-  int32_t *d_x = (int32_t *)buf, *d_e = (int32_t *)(buf + (((size_t)length * 4 + 127) & ~(size_t)127));
-  if (hipMemcpyAsync(d_x, input, (size_t)length * 4, hipMemcpyHostToDevice, g_scr.s) != hipSuccess ||
-      oai4g_launch_signal_energy(d_x, 1, 0, length, d_e, g_scr.s) != hipSuccess ||
-      hipMemcpyAsync(&e, d_e, 4, hipMemcpyDeviceToHost, g_scr.s) != hipSuccess || hipStreamSynchronize(g_scr.s) != hipSuccess) {
-    set_err("signal_energy: device call failed");
-    return -1;
-  }
+  stage_t st("signal_energy");
+  const int r_x = st.add((size_t)length * 4), r_e = st.add(4, 252);
+  if (!st.open()) return -1;
+  HCK(st.up(r_x, input, (size_t)length * 4), -1);
+  HCK(oai4g_launch_signal_energy(st.ptr<int32_t>(r_x), 1, 0, length, st.ptr<int32_t>(r_e), g_scr.s), -1);
+  HCK(st.down(&e, r_e, 4), -1);
+  HCK(st.sync(), -1);
   return e;
 }
 
@@ -1863,11 +1936,7 @@ extern "C" void oai4g_free_dlsch(oai4g_dlsch_t *d)
 /* lte_gold_generic (lte_gold.c:151-177): host-side scalar helper */
 extern "C" uint32_t oai4g_lte_gold_generic(uint32_t *x1, uint32_t *x2, uint8_t reset)
 {
-  if (reset) {
-    *x1 = 1u + (1u << 31);
-    *x2 = *x2 ^ ((*x2 ^ (*x2 >> 1) ^ (*x2 >> 2) ^ (*x2 >> 3)) << 31);
-    for (int n = 1; n < 50; n++) gold_step_h(x1, x2);
-  }
+  if (reset) gold_start_h(*x2, x1, x2);
   gold_step_h(x1, x2);
   return *x1 ^ *x2;
 }
@@ -1879,14 +1948,14 @@ static uint32_t crc_dropin(const uint8_t *in, int bitlen, uint32_t poly_top)
 {
   NEED_INIT(0);
   uint32_t nbytes = (uint32_t)(bitlen + 7) / 8;
-  uint8_t *buf = scratch(nbytes + 64);
-  if (!buf) { set_err("scratch allocation failed"); return 0; }
-  uint32_t *d_out = (uint32_t *)(buf + ((nbytes + 15) & ~15u));
+  stage_t st("crc24");
+  const int r_in = st.add(nbytes), r_out = st.add(4, 60);
+  if (!st.open()) return 0;
   uint32_t out = 0;
-  HCK(hipMemcpyAsync(buf, in, nbytes, hipMemcpyHostToDevice, g_scr.s), 0);
-  HCK(oai4g_launch_crc24(buf, bitlen, poly_top, d_out, g_scr.s), 0);
-  HCK(hipMemcpyAsync(&out, d_out, 4, hipMemcpyDeviceToHost, g_scr.s), 0);
-  HCK(hipStreamSynchronize(g_scr.s), 0);
+  HCK(st.up(r_in, in, nbytes), 0);
+  HCK(oai4g_launch_crc24(st.ptr(r_in), bitlen, poly_top, st.ptr<uint32_t>(r_out), g_scr.s), 0);
+  HCK(st.down(&out, r_out, 4), 0);
+  HCK(st.sync(), 0);
   return out;
 }
 
@@ -1927,12 +1996,13 @@ extern "C" void oai4g_threegpplte_turbo_encoder(const uint8_t *input, uint16_t i
     printf("Illegal frame length!\n");
     return;
   }
-  uint8_t *buf = scratch(1024 + 3 * 6144 + 64);
-  if (!buf) return;
-  HCK(hipMemcpyAsync(buf, input, input_length_bytes, hipMemcpyHostToDevice, g_scr.s), );
-  HCK(oai4g_launch_turbo_bytes(buf, input_length_bytes, buf + 1024, f1, f2, g_scr.s), );
-  HCK(hipMemcpyAsync(output, buf + 1024, 3 * K + 12, hipMemcpyDeviceToHost, g_scr.s), );
-  HCK(hipStreamSynchronize(g_scr.s), );
+  stage_t st("threegpplte_turbo_encoder");
+  const int r_in = st.add(6144 / 8, 256), r_out = st.add(3 * 6144 + 12, 52);   /* the largest block */
+  if (!st.open()) return;
+  HCK(st.up(r_in, input, input_length_bytes), );
+  HCK(oai4g_launch_turbo_bytes(st.ptr(r_in), input_length_bytes, st.ptr(r_out), f1, f2, g_scr.s), );
+  HCK(st.down(output, r_out, 3 * K + 12), );
+  HCK(st.sync(), );
 }
 
 extern "C" uint32_t oai4g_sub_block_interleaving_turbo(uint32_t D, uint8_t *d, uint8_t *w)
@@ -1940,12 +2010,13 @@ extern "C" uint32_t oai4g_sub_block_interleaving_turbo(uint32_t D, uint8_t *d, u
   NEED_INIT(0);
   uint32_t R = (D + 31) >> 5, Kpi = R << 5;
   size_t dbytes = 96 + 3 * (size_t)D + 3;
-  uint8_t *buf = scratch(dbytes + 3 * Kpi + 64);
-  if (!buf) return 0;
-  HCK(hipMemcpyAsync(buf, d - 96, dbytes, hipMemcpyHostToDevice, g_scr.s), 0);
-  HCK(oai4g_launch_subblock_bytes(D, buf, buf + ((dbytes + 15) & ~(size_t)15), g_scr.s), 0);
-  HCK(hipMemcpyAsync(w, buf + ((dbytes + 15) & ~(size_t)15), 3 * Kpi, hipMemcpyDeviceToHost, g_scr.s), 0);
-  HCK(hipStreamSynchronize(g_scr.s), 0);
+  stage_t st("sub_block_interleaving_turbo");
+  const int r_d = st.add(dbytes), r_w = st.add(3 * (size_t)Kpi, 64);
+  if (!st.open()) return 0;
+  HCK(st.up(r_d, d - 96, dbytes), 0);
+  HCK(oai4g_launch_subblock_bytes(D, st.ptr(r_d), st.ptr(r_w), g_scr.s), 0);
+  HCK(st.down(w, r_w, 3 * (size_t)Kpi), 0);
+  HCK(st.sync(), 0);
   d[3 * D + 2] = d[2]; /* side effect kept (lte_rate_matching.c:75) */
   return R;
 }
@@ -1969,13 +2040,13 @@ extern "C" uint32_t oai4g_lte_rate_matching_turbo(uint32_t RTC, uint32_t G, cons
   else E = Nl * Qm * ((GpmodC == 0 ? 0 : 1) + (Gp / C));
   uint32_t ncol8 = RTC << 3;
   uint32_t k0 = RTC * (2 + rvidx * ((Ncb % ncol8 ? 1 : 0) + Ncb / ncol8) * 2);
-  size_t woff = 0, eoff = (Ncb + 63) & ~(size_t)63, soff = eoff + ((E + 63) & ~(size_t)63);
-  uint8_t *buf = scratch(soff + 64);
-  if (!buf) return 0;
-  HCK(hipMemcpyAsync(buf + woff, w, Ncb, hipMemcpyHostToDevice, g_scr.s), 0);
-  HCK(oai4g_launch_rm_bytes(buf + woff, Ncb, k0, E, buf + eoff, (uint32_t *)(buf + soff), g_scr.s), 0);
-  HCK(hipMemcpyAsync(e, buf + eoff, E, hipMemcpyDeviceToHost, g_scr.s), 0);
-  HCK(hipStreamSynchronize(g_scr.s), 0);
+  stage_t st("lte_rate_matching_turbo");
+  const int r_w = st.add(Ncb), r_e = st.add(E), r_s = st.add(4, 60);   /* s: the status word */
+  if (!st.open()) return 0;
+  HCK(st.up(r_w, w, Ncb), 0);
+  HCK(oai4g_launch_rm_bytes(st.ptr(r_w), Ncb, k0, E, st.ptr(r_e), st.ptr<uint32_t>(r_s), g_scr.s), 0);
+  HCK(st.down(e, r_e, E), 0);
+  HCK(st.sync(), 0);
   return E;
 }
 
@@ -2062,24 +2133,25 @@ static int dlsch_encoding_retx(const oai4g_frame_parms_t *fp, uint8_t num_pdcch_
     blk[r].E = r < C - GpmodC ? Nl * Qm * (Gp / C) : Nl * Qm * ((GpmodC ? 1 : 0) + Gp / C);
     blk[r].eoff = etot;
     etot += blk[r].E;
-    wtot += (Ncb + 63) & ~(size_t)63;
+    wtot += up256(Ncb);
     max_Ncb = Ncb > max_Ncb ? Ncb : max_Ncb;
   }
   if (etot == 0) return 0;
   if (etot > OAI4G_MAX_CHANNEL_BITS) { set_err("dlsch_encoding: %u e bits", etot); return -1; }
-  const size_t off_blk = wtot, off_s = off_blk + sizeof(blk), off_e = off_s + st_bytes;
-  std::vector<uint8_t> up(off_e, 0);
+  stage_t st("dlsch_encoding");
+  const int r_w = st.add(wtot), r_blk = st.add(sizeof(blk)), r_s = st.add(st_bytes), r_e = st.add(etot, 64);
+  const size_t up_bytes = st.off[r_s] + st_bytes, e_at = st.off[r_e] - st.off[r_s];   /* host images follow the regions */
+  std::vector<uint8_t> up(up_bytes, 0);
   for (uint32_t r = 0; r < C; r++)
     if (blk[r].E) memcpy(up.data() + blk[r].woff, h->w[r], blk[r].Ncb);
-  memcpy(up.data() + off_blk, blk, sizeof(blk));
-  uint8_t *buf = scratch(off_e + etot + 64);
-  if (!buf) return -1;
-  HCK(hipMemcpyAsync(buf, up.data(), off_e, hipMemcpyHostToDevice, g_scr.s), -1);
-  HCK(oai4g_launch_rm_bytes_blocks(buf, (const rm_blk_t *)(buf + off_blk), (int)C, max_Ncb, buf + off_e,
-                                   (uint32_t *)(buf + off_s), g_scr.s), -1);
-  std::vector<uint8_t> down(st_bytes + etot);
-  HCK(hipMemcpyAsync(down.data(), buf + off_s, down.size(), hipMemcpyDeviceToHost, g_scr.s), -1);
-  HCK(hipStreamSynchronize(g_scr.s), -1);
+  memcpy(up.data() + st.off[r_blk], blk, sizeof(blk));
+  if (!st.open()) return -1;
+  HCK(st.up(r_w, up.data(), up_bytes, 0, r_s), -1);
+  HCK(oai4g_launch_rm_bytes_blocks(st.ptr(r_w), st.ptr<const rm_blk_t>(r_blk), (int)C, max_Ncb, st.ptr(r_e),
+                                   st.ptr<uint32_t>(r_s), g_scr.s), -1);
+  std::vector<uint8_t> down(e_at + etot);
+  HCK(st.down(down.data(), r_s, down.size(), 0, r_e), -1);
+  HCK(st.sync(), -1);
   /* a row without a single non-NULL byte has nothing to repeat (the block's status word is 1, its e
    * bytes were not written): no stored w of a first round looks like that, so e stays as it was */
   uint32_t status[OAI4G_MAX_SEGMENTS];
@@ -2089,7 +2161,7 @@ static int dlsch_encoding_retx(const oai4g_frame_parms_t *fp, uint8_t num_pdcch_
       set_err("dlsch_encoding: round %u, w[%u] holds no non-NULL entry below Ncb %u", h->round, r, blk[r].Ncb);
       return -1;
     }
-  memcpy(h->e, down.data() + st_bytes, etot);
+  memcpy(h->e, down.data() + e_at, etot);
   return 0;
 }
 
@@ -2109,20 +2181,24 @@ extern "C" int oai4g_dlsch_encoding(uint8_t *a, const oai4g_frame_parms_t *frame
   int rc = derive_cfg(&cfg, &p, Nl, false, -1);
   bool rm_fail = rc == -2; /* reference: every block's rate matcher returns E = 0, e untouched */
   if (rc != 0 && !rm_fail) return -1;
-  if (upload_cfg(&cfg) != 0) { release_cfg(&cfg); return -1; }
+  cfg_scope_t scope = {&cfg};
+  if (upload_cfg(&cfg) != 0) return -1;
   cw_dev_t &c = cfg.h.cw[0];
   uint32_t G = c.G[subframe % 10];
-  size_t off_pay = 0, off_b = 16 * 1024, off_c = off_b + 16 * 1024, off_d = off_c + 16 * (8 + 3 + 768),
-         off_w = off_d + 16 * (size_t)OAI4G_D_BYTES, off_e = off_w + 16 * (size_t)OAI4G_W_BYTES;
-  uint8_t *buf = scratch(off_e + OAI4G_MAX_CHANNEL_BITS + 64);
-  if (!buf) { release_cfg(&cfg); return -1; }
-  HCK(hipMemcpyAsync(buf + off_pay, a, c.A_bytes, hipMemcpyHostToDevice, g_scr.s), -1);
-  enc_debug_t dbg = {buf + off_c, buf + off_d, buf + off_w, rm_fail ? nullptr : buf + off_e, buf + off_b};
-  HCK(oai4g_launch_encode_debug(cfg.d, &cfg.h, 0, subframe % 10, buf + off_pay, dbg, g_scr.s), -1);
+  /* payload | b | c | d | w | e, downloaded in one copy: the host image hb follows the regions */
+  const size_t n_seg = OAI4G_MAX_SEGMENTS;                  /* 768 bytes a block */
+  stage_t st("dlsch_encoding");
+  const int r_pay = st.add(n_seg * 768, 4096), r_b = st.add(n_seg * 768, 4096), r_c = st.add(n_seg * (8 + 3 + 768));
+  const int r_d = st.add(n_seg * OAI4G_D_BYTES), r_w = st.add(n_seg * OAI4G_W_BYTES), r_e = st.add(OAI4G_MAX_CHANNEL_BITS, 64);
+  const size_t off_b = st.off[r_b], off_c = st.off[r_c], off_d = st.off[r_d], off_w = st.off[r_w], off_e = st.off[r_e];
+  if (!st.open()) return -1;
+  HCK(st.up(r_pay, a, c.A_bytes), -1);
+  enc_debug_t dbg = {st.ptr(r_c), st.ptr(r_d), st.ptr(r_w), rm_fail ? nullptr : st.ptr(r_e), st.ptr(r_b)};
+  HCK(oai4g_launch_encode_debug(cfg.d, &cfg.h, 0, subframe % 10, st.ptr(r_pay), dbg, g_scr.s), -1);
   std::vector<uint8_t> hb(off_e + G);
-  HCK(hipMemcpyAsync(hb.data(), buf, off_e + G, hipMemcpyDeviceToHost, g_scr.s), -1);
-  HCK(hipStreamSynchronize(g_scr.s), -1);
-  release_cfg(&cfg);
+  HCK(st.down(hb.data(), r_pay, off_e + G, 0, r_e), -1);
+  HCK(st.sync(), -1);
+  scope.done = true;
   /* CRC appended into the caller's buffer and copied to b (dlsch_coding.c:296-305) */
   memcpy(a + c.A_bytes, hb.data() + off_b + c.A_bytes, 3);
   h->B = c.TBS + 24;
@@ -2148,12 +2224,13 @@ extern "C" void oai4g_dlsch_scrambling(const oai4g_frame_parms_t *frame_parms, i
                                       frame_parms->Nid_cell
                                 : ((uint32_t)(Ns >> 1) << 9) + frame_parms->Nid_cell_mbsfn;   /* :70-72 */
   int n = (1 + (G >> 5)) * 32; /* the reference writes past G (dlsch_scrambling.c:83-92) */
-  uint8_t *buf = scratch((size_t)n + 64);
-  if (!buf) return;
-  HCK(hipMemcpyAsync(buf, e, n, hipMemcpyHostToDevice, g_scr.s), );
-  HCK(oai4g_launch_scramble_bytes(buf, n, x2, g_gx1, g_gx2j, g_scr.s), );
-  HCK(hipMemcpyAsync(e, buf, n, hipMemcpyDeviceToHost, g_scr.s), );
-  HCK(hipStreamSynchronize(g_scr.s), );
+  stage_t st("dlsch_scrambling");
+  const int r_e = st.add((size_t)n, 64);      /* n covers the write past G */
+  if (!st.open()) return;
+  HCK(st.up(r_e, e, n), );
+  HCK(oai4g_launch_scramble_bytes(st.ptr(r_e), n, x2, g_gx1, g_gx2j, g_scr.s), );
+  HCK(st.down(e, r_e, n), );
+  HCK(st.sync(), );
 }
 
 extern "C" int oai4g_dlsch_modulation(int32_t **txdataF, int16_t amp, uint32_t subframe_offset,
@@ -2186,32 +2263,28 @@ extern "C" int oai4g_dlsch_modulation(int32_t **txdataF, int16_t amp, uint32_t s
   }
   int rc = derive_cfg(&cfg, &p, Nl, true, (int)(subframe_offset % 10));
   if (rc != 0 && rc != -2) return -1;
-  if (upload_cfg(&cfg) != 0) { release_cfg(&cfg); return -1; }
+  cfg_scope_t scope = {&cfg};
+  if (upload_cfg(&cfg) != 0) return -1;
   int sf = (int)(subframe_offset % 10);
   uint32_t N = cfg.h.N, nsymb = cfg.h.nsymb, nant = cfg.h.n_ant;
-  size_t grid_bytes = (size_t)nant * nsymb * N * 4;
+  const size_t ant_bytes = (size_t)nsymb * N * 4;
   uint32_t n_re = (uint32_t)cfg.re_count[sf];
-  size_t e0_bytes = (size_t)n_re * cfg.h.cw[0].Qm + 64, e1_bytes = p.n_cw > 1 ? (size_t)n_re * cfg.h.cw[1].Qm + 64 : 0;
-  size_t off_e0 = (grid_bytes + 255) & ~(size_t)255, off_e1 = off_e0 + ((e0_bytes + 255) & ~(size_t)255);
-  uint8_t *buf = scratch(off_e1 + e1_bytes + 64);
-  if (!buf) { release_cfg(&cfg); return -1; }
+  const size_t e0_bytes = (size_t)n_re * cfg.h.cw[0].Qm, e1_bytes = p.n_cw > 1 ? (size_t)n_re * cfg.h.cw[1].Qm : 0;
+  stage_t st("dlsch_modulation");
+  const int r_grid = st.add(nant * ant_bytes);
+  /* k_modulate_bytes loads 4 unaligned bytes past n_re Qm: 64 each; the last 64 have no known reader */
+  const int r_e0 = st.add(e0_bytes, 64), r_e1 = st.add(e1_bytes, 64 + 64);
+  if (!st.open()) return -1;
   size_t sym_off = (size_t)N * subframe_offset * nsymb;
-  for (uint32_t aa = 0; aa < nant; aa++)
-    HCK(hipMemcpyAsync(buf + (size_t)aa * nsymb * N * 4, txdataF[aa] + sym_off, (size_t)nsymb * N * 4,
-                       hipMemcpyHostToDevice, g_scr.s), -1);
-  HCK(hipMemcpyAsync(buf + off_e0, h0->e, (size_t)n_re * cfg.h.cw[0].Qm, hipMemcpyHostToDevice, g_scr.s), -1);
-  if (p.n_cw > 1)
-    HCK(hipMemcpyAsync(buf + off_e1, dlsch1->harq_processes[dlsch0->current_harq_pid]->e,
-                       (size_t)n_re * cfg.h.cw[1].Qm, hipMemcpyHostToDevice, g_scr.s), -1);
-  HCK(oai4g_launch_modulate_bytes(cfg.d, &cfg.h, sf, buf + off_e0, p.n_cw > 1 ? buf + off_e1 : nullptr,
-                                  (int32_t *)buf, g_scr.s), -1);
-  for (uint32_t aa = 0; aa < nant; aa++)
-    HCK(hipMemcpyAsync(txdataF[aa] + sym_off, buf + (size_t)aa * nsymb * N * 4, (size_t)nsymb * N * 4,
-                       hipMemcpyDeviceToHost, g_scr.s), -1);
-  HCK(hipStreamSynchronize(g_scr.s), -1);
-  const int ret = cfg.re_alloc[sf];
-  release_cfg(&cfg);
-  return ret;
+  for (uint32_t aa = 0; aa < nant; aa++) HCK(st.up(r_grid, txdataF[aa] + sym_off, ant_bytes, aa * ant_bytes), -1);
+  HCK(st.up(r_e0, h0->e, e0_bytes), -1);
+  if (p.n_cw > 1) HCK(st.up(r_e1, dlsch1->harq_processes[dlsch0->current_harq_pid]->e, e1_bytes), -1);
+  HCK(oai4g_launch_modulate_bytes(cfg.d, &cfg.h, sf, st.ptr(r_e0), p.n_cw > 1 ? st.ptr(r_e1) : nullptr,
+                                  st.ptr<int32_t>(r_grid), g_scr.s), -1);
+  for (uint32_t aa = 0; aa < nant; aa++) HCK(st.down(txdataF[aa] + sym_off, r_grid, ant_bytes, aa * ant_bytes), -1);
+  HCK(st.sync(), -1);
+  scope.done = true;
+  return cfg.re_alloc[sf];
 }
 
 /* ------------------------------------------------------------------------------------------
@@ -2221,16 +2294,15 @@ static int run_ofdm(const int32_t *input, size_t in_n, int32_t *output, size_t o
                     int nsym, const ofdm_sym_t *syms, int scale)
 {
   NEED_INIT(-1);
-  size_t in_bytes = in_n * 4, out_off = (in_bytes + 255) & ~(size_t)255;
-  uint8_t *buf = scratch(out_off + out_n * 4 + 64);
-  if (!buf) return -1;
-  int32_t *d_in = (int32_t *)buf, *d_out = (int32_t *)(buf + out_off);
-  HCK(hipMemcpyAsync(d_in, input, in_bytes, hipMemcpyHostToDevice, g_scr.s), -1);
+  stage_t st("ofdm");
+  const int r_in = st.add(in_n * 4), r_out = st.add(out_n * 4, 64);
+  if (!st.open()) return -1;
+  HCK(st.up(r_in, input, in_n * 4), -1);
   /* the output window is read-modify-write: samples outside the written symbols stay intact */
-  HCK(hipMemcpyAsync(d_out, output + out_lo, out_n * 4, hipMemcpyHostToDevice, g_scr.s), -1);
-  HCK(oai4g_launch_ofdm(d_in, d_out, log2n, nsym, syms, scale, g_tw, g_scr.s), -1);
-  HCK(hipMemcpyAsync(output + out_lo, d_out, out_n * 4, hipMemcpyDeviceToHost, g_scr.s), -1);
-  HCK(hipStreamSynchronize(g_scr.s), -1);
+  HCK(st.up(r_out, output + out_lo, out_n * 4), -1);
+  HCK(oai4g_launch_ofdm(st.ptr<int32_t>(r_in), st.ptr<int32_t>(r_out), log2n, nsym, syms, scale, g_tw, g_scr.s), -1);
+  HCK(st.down(output + out_lo, r_out, out_n * 4), -1);
+  HCK(st.sync(), -1);
   return 0;
 }
 
@@ -2327,20 +2399,16 @@ static int run_crs(int32_t *const *grids, int n_grids, size_t grid_res, const cr
   uint32_t gt[20][2][14];
   lte_gold_table_h(fp, gt);
   const size_t gbytes = sizeof(gt), jbytes = (size_t)n_jobs * sizeof(crs_job_t), dbytes = (size_t)n_grids * grid_res * 4;
-  uint8_t *buf = scratch(gbytes + jbytes + dbytes + 256);
-  if (!buf) return -1;
-  uint32_t *d_gold = (uint32_t *)buf;
-  crs_job_t *d_jobs = (crs_job_t *)(buf + ((gbytes + 15) & ~(size_t)15));
-  int32_t *d_grid = (int32_t *)(buf + ((gbytes + 15) & ~(size_t)15) + ((jbytes + 255) & ~(size_t)255));
-  HCK(hipMemcpyAsync(d_gold, gt, gbytes, hipMemcpyHostToDevice, g_scr.s), -1);
-  HCK(hipMemcpyAsync(d_jobs, jobs, jbytes, hipMemcpyHostToDevice, g_scr.s), -1);
-  for (int g = 0; g < n_grids; g++)
-    HCK(hipMemcpyAsync(d_grid + g * grid_res, grids[g], grid_res * 4, hipMemcpyHostToDevice, g_scr.s), -1);
-  HCK(oai4g_launch_crs(d_grid, d_jobs, n_jobs, d_gold, amp, fp->ofdm_symbol_size, fp->N_RB_DL, fp->nushift,
-                       fp->first_carrier_offset, g_scr.s), -1);
-  for (int g = 0; g < n_grids; g++)
-    HCK(hipMemcpyAsync(grids[g], d_grid + g * grid_res, grid_res * 4, hipMemcpyDeviceToHost, g_scr.s), -1);
-  HCK(hipStreamSynchronize(g_scr.s), -1);
+  stage_t st("crs");
+  const int r_gold = st.add(gbytes), r_jobs = st.add(jbytes), r_grid = st.add(dbytes, 256);
+  if (!st.open()) return -1;
+  HCK(st.up(r_gold, gt, gbytes), -1);
+  HCK(st.up(r_jobs, jobs, jbytes), -1);
+  for (int g = 0; g < n_grids; g++) HCK(st.up(r_grid, grids[g], grid_res * 4, g * grid_res * 4), -1);
+  HCK(oai4g_launch_crs(st.ptr<int32_t>(r_grid), st.ptr<crs_job_t>(r_jobs), n_jobs, st.ptr<uint32_t>(r_gold), amp,
+                       fp->ofdm_symbol_size, fp->N_RB_DL, fp->nushift, fp->first_carrier_offset, g_scr.s), -1);
+  for (int g = 0; g < n_grids; g++) HCK(st.down(grids[g], r_grid, grid_res * 4, g * grid_res * 4), -1);
+  HCK(st.sync(), -1);
   return 0;
 }
 
@@ -2479,24 +2547,22 @@ extern "C" uint8_t oai4g_phy_threegpplte_turbo_decoder8(const int16_t *y, uint8_
     set_err("turbo decoder8: n %u / crc %u outside the restated scope", n, crc_type);
     return 255;
   }
-  const size_t ly = 3 * (size_t)n + 16, b_y = (ly * 2 + 255) & ~(size_t)255, b_o = ((size_t)n / 8 + 256) & ~(size_t)255;
-  const size_t b_s = oai4g_td8_scratch_bytes(n, 1);
-  uint8_t *buf = scratch(b_y + b_o + 256 + b_s);
-  if (!buf) return 255;
-  int16_t *dy = (int16_t *)buf;
-  uint8_t *dout = buf + b_y, *dit = dout + b_o, *dscr = dit + 256;
+  const size_t ly = 3 * (size_t)n + 16;
+  stage_t st("turbo decoder8");
+  const int r_y = st.add(ly * 2), r_out = st.add((size_t)n / 8, 256), r_it = st.add(1, 255);
+  const int r_scr = st.add(oai4g_td8_scratch_bytes(n, 1));
+  if (!st.open()) return 255;
   std::vector<int16_t> h(ly, 0);
   memcpy(h.data(), y, (3 * (size_t)n + 12) * 2);
   uint8_t itc = 255;
-  if (hipMemcpyAsync(dy, h.data(), ly * 2, hipMemcpyHostToDevice, g_scr.s) != hipSuccess ||
-      hipMemcpyAsync(dout, decoded_bytes, n / 8, hipMemcpyHostToDevice, g_scr.s) != hipSuccess ||
-      oai4g_td8_batch(1, n, dy, ly, dout, n / 8, dit, max_iterations, crc_type, F, dscr, g_scr.s) != 0 ||
-      hipMemcpyAsync(decoded_bytes, dout, n / 8, hipMemcpyDeviceToHost, g_scr.s) != hipSuccess ||
-      hipMemcpyAsync(&itc, dit, 1, hipMemcpyDeviceToHost, g_scr.s) != hipSuccess ||
-      hipStreamSynchronize(g_scr.s) != hipSuccess) {
-    set_err("turbo decoder8: HIP error");
+  HCK(st.up(r_y, h.data(), ly * 2), 255);
+  HCK(st.up(r_out, decoded_bytes, n / 8), 255);
+  if (oai4g_td8_batch(1, n, st.ptr<int16_t>(r_y), ly, st.ptr(r_out), n / 8, st.ptr(r_it), max_iterations, crc_type, F,
+                      st.ptr(r_scr), g_scr.s) != 0)
     return 255;
-  }
+  HCK(st.down(decoded_bytes, r_out, n / 8), 255);
+  HCK(st.down(&itc, r_it, 1), 255);
+  HCK(st.sync(), 255);
   return itc;
 }
 
@@ -2678,7 +2744,7 @@ extern "C" int oai4g_ul_config_C(const oai4g_ul_config_t *cfg) { return (int)cfg
 extern "C" uint32_t oai4g_ul_config_G_offset(const oai4g_ul_config_t *cfg, int r) { return cfg->h.off[r]; }
 extern "C" uint32_t oai4g_ul_config_E(const oai4g_ul_config_t *cfg, int r) { return cfg->h.E[r]; }
 
-static int ul_scratch(oai4g_ul_config_t *cfg, int n_tb)
+static int ul_reserve(oai4g_ul_config_t *cfg, int n_tb)
 {
   if (n_tb <= cfg->cap) return 0;
   if (cfg->d_dfull) hipFree(cfg->d_dfull);
@@ -2726,7 +2792,7 @@ extern "C" int oai4g_ul_decode_batch(oai4g_ul_config_t *cfg, int n_tb, const int
   NEED_INIT(-1);
   if (n_tb <= 0) return 0;
   if (c_stride < cfg->Kplus / 8 || e_stride < cfg->G) { set_err("ul_decode_batch: strides too small"); return -1; }
-  if (ul_scratch(cfg, n_tb) != 0) return -1;
+  if (ul_reserve(cfg, n_tb) != 0) return -1;
   hipStream_t s = (hipStream_t)stream;
   HCK(oai4g_launch_ul_rm_deint(cfg->d, &cfg->h, n_tb, d_e, e_stride, cfg->d_dfull, cfg->d_stride, s), -1);
   return ul_decode_rows(cfg, n_tb, d_c, c_stride, d_iters, s);
@@ -2747,7 +2813,7 @@ extern "C" int oai4g_ul_decode_batch_harq(oai4g_ul_config_t *cfg, int n_tb, cons
     set_err("ul_decode_batch_harq: strides too small");
     return -1;
   }
-  if (ul_scratch(cfg, n_tb) != 0) return -1;
+  if (ul_reserve(cfg, n_tb) != 0) return -1;
   hipStream_t s = (hipStream_t)stream;
   HCK(oai4g_launch_ul_rm_harq(cfg->d, &cfg->h, n_tb, d_e, e_stride, d_w, w_stride, rvidx, clear, cfg->d_dfull,
                               cfg->d_stride, s), -1);
@@ -2766,7 +2832,7 @@ extern "C" int oai4g_ul_decode_batch_harq_tb(oai4g_ul_config_t *cfg, int n_tb, c
     set_err("ul_decode_batch_harq_tb: strides too small");
     return -1;
   }
-  if (ul_scratch(cfg, n_tb) != 0) return -1;
+  if (ul_reserve(cfg, n_tb) != 0) return -1;
   hipStream_t s = (hipStream_t)stream;
   HCK(oai4g_launch_ul_rm_harq_tb(cfg->d, &cfg->h, n_tb, d_e, e_stride, d_w, w_stride, d_rv, d_clear, cfg->d_dfull,
                                  cfg->d_stride, s), -1);
@@ -2783,20 +2849,18 @@ extern "C" uint8_t oai4g_phy_threegpplte_turbo_decoder16(const int16_t *y, uint8
   if (oai4g_qpp_index(n) < 0) { set_err("Illegal frame length!"); return 255; }
   if (crc_type > OAI4G_CRC24_B) { set_err("turbo decoder: CRC16 / CRC8 are not on the path"); return 255; }
   const size_t ybytes = (3 * (size_t)n + 12) * 2, sbytes = oai4g_td_scratch_bytes(n, 1);
-  uint8_t *buf = scratch(ybytes + 256 + (size_t)n / 8 + 256 + sbytes + 512);
-  if (!buf) return 255;
-  int16_t *d_y = (int16_t *)buf;
-  uint8_t *d_iter = buf + ((ybytes + 255) & ~(size_t)255);
-  uint8_t *d_out = d_iter + 256;
-  uint8_t *d_scr = d_out + (((size_t)n / 8 + 255) & ~(size_t)255);
-  HCK(hipMemcpyAsync(d_y, y, ybytes, hipMemcpyHostToDevice, g_scr.s), 255);
-  HCK(hipMemcpyAsync(d_out, decoded_bytes, n / 8, hipMemcpyHostToDevice, g_scr.s), 255);   /* untouched if never decided */
-  if (oai4g_td_batch(1, n, d_y, 3 * (size_t)n + 12, d_out, n / 8, d_iter, max_iterations, crc_type, F, d_scr, g_scr.s))
+  stage_t st("turbo decoder");
+  const int r_y = st.add(ybytes), r_it = st.add(1, 255), r_out = st.add((size_t)n / 8), r_scr = st.add(sbytes, 768);
+  if (!st.open()) return 255;
+  HCK(st.up(r_y, y, ybytes), 255);
+  HCK(st.up(r_out, decoded_bytes, n / 8), 255);            /* untouched if never decided */
+  if (oai4g_td_batch(1, n, st.ptr<int16_t>(r_y), 3 * (size_t)n + 12, st.ptr(r_out), n / 8, st.ptr(r_it), max_iterations,
+                     crc_type, F, st.ptr(r_scr), g_scr.s))
     return 255;
   uint8_t it = 0;
-  HCK(hipMemcpyAsync(decoded_bytes, d_out, n / 8, hipMemcpyDeviceToHost, g_scr.s), 255);
-  HCK(hipMemcpyAsync(&it, d_iter, 1, hipMemcpyDeviceToHost, g_scr.s), 255);
-  HCK(hipStreamSynchronize(g_scr.s), 255);
+  HCK(st.down(decoded_bytes, r_out, n / 8), 255);
+  HCK(st.down(&it, r_it, 1), 255);
+  HCK(st.sync(), 255);
   return it;
 }
 
@@ -2823,19 +2887,17 @@ extern "C" int oai4g_lte_rate_matching_turbo_rx(uint32_t RTC, uint32_t G, int16_
   if (k0 >= Ncb) k0c = 0;   /* the reference's first pass is empty; selection starts at 0 */
   if (nn == 0 && E > 0) { set_err("rate_matching_rx: no non-NULL entries"); return -1; }
   const size_t b_soft = (size_t)E * 2, b_w = (size_t)Ncb * 2, b_c = (size_t)Ncb * 4;
-  uint8_t *buf = scratch(b_soft + b_w + b_c + Ncb + 1024);
-  if (!buf) return -1;
-  int16_t *d_soft = (int16_t *)buf;
-  int16_t *d_w = (int16_t *)(buf + ((b_soft + 255) & ~(size_t)255));
-  uint32_t *d_c = (uint32_t *)((uint8_t *)d_w + ((b_w + 255) & ~(size_t)255));
-  uint8_t *d_dummy = (uint8_t *)d_c + ((b_c + 255) & ~(size_t)255);
-  HCK(hipMemcpyAsync(d_soft, soft_input, b_soft, hipMemcpyHostToDevice, g_scr.s), -1);
-  HCK(hipMemcpyAsync(d_w, w, b_w, hipMemcpyHostToDevice, g_scr.s), -1);
-  HCK(hipMemcpyAsync(d_c, cidx.data(), b_c, hipMemcpyHostToDevice, g_scr.s), -1);
-  HCK(hipMemcpyAsync(d_dummy, dummy_w, Ncb, hipMemcpyHostToDevice, g_scr.s), -1);
-  HCK(oai4g_launch_rm_rx(d_soft, E, d_w, d_dummy, d_c, Ncb, nn, k0c, clear == 1, g_scr.s), -1);
-  HCK(hipMemcpyAsync(w, d_w, b_w, hipMemcpyDeviceToHost, g_scr.s), -1);
-  HCK(hipStreamSynchronize(g_scr.s), -1);
+  stage_t st("rate_matching_rx");
+  const int r_soft = st.add(b_soft), r_w = st.add(b_w), r_c = st.add(b_c), r_dummy = st.add(Ncb, 1024);
+  if (!st.open()) return -1;
+  HCK(st.up(r_soft, soft_input, b_soft), -1);
+  HCK(st.up(r_w, w, b_w), -1);
+  HCK(st.up(r_c, cidx.data(), b_c), -1);
+  HCK(st.up(r_dummy, dummy_w, Ncb), -1);
+  HCK(oai4g_launch_rm_rx(st.ptr<int16_t>(r_soft), E, st.ptr<int16_t>(r_w), st.ptr(r_dummy), st.ptr<uint32_t>(r_c), Ncb, nn,
+                         k0c, clear == 1, g_scr.s), -1);
+  HCK(st.down(w, r_w, b_w), -1);
+  HCK(st.sync(), -1);
   *E_out = E;
   return 0;
 }
@@ -2845,14 +2907,14 @@ extern "C" void oai4g_sub_block_deinterleaving_turbo(uint32_t D, int16_t *d, con
   NEED_INIT();
   const uint32_t R = (D + 31) >> 5, Kpi = R << 5;
   const size_t nd = 96 + 3 * (size_t)D + 8, b_d = nd * 2, b_w = 3 * (size_t)Kpi * 2;
-  uint8_t *buf = scratch(b_d + b_w + 512);
-  if (!buf) return;
-  int16_t *d_d = (int16_t *)buf, *d_w = (int16_t *)(buf + ((b_d + 255) & ~(size_t)255));
-  HCK(hipMemcpyAsync(d_d, d - 96, b_d, hipMemcpyHostToDevice, g_scr.s), );
-  HCK(hipMemcpyAsync(d_w, w, b_w, hipMemcpyHostToDevice, g_scr.s), );
-  HCK(oai4g_launch_subblock_deint(D, d_d, d_w, g_scr.s), );
-  HCK(hipMemcpyAsync(d - 96, d_d, b_d, hipMemcpyDeviceToHost, g_scr.s), );
-  HCK(hipStreamSynchronize(g_scr.s), );
+  stage_t st("sub_block_deinterleaving_turbo");
+  const int r_d = st.add(b_d), r_w = st.add(b_w, 512);
+  if (!st.open()) return;
+  HCK(st.up(r_d, d - 96, b_d), );
+  HCK(st.up(r_w, w, b_w), );
+  HCK(oai4g_launch_subblock_deint(D, st.ptr<int16_t>(r_d), st.ptr<int16_t>(r_w), g_scr.s), );
+  HCK(st.down(d - 96, r_d, b_d), );
+  HCK(st.sync(), );
 }
 
 extern "C" int oai4g_idft(int log2n, const int16_t *x, int16_t *y, int scale)
@@ -2876,9 +2938,9 @@ static int run_fep_window(const int32_t *h_in, int32_t *h_out, int log2n, int sc
 {
   NEED_INIT(-1);
   const size_t N = (size_t)1 << log2n;
-  uint8_t *buf = scratch(2 * N * 4 + 256);
-  if (!buf) return -1;
-  int32_t *d_in = (int32_t *)buf, *d_out = (int32_t *)(buf + ((N * 4 + 255) & ~(size_t)255));
+  stage_t st("dft");
+  const int r_in = st.add(N * 4), r_out = st.add(N * 4, 256);
+  if (!st.open()) return -1;
   fep_args_t a;
   memset(&a, 0, sizeof(a));
   a.n_units = 1;
@@ -2886,10 +2948,10 @@ static int run_fep_window(const int32_t *h_in, int32_t *h_out, int log2n, int sc
   a.in_stride = a.in_len = (uint32_t)N;
   a.out_stride = (uint32_t)N;
   a.scale = scale;
-  HCK(hipMemcpyAsync(d_in, h_in, N * 4, hipMemcpyHostToDevice, g_scr.s), -1);
-  HCK(oai4g_launch_fep(d_in, d_out, log2n, a, g_twf, g_n_cu, g_scr.s), -1);
-  HCK(hipMemcpyAsync(h_out, d_out, N * 4, hipMemcpyDeviceToHost, g_scr.s), -1);
-  HCK(hipStreamSynchronize(g_scr.s), -1);
+  HCK(st.up(r_in, h_in, N * 4), -1);
+  HCK(oai4g_launch_fep(st.ptr<int32_t>(r_in), st.ptr<int32_t>(r_out), log2n, a, g_twf, g_n_cu, g_scr.s), -1);
+  HCK(st.down(h_out, r_out, N * 4), -1);
+  HCK(st.sync(), -1);
   return 0;
 }
 
@@ -3018,6 +3080,28 @@ extern "C" void oai4g_generate_pcfich_reg_mapping(const oai4g_frame_parms_t *fp,
   printf("pcfich_reg : %d,%d,%d,%d\n", pcfich_reg[0], pcfich_reg[1], pcfich_reg[2], pcfich_reg[3]);
 }
 
+/* the PCFICH kernel's arguments: scrambling c_init (pcfich.c:96), the first RE of each REG in
+ * symbol 0 (wrapped over DC), and the caller's gain / antenna choice */
+static void pcfich_args_h(const oai4g_frame_parms_t *fp, uint32_t subframe, uint8_t cfi, int16_t gain, uint8_t mode1,
+                          uint32_t n_ant, pcfich_args_t *a)
+{
+  uint16_t reg[4];
+  uint8_t first_idx;
+  pcfich_regs(fp, reg, &first_idx);
+  memset(a, 0, sizeof(*a));
+  a->c_init = ((((2u * fp->Nid_cell) + 1u) * (1u + subframe)) << 9) + fp->Nid_cell;
+  a->cfi = cfi;
+  a->gain = gain;
+  a->mode1 = mode1;
+  a->nushift3 = (uint8_t)(fp->nushift % 3);
+  for (int q = 0; q < 4; q++) {
+    uint32_t ro = fp->first_carrier_offset + (uint32_t)reg[q] * 6;
+    if (ro >= fp->ofdm_symbol_size) ro = 1 + ro - fp->ofdm_symbol_size;
+    a->reg_off[q] = ro;
+  }
+  a->n_ant = n_ant;
+}
+
 /* generate_pcfich (pcfich.c:144, decl proto.h:1432): overwrites the 16 PCFICH REs of symbol 0 of
  * `subframe` in the frame grids txdataF[0] (and txdataF[1] with two antennas).  The reference
  * reads frame_parms->pcfich_reg (set at init by generate_pcfich_reg_mapping); here they are
@@ -3031,33 +3115,19 @@ extern "C" int oai4g_generate_pcfich(uint8_t num_pdcch_symbols, int16_t amp, con
     set_err("generate_pcfich: num_pdcch_symbols %u / subframe %u out of range", num_pdcch_symbols, subframe);
     return -1;
   }
-  uint16_t reg[4];
-  uint8_t first_idx;
-  pcfich_regs(fp, reg, &first_idx);
   const uint32_t N = fp->ofdm_symbol_size, nsymb = fp->Ncp == 0 ? 14 : 12;
   const size_t symbol_offset = (size_t)N * subframe * nsymb;
   pcfich_args_t a;
-  memset(&a, 0, sizeof(a));
-  a.c_init = ((((2u * fp->Nid_cell) + 1u) * (1u + subframe)) << 9) + fp->Nid_cell;
-  a.cfi = num_pdcch_symbols;
-  a.gain = fp->mode1_flag == 1 ? (int16_t)((amp * 23170) >> 15) : (int16_t)(amp / 2);
-  a.mode1 = fp->mode1_flag ? 1 : 0;
-  a.nushift3 = (uint8_t)(fp->nushift % 3);
-  for (int q = 0; q < 4; q++) {
-    uint32_t ro = fp->first_carrier_offset + (uint32_t)reg[q] * 6;
-    if (ro >= N) ro = 1 + ro - N;
-    a.reg_off[q] = ro;
-  }
-  a.n_ant = fp->nb_antennas_tx > 1 ? 2 : 1;
-  uint8_t *buf = scratch(2 * (size_t)N * 4 + 256);
-  if (!buf) return -1;
-  int32_t *d0 = (int32_t *)buf, *d1 = (int32_t *)(buf + (((size_t)N * 4 + 255) & ~(size_t)255));
-  for (uint32_t aa = 0; aa < a.n_ant; aa++)
-    HCK(hipMemcpyAsync(aa ? d1 : d0, txdataF[aa] + symbol_offset, (size_t)N * 4, hipMemcpyHostToDevice, g_scr.s), -1);
-  HCK(oai4g_launch_pcfich(d0, d1, a, g_scr.s), -1);
-  for (uint32_t aa = 0; aa < a.n_ant; aa++)
-    HCK(hipMemcpyAsync(txdataF[aa] + symbol_offset, aa ? d1 : d0, (size_t)N * 4, hipMemcpyDeviceToHost, g_scr.s), -1);
-  HCK(hipStreamSynchronize(g_scr.s), -1);
+  pcfich_args_h(fp, subframe, num_pdcch_symbols,
+                fp->mode1_flag == 1 ? (int16_t)((amp * 23170) >> 15) : (int16_t)(amp / 2), fp->mode1_flag ? 1 : 0,
+                fp->nb_antennas_tx > 1 ? 2 : 1, &a);
+  stage_t st("generate_pcfich");
+  const int r_g[2] = {st.add((size_t)N * 4), st.add((size_t)N * 4, 256)};
+  if (!st.open()) return -1;
+  for (uint32_t aa = 0; aa < a.n_ant; aa++) HCK(st.up(r_g[aa], txdataF[aa] + symbol_offset, (size_t)N * 4), -1);
+  HCK(oai4g_launch_pcfich(st.ptr<int32_t>(r_g[0]), st.ptr<int32_t>(r_g[1]), a, g_scr.s), -1);
+  for (uint32_t aa = 0; aa < a.n_ant; aa++) HCK(st.down(txdataF[aa] + symbol_offset, r_g[aa], (size_t)N * 4), -1);
+  HCK(st.sync(), -1);
   return 0;
 }
 
@@ -3193,8 +3263,6 @@ extern "C" int oai4g_get_nCCE_offset(uint8_t L, int nCCE, int common_dci, uint16
 static uint32_t pdcch_map(const oai4g_frame_parms_t *fp, uint8_t npdcch, uint8_t mi, std::vector<uint32_t> &map,
                           std::vector<uint16_t> &src)
 {
-  static const uint8_t bitrev_cc[32] = {1, 17, 9, 25, 5, 21, 13, 29, 3, 19, 11, 27, 7, 23, 15, 31,
-                                        0, 16, 8, 24, 4, 20, 12, 28, 2, 18, 10, 26, 6, 22, 14, 30};
   const uint32_t N = fp->ofdm_symbol_size, Mquad = oai4g_get_nquad(npdcch, fp, mi);
   const int Msymb = ((2 * 33 + 22) * 72) / 2;
   int Msymb2;
@@ -3330,41 +3398,22 @@ extern "C" uint8_t oai4g_generate_dci_top(uint8_t num_ue_spec_dci, uint8_t num_c
   if (npd < 1 || npd > 3) return npd;
   const uint32_t N = fp->ofdm_symbol_size, nsymb = 14;
   const size_t sym_off = (size_t)N * subframe * nsymb, gbytes = (size_t)npd * N * 4;
-  const size_t gpad = (gbytes + 255) & ~(size_t)255, mbytes = ((size_t)a.n_re * 4 + 255) & ~(size_t)255;
-  uint8_t *buf = scratch(2 * gpad + mbytes + (size_t)a.n_re * 2 + 256);
-  if (!buf) return 0;
-  int32_t *d0 = (int32_t *)buf, *d1 = (int32_t *)(buf + gpad);
-  uint32_t *dmap = (uint32_t *)(buf + 2 * gpad);
-  uint16_t *dsrc = (uint16_t *)(buf + 2 * gpad + mbytes);
+  stage_t st("generate_dci_top");
+  const int r_g[2] = {st.add(gbytes), st.add(gbytes)};
+  const int r_map = st.add((size_t)a.n_re * 4), r_src = st.add((size_t)a.n_re * 2, 256);
+  if (!st.open()) return 0;
+  int32_t *d0 = st.ptr<int32_t>(r_g[0]), *d1 = st.ptr<int32_t>(r_g[1]);
   const uint32_t n_ant = a.n_ant;
-  for (uint32_t aa = 0; aa < n_ant; aa++)
-    HCK(hipMemcpyAsync(aa ? d1 : d0, txdataF[aa] + sym_off, gbytes, hipMemcpyHostToDevice, g_scr.s), 0);
-  HCK(hipMemcpyAsync(dmap, map.data(), (size_t)a.n_re * 4, hipMemcpyHostToDevice, g_scr.s), 0);
-  HCK(hipMemcpyAsync(dsrc, src.data(), (size_t)a.n_re * 2, hipMemcpyHostToDevice, g_scr.s), 0);
+  for (uint32_t aa = 0; aa < n_ant; aa++) HCK(st.up(r_g[aa], txdataF[aa] + sym_off, gbytes), 0);
+  HCK(st.up(r_map, map.data(), (size_t)a.n_re * 4), 0);
+  HCK(st.up(r_src, src.data(), (size_t)a.n_re * 2), 0);
   /* PCFICH first (generate_dci_top :2084-2088), then the PDCCH REs */
   pcfich_args_t pa;
-  memset(&pa, 0, sizeof(pa));
-  {
-    uint16_t reg[4];
-    uint8_t fi;
-    pcfich_regs(fp, reg, &fi);
-    pa.c_init = ((((2u * fp->Nid_cell) + 1u) * (1u + subframe)) << 9) + fp->Nid_cell;
-    pa.cfi = npd;
-    pa.gain = a.gain;
-    pa.mode1 = a.mode1;
-    pa.nushift3 = (uint8_t)(fp->nushift % 3);
-    for (int q = 0; q < 4; q++) {
-      uint32_t ro = fp->first_carrier_offset + (uint32_t)reg[q] * 6;
-      if (ro >= N) ro = 1 + ro - N;
-      pa.reg_off[q] = ro;
-    }
-    pa.n_ant = n_ant;
-  }
+  pcfich_args_h(fp, subframe, npd, a.gain, a.mode1, n_ant, &pa);
   HCK(oai4g_launch_pcfich(d0, d1, pa, g_scr.s), 0);
-  HCK(oai4g_launch_dci(a, dmap, dsrc, d0, d1, 0, g_scr.s), 0);
-  for (uint32_t aa = 0; aa < n_ant; aa++)
-    HCK(hipMemcpyAsync(txdataF[aa] + sym_off, aa ? d1 : d0, gbytes, hipMemcpyDeviceToHost, g_scr.s), 0);
-  HCK(hipStreamSynchronize(g_scr.s), 0);
+  HCK(oai4g_launch_dci(a, st.ptr<uint32_t>(r_map), st.ptr<uint16_t>(r_src), d0, d1, 0, g_scr.s), 0);
+  for (uint32_t aa = 0; aa < n_ant; aa++) HCK(st.down(txdataF[aa] + sym_off, r_g[aa], gbytes), 0);
+  HCK(st.sync(), 0);
   return npd;
 }
 
@@ -3394,19 +3443,23 @@ static int rebuild_static(oai4g_tx_config_t *cfg)
     const oai4g_frame_parms_t &fp = cfg->fp;
     const uint32_t n_tab = cfg->ctl_planes = n_ant > 2 ? n_ant : 2;
     std::vector<uint32_t> tab((size_t)10 * 14 * n_tab * N, 0);
-    const size_t gbytes = (size_t)14 * N * 4, gpad = (gbytes + 255) & ~(size_t)255;
+    const size_t gbytes = (size_t)14 * N * 4;
     const size_t mcap = (size_t)4 * 1024;    /* >= 4 nquad REs for every geometry */
     const size_t accb = (size_t)4 * 4 * N * 4;   /* PHICH accumulators / PBCH encode grid (4 antennas x 4 symbols) */
-    uint8_t *buf = scratch(4 * gpad + mcap * 4 + mcap * 2 + accb + 2048 + 256);
-    if (!buf) return -1;
-    int32_t *dg[4] = {(int32_t *)buf, (int32_t *)(buf + gpad), (int32_t *)(buf + 2 * gpad), (int32_t *)(buf + 3 * gpad)};
-    uint32_t *dmap = (uint32_t *)(buf + 4 * gpad);
-    uint16_t *dsrc = (uint16_t *)(buf + 4 * gpad + mcap * 4);
-    int32_t *dacc = (int32_t *)(buf + 4 * gpad + mcap * 6);
-    uint8_t *dpe = buf + 4 * gpad + mcap * 6 + accb;
+    /* the regions serve all ten subframe indices in turn */
+    stage_t st("static REs");
+    const int r_g[4] = {st.add(gbytes), st.add(gbytes), st.add(gbytes), st.add(gbytes)};   /* cleared as one span */
+    const int r_map = st.add(mcap * 4), r_src = st.add(mcap * 2), r_acc = st.add(accb);
+    const int r_pe = st.add(1920, 128 + 256);    /* the PBCH's E <= 1920 bytes */
+    if (!st.open()) return -1;
+    int32_t *dg[4] = {st.ptr<int32_t>(r_g[0]), st.ptr<int32_t>(r_g[1]), st.ptr<int32_t>(r_g[2]), st.ptr<int32_t>(r_g[3])};
+    uint32_t *dmap = st.ptr<uint32_t>(r_map);
+    uint16_t *dsrc = st.ptr<uint16_t>(r_src);
+    int32_t *dacc = st.ptr<int32_t>(r_acc);
+    uint8_t *dpe = st.ptr(r_pe);
     std::vector<uint32_t> g((size_t)14 * N);
     for (uint32_t sf = 0; sf < 10; sf++) {
-      HCK(hipMemsetAsync(buf, 0, 4 * gpad, g_scr.s), -1);
+      HCK(st.zero(r_g[0], st.off[r_g[3]] - st.off[r_g[0]] + gbytes, r_g[3]), -1);
       uint32_t n_out = n_ant > 2 ? 2 : n_ant;          /* antennas that can carry a static RE */
       if (dci_on) {
         dci_args_t a;
@@ -3421,24 +3474,10 @@ static int rebuild_static(oai4g_tx_config_t *cfg)
           return -1;
         }
         if (map.size() > mcap) { set_err("set_control: PDCCH map too large"); return -1; }
-        HCK(hipMemcpyAsync(dmap, map.data(), map.size() * 4, hipMemcpyHostToDevice, g_scr.s), -1);
-        HCK(hipMemcpyAsync(dsrc, src.data(), src.size() * 2, hipMemcpyHostToDevice, g_scr.s), -1);
+        HCK(st.up(r_map, map.data(), map.size() * 4), -1);
+        HCK(st.up(r_src, src.data(), src.size() * 2), -1);
         pcfich_args_t pa;
-        memset(&pa, 0, sizeof(pa));
-        uint16_t reg[4];
-        uint8_t fi;
-        pcfich_regs(&fp, reg, &fi);
-        pa.c_init = ((((2u * fp.Nid_cell) + 1u) * (1u + sf)) << 9) + fp.Nid_cell;
-        pa.cfi = npd;
-        pa.gain = a.gain;
-        pa.mode1 = a.mode1;
-        pa.nushift3 = (uint8_t)(fp.nushift % 3);
-        for (int q = 0; q < 4; q++) {
-          uint32_t ro = fp.first_carrier_offset + (uint32_t)reg[q] * 6;
-          if (ro >= N) ro = 1 + ro - N;
-          pa.reg_off[q] = ro;
-        }
-        pa.n_ant = a.n_ant;
+        pcfich_args_h(&fp, sf, npd, a.gain, a.mode1, a.n_ant, &pa);
         HCK(oai4g_launch_pcfich(dg[0], dg[1], pa, g_scr.s), -1);
         HCK(oai4g_launch_dci(a, dmap, dsrc, dg[0], dg[1], 0, g_scr.s), -1);
       }
@@ -3484,8 +3523,8 @@ static int rebuild_static(oai4g_tx_config_t *cfg)
         if (cm.pbch || cm.pss_sss) n_out = n_ant;
       }
       for (uint32_t ant = 0; ant < n_out; ant++) {
-        HCK(hipMemcpyAsync(g.data(), dg[ant], gbytes, hipMemcpyDeviceToHost, g_scr.s), -1);
-        HCK(hipStreamSynchronize(g_scr.s), -1);
+        HCK(st.down(g.data(), r_g[ant], gbytes), -1);
+        HCK(st.sync(), -1);
         for (uint32_t l = 0; l < nsymb; l++)
           for (uint32_t k = 0; k < N; k++) {
             const uint32_t v = g[(size_t)l * N + k];
@@ -3604,20 +3643,20 @@ static int sync_dropin(int32_t **txdataF, int16_t amp, const oai4g_frame_parms_t
   NEED_INIT(-1);
   const uint32_t N = fp->ofdm_symbol_size, Nsymb = fp->Ncp == 0 ? 14 : 12, n_ant = fp->nb_antennas_tx;
   if (n_ant < 1 || n_ant > 4) { set_err("generate_%s: nb_antennas_tx %u", pss ? "pss" : "sss", n_ant); return -1; }
-  const size_t off = (size_t)slot_offset * Nsymb / 2 * N + (size_t)symbol * N, sb = ((size_t)N * 4 + 255) & ~(size_t)255;
+  const size_t off = (size_t)slot_offset * Nsymb / 2 * N + (size_t)symbol * N, sb = (size_t)N * 4;
   sync_args_t a;
   sync_args(fp, amp, pss, slot_offset, a);
-  uint8_t *buf = scratch(4 * sb);
-  if (!buf) return -1;
+  stage_t st(pss ? "generate_pss" : "generate_sss");
+  const int r_g[4] = {st.add(sb), st.add(sb), st.add(sb), st.add(sb)};
+  if (!st.open()) return -1;
   int32_t *d[4];
   for (uint32_t aa = 0; aa < n_ant; aa++) {
-    d[aa] = (int32_t *)(buf + aa * sb);
-    HCK(hipMemcpyAsync(d[aa], txdataF[aa] + off, (size_t)N * 4, hipMemcpyHostToDevice, g_scr.s), -1);
+    d[aa] = st.ptr<int32_t>(r_g[aa]);
+    HCK(st.up(r_g[aa], txdataF[aa] + off, sb), -1);
   }
   HCK(oai4g_launch_sync(d, a, g_scr.s), -1);
-  for (uint32_t aa = 0; aa < n_ant; aa++)
-    HCK(hipMemcpyAsync(txdataF[aa] + off, d[aa], (size_t)N * 4, hipMemcpyDeviceToHost, g_scr.s), -1);
-  HCK(hipStreamSynchronize(g_scr.s), -1);
+  for (uint32_t aa = 0; aa < n_ant; aa++) HCK(st.down(txdataF[aa] + off, r_g[aa], sb), -1);
+  HCK(st.sync(), -1);
   return 0;
 }
 
@@ -3666,21 +3705,21 @@ extern "C" int oai4g_generate_pbch(oai4g_pbch_t *st, int32_t **txdataF, int amp,
   }
   pbch_args_t a;
   pbch_args(fp, amp, pbch_pdu, frame_mod4, a);
-  const size_t gb = (size_t)4 * N * 4, gs = (gb + 255) & ~(size_t)255, off = (size_t)(nsymb >> 1) * N;
-  uint8_t *buf = scratch(4 * gs + 2048);
-  if (!buf) return -1;
+  const size_t gb = (size_t)4 * N * 4, off = (size_t)(nsymb >> 1) * N;
+  stage_t sg("generate_pbch");
+  const int r_g[4] = {sg.add(gb), sg.add(gb), sg.add(gb), sg.add(gb)};
+  const int r_e = sg.add(1920, 128);          /* E <= 1920 bytes */
+  if (!sg.open()) return -1;
   int32_t *d[4];
-  uint8_t *de = buf + 4 * gs;
   for (uint32_t aa = 0; aa < n_ant; aa++) {
-    d[aa] = (int32_t *)(buf + aa * gs);
-    HCK(hipMemcpyAsync(d[aa], txdataF[aa] + off, gb, hipMemcpyHostToDevice, g_scr.s), -1);
+    d[aa] = sg.ptr<int32_t>(r_g[aa]);
+    HCK(sg.up(r_g[aa], txdataF[aa] + off, gb), -1);
   }
-  if (!a.encode) HCK(hipMemcpyAsync(de, st->pbch_e, a.E, hipMemcpyHostToDevice, g_scr.s), -1);
-  HCK(oai4g_launch_pbch(d, de, a, g_scr.s), -1);
-  if (a.encode) HCK(hipMemcpyAsync(st->pbch_e, de, a.E, hipMemcpyDeviceToHost, g_scr.s), -1);
-  for (uint32_t aa = 0; aa < n_ant; aa++)
-    HCK(hipMemcpyAsync(txdataF[aa] + off, d[aa], gb, hipMemcpyDeviceToHost, g_scr.s), -1);
-  HCK(hipStreamSynchronize(g_scr.s), -1);
+  if (!a.encode) HCK(sg.up(r_e, st->pbch_e, a.E), -1);
+  HCK(oai4g_launch_pbch(d, sg.ptr(r_e), a, g_scr.s), -1);
+  if (a.encode) HCK(sg.down(st->pbch_e, r_e, a.E), -1);
+  for (uint32_t aa = 0; aa < n_ant; aa++) HCK(sg.down(txdataF[aa] + off, r_g[aa], gb), -1);
+  HCK(sg.sync(), -1);
   return 0;
 }
 
@@ -3734,15 +3773,16 @@ extern "C" int oai4g_generate_phich(const oai4g_frame_parms_t *fp, int16_t amp, 
   phich_common(fp, amp, a);
   if (a.n_ant > 1 && fp->nb_antennas_tx < 2) { set_err("generate_phich: ALAMOUTI needs two grids"); return -1; }
   const uint32_t N = fp->ofdm_symbol_size;
-  const size_t wb = (size_t)a.win * 4, ws = (wb + 255) & ~(size_t)255, off = (size_t)14 * N * subframe;
-  uint8_t *buf = scratch(2 * ws + 4 * ws);
-  if (!buf) return -1;
-  int32_t *d[2] = {(int32_t *)buf, (int32_t *)(buf + ws)};
-  int32_t *acc = (int32_t *)(buf + 2 * ws);
-  for (uint32_t aa = 0; aa < a.n_ant; aa++) HCK(hipMemcpyAsync(d[aa], y[aa] + off, wb, hipMemcpyHostToDevice, g_scr.s), -1);
-  HCK(oai4g_launch_phich(d, acc, a, g_scr.s), -1);
-  for (uint32_t aa = 0; aa < a.n_ant; aa++) HCK(hipMemcpyAsync(y[aa] + off, d[aa], wb, hipMemcpyDeviceToHost, g_scr.s), -1);
-  HCK(hipStreamSynchronize(g_scr.s), -1);
+  const size_t wb = (size_t)a.win * 4, off = (size_t)14 * N * subframe;
+  stage_t st("generate_phich");
+  const int r_y[2] = {st.add(wb), st.add(wb)};
+  const int r_acc = st.add(4 * up256(wb));    /* the accumulators of four windows */
+  if (!st.open()) return -1;
+  int32_t *d[2] = {st.ptr<int32_t>(r_y[0]), st.ptr<int32_t>(r_y[1])};
+  for (uint32_t aa = 0; aa < a.n_ant; aa++) HCK(st.up(r_y[aa], y[aa] + off, wb), -1);
+  HCK(oai4g_launch_phich(d, st.ptr<int32_t>(r_acc), a, g_scr.s), -1);
+  for (uint32_t aa = 0; aa < a.n_ant; aa++) HCK(st.down(y[aa] + off, r_y[aa], wb), -1);
+  HCK(st.sync(), -1);
   return 0;
 }
 
@@ -4168,21 +4208,8 @@ static oai4g_rx_config_t *rx_config_build(const oai4g_frame_parms_t *fp, const u
    * Ns = 2 subframe (dlsch_scrambling.c:116), word w = lte_gold_generic output 50 + w */
   h.gold_words = (max_llr + 31) / 32 + 1;
   std::vector<uint32_t> gold((size_t)10 * h.gold_words);
-  for (uint32_t sf = 0; sf < 10; sf++) {
-    uint32_t x1 = 1u + (1u << 31), x2 = ((uint32_t)rnti << 14) + (sf << 9) + fp->Nid_cell;
-    x2 = x2 ^ ((x2 ^ (x2 >> 1) ^ (x2 >> 2) ^ (x2 >> 3)) << 31);
-    auto step = [&]() {
-      x1 = (x1 >> 1) ^ (x1 >> 4);
-      x1 = x1 ^ (x1 << 31) ^ (x1 << 28);
-      x2 = (x2 >> 1) ^ (x2 >> 2) ^ (x2 >> 3) ^ (x2 >> 4);
-      x2 = x2 ^ (x2 << 31) ^ (x2 << 30) ^ (x2 << 29) ^ (x2 << 28);
-    };
-    for (int n = 1; n < 50; n++) step();
-    for (uint32_t w = 0; w < h.gold_words; w++) {
-      step();
-      gold[(size_t)sf * h.gold_words + w] = x1 ^ x2;
-    }
-  }
+  for (uint32_t sf = 0; sf < 10; sf++)
+    gold_seq_h(((uint32_t)rnti << 14) + (sf << 9) + fp->Nid_cell, gold.data() + (size_t)sf * h.gold_words, h.gold_words);
   if (hipMalloc(&cfg->d_map, map.size() * 4) != hipSuccess || hipMalloc(&cfg->d_gold, gold.size() * 4) != hipSuccess ||
       hipMalloc(&cfg->d, sizeof(rx_dev_t)) != hipSuccess) {
     set_err("rx_config: device allocation failed");
@@ -4425,24 +4452,22 @@ int rx_pdsch_run(oai4g_rx_config_t *cfg, const char *who, uint8_t subframe, int 
 {
   if (!cfg) return -1;
   if (rx_check_batch(cfg, 1) != 0) return -1;
-  const size_t gb = (size_t)cfg->h.nsymb * cfg->h.N * 4, gs = (gb + 255) & ~(size_t)255, ny = n_planes == 1 ? 1 : 2;
+  const size_t gb = (size_t)cfg->h.nsymb * cfg->h.N * 4, ny = n_planes == 1 ? 1 : 2, lb = (size_t)cfg->h.llr_stride * 2;
   const int n = (int)cfg->llr_count[subframe % 10];
-  uint8_t *buf = scratch((ny + n_planes) * gs + (size_t)cfg->h.llr_stride * 2 * n_out + 256);
-  if (!buf) return -1;
-  uint8_t *dy = buf, *de = buf + ny * gs;                         /* [nb_rx][grid], planes [p * 2 + a] */
-  int16_t *dl = (int16_t *)(buf + (ny + n_planes) * gs);
-  bool ok = true;
-  for (int a = 0; a < nb_rx && ok; a++) ok = hipMemcpyAsync(dy + a * gb, rxdataF[a], gb, hipMemcpyHostToDevice, g_scr.s) == hipSuccess;
-  for (int pa = 0; pa < n_planes && ok; pa++)
-    if ((pa & 1) < nb_rx) ok = hipMemcpyAsync(de + pa * gb, est[pa], gb, hipMemcpyHostToDevice, g_scr.s) == hipSuccess;
-  ok = ok && batch((const int32_t *)dy, (const int32_t *)de, dl, dl + cfg->h.llr_stride) == 0;
-  for (int i = 0; i < n_out && ok; i++)
-    ok = hipMemcpyAsync(llr[i], dl + i * cfg->h.llr_stride, (size_t)n * 2, hipMemcpyDeviceToHost, g_scr.s) == hipSuccess;
-  if (ok && (!log2_maxh || hipMemcpyAsync(log2_maxh, cfg->d_shift, 1, hipMemcpyDeviceToHost, g_scr.s) == hipSuccess) &&
-      hipStreamSynchronize(g_scr.s) == hipSuccess)
-    return n;
-  set_err("%s: HIP error", who);
-  return -1;
+  stage_t st(who);
+  const int r_y = st.add(ny * up256(gb)), r_e = st.add(n_planes * up256(gb));   /* [nb_rx][grid], planes [p * 2 + a] */
+  const int r_l = st.add(lb * n_out, 256);
+  if (!st.open()) return -1;
+  for (int a = 0; a < nb_rx; a++) HCK(st.up(r_y, rxdataF[a], gb, a * gb), -1);
+  for (int pa = 0; pa < n_planes; pa++)
+    if ((pa & 1) < nb_rx) HCK(st.up(r_e, est[pa], gb, pa * gb), -1);
+  int16_t *dl = st.ptr<int16_t>(r_l);
+  if (batch(st.ptr<const int32_t>(r_y), st.ptr<const int32_t>(r_e), dl, dl + cfg->h.llr_stride) != 0) return -1;
+  for (int i = 0; i < n_out; i++) HCK(st.down(llr[i], r_l, (size_t)n * 2, i * lb), -1);
+  /* the shift lives in the configuration, not in the staging buffer */
+  if (log2_maxh) HCK(hipMemcpyAsync(log2_maxh, cfg->d_shift, 1, hipMemcpyDeviceToHost, g_scr.s), -1);
+  HCK(st.sync(), -1);
+  return n;
 }
 }  // namespace
 
@@ -4522,34 +4547,20 @@ extern "C" void oai4g_dlsch_unscrambling(const oai4g_frame_parms_t *fp, int mbsf
   NEED_INIT();
   if (G < 0) return;
   /* dlsch_scrambling.c:115-118: the PMCH (mbsfn_flag) sequence depends on the MBSFN area only */
-  uint32_t x1 = 1u + (1u << 31),
-           x2 = mbsfn_flag ? ((uint32_t)(Ns >> 1) << 9) + fp->Nid_cell_mbsfn
-                           : ((uint32_t)rnti << 14) + ((uint32_t)q << 13) + ((uint32_t)(Ns >> 1) << 9) + fp->Nid_cell;
-  x2 = x2 ^ ((x2 ^ (x2 >> 1) ^ (x2 >> 2) ^ (x2 >> 3)) << 31);
-  auto step = [&]() {
-    x1 = (x1 >> 1) ^ (x1 >> 4);
-    x1 = x1 ^ (x1 << 31) ^ (x1 << 28);
-    x2 = (x2 >> 1) ^ (x2 >> 2) ^ (x2 >> 3) ^ (x2 >> 4);
-    x2 = x2 ^ (x2 << 31) ^ (x2 << 30) ^ (x2 << 29) ^ (x2 << 28);
-  };
-  for (int n = 1; n < 50; n++) step();
+  const uint32_t c_init = mbsfn_flag ? ((uint32_t)(Ns >> 1) << 9) + fp->Nid_cell_mbsfn
+                                     : ((uint32_t)rnti << 14) + ((uint32_t)q << 13) + ((uint32_t)(Ns >> 1) << 9) + fp->Nid_cell;
   const int words = 1 + (G >> 5);
   std::vector<uint32_t> c(words);
-  for (int i = 0; i < words; i++) {
-    step();
-    c[i] = x1 ^ x2;
-  }
-  const size_t lb = (size_t)words * 64, lbs = (lb + 255) & ~(size_t)255;
-  uint8_t *buf = scratch(lbs + (size_t)words * 4);
-  if (!buf) return;
-  int16_t *dl = (int16_t *)buf;
-  uint32_t *dc = (uint32_t *)(buf + lbs);
-  if (hipMemcpyAsync(dl, llr, lb, hipMemcpyHostToDevice, g_scr.s) != hipSuccess ||
-      hipMemcpyAsync(dc, c.data(), (size_t)words * 4, hipMemcpyHostToDevice, g_scr.s) != hipSuccess ||
-      oai4g_launch_unscramble(dl, dc, words * 32, g_scr.s) != hipSuccess ||
-      hipMemcpyAsync(llr, dl, lb, hipMemcpyDeviceToHost, g_scr.s) != hipSuccess ||
-      hipStreamSynchronize(g_scr.s) != hipSuccess)
-    set_err("dlsch_unscrambling: HIP error");
+  gold_seq_h(c_init, c.data(), c.size());
+  const size_t lb = (size_t)words * 64;
+  stage_t st("dlsch_unscrambling");
+  const int r_l = st.add(lb), r_c = st.add((size_t)words * 4);
+  if (!st.open()) return;
+  HCK(st.up(r_l, llr, lb), );
+  HCK(st.up(r_c, c.data(), (size_t)words * 4), );
+  HCK(oai4g_launch_unscramble(st.ptr<int16_t>(r_l), st.ptr<uint32_t>(r_c), words * 32, g_scr.s), );
+  HCK(st.down(llr, r_l, lb), );
+  HCK(st.sync(), );
 }
 
 /* ------------------------------------------------------------------------------------------
@@ -4727,29 +4738,25 @@ extern "C" int oai4g_lte_dl_channel_estimation(const oai4g_frame_parms_t *fp, co
   }
   chest_dev_t h;
   if (chest_fill(fp, p, h) != 0) return -1;
-  const size_t N = fp->ofdm_symbol_size, eb = (size_t)nsymb * N * 4, cs = (sizeof(chest_dev_t) + 255) & ~(size_t)255;
-  uint8_t *buf = scratch(cs + eb + N * 4);
-  if (!buf) return -1;
-  chest_dev_t *dc = (chest_dev_t *)buf;
-  int32_t *de = (int32_t *)(buf + cs), *dr = (int32_t *)(buf + cs + eb);
+  const size_t N = fp->ofdm_symbol_size, rb = N * 4;
+  stage_t st("lte_dl_channel_estimation");
+  const int r_c = st.add(sizeof(chest_dev_t)), r_e = st.add(nsymb * rb), r_r = st.add(rb);
+  if (!st.open()) return -1;
   /* the call reads the previous pilot row and writes its own row plus the rows between the two
    * (k_chest_symbol / ce_interp): only those rows cross PCIe */
   const uint32_t prev_row = symbol == 0 ? p3 : symbol == p1 ? 0 : symbol == p2 ? p1 : p2;
-  const size_t rb = N * 4;
-  auto rows_d2h = [&](uint32_t r0, uint32_t n) {
-    return hipMemcpyAsync(dl_ch_estimates + (size_t)r0 * N, de + (size_t)r0 * N, n * rb, hipMemcpyDeviceToHost,
-                          g_scr.s) == hipSuccess;
-  };
-  if (hipMemcpyAsync(dc, &h, sizeof(h), hipMemcpyHostToDevice, g_scr.s) != hipSuccess ||
-      hipMemcpyAsync(de + (size_t)prev_row * N, dl_ch_estimates + (size_t)prev_row * N, rb, hipMemcpyHostToDevice,
-                     g_scr.s) != hipSuccess ||
-      hipMemcpyAsync(dr, rxdataF + (size_t)symbol * N, N * 4, hipMemcpyHostToDevice, g_scr.s) != hipSuccess ||
-      oai4g_launch_chest_symbol(dc, &h, dr, de, Ns, l, symbol, g_scr.s) != hipSuccess ||
-      !(symbol == 0 ? rows_d2h(p3 + 1, nsymb - 1 - p3) && rows_d2h(0, 1) : rows_d2h(prev_row + 1, symbol - prev_row)) ||
-      hipStreamSynchronize(g_scr.s) != hipSuccess) {
-    set_err("lte_dl_channel_estimation: HIP error");
-    return -1;
-  }
+  auto rows_d2h = [&](uint32_t r0, uint32_t n) { return st.down(dl_ch_estimates + (size_t)r0 * N, r_e, n * rb, r0 * rb); };
+  HCK(st.up(r_c, &h, sizeof(h)), -1);
+  HCK(st.up(r_e, dl_ch_estimates + (size_t)prev_row * N, rb, prev_row * rb), -1);
+  HCK(st.up(r_r, rxdataF + (size_t)symbol * N, rb), -1);
+  HCK(oai4g_launch_chest_symbol(st.ptr<chest_dev_t>(r_c), &h, st.ptr<int32_t>(r_r), st.ptr<int32_t>(r_e), Ns, l, symbol,
+                                g_scr.s), -1);
+  if (symbol == 0) {
+    HCK(rows_d2h(p3 + 1, nsymb - 1 - p3), -1);
+    HCK(rows_d2h(0, 1), -1);
+  } else
+    HCK(rows_d2h(prev_row + 1, symbol - prev_row), -1);
+  HCK(st.sync(), -1);
   return 0;
 }
 
@@ -4811,14 +4818,14 @@ extern "C" int oai4g_lte_est_freq_offset(int32_t *const *dl_ch_estimates, const 
   uint32_t ro, po;
   if (fo_rows(fp, l, &ro, &po) != 0) return -1;
   const size_t words = (size_t)(4 - fp->Ncp + 1) * fp->ofdm_symbol_size;   /* rows 0 .. 4 - Ncp */
-  uint8_t *buf = scratch(words * 4 + 256);
-  if (!buf) return -1;
-  int32_t *d_est = (int32_t *)buf, *d_om = (int32_t *)(buf + ((words * 4 + 255) & ~(size_t)255));
+  stage_t st("lte_est_freq_offset");
+  const int r_est = st.add(words * 4), r_om = st.add(4, 252);
+  if (!st.open()) return -1;
   int32_t om = 0;
-  HCK(hipMemcpyAsync(d_est, dl_ch_estimates[0], words * 4, hipMemcpyHostToDevice, g_scr.s), -1);
-  HCK(oai4g_launch_freq_offset(d_est, 0, 1, fp->N_RB_DL, ro, po, d_om, g_scr.s), -1);
-  HCK(hipMemcpyAsync(&om, d_om, 4, hipMemcpyDeviceToHost, g_scr.s), -1);
-  HCK(hipStreamSynchronize(g_scr.s), -1);
+  HCK(st.up(r_est, dl_ch_estimates[0], words * 4), -1);
+  HCK(oai4g_launch_freq_offset(st.ptr<int32_t>(r_est), 0, 1, fp->N_RB_DL, ro, po, st.ptr<int32_t>(r_om), g_scr.s), -1);
+  HCK(st.down(&om, r_om, 4), -1);
+  HCK(st.sync(), -1);
   return oai4g_freq_offset_update(fp, om, freq_offset, &g_fo_first_run);
 }
 
@@ -4859,15 +4866,14 @@ extern "C" int oai4g_dl_ch_estimates_time(const oai4g_frame_parms_t *fp, int nb_
       if (dl_ch_estimates[(p << 1) + aarx]) planes[np++] = (p << 1) + aarx;
   if (np == 0) return 0;
   const size_t ib = (size_t)np * in_w * 4, ob = (size_t)np * n * 4;
-  uint8_t *buf = scratch(ib + ob + 256);
-  if (!buf) return -1;
-  int32_t *d_in = (int32_t *)buf, *d_out = (int32_t *)(buf + ((ib + 255) & ~(size_t)255));
-  for (int i = 0; i < np; i++)
-    HCK(hipMemcpyAsync(d_in + i * in_w, dl_ch_estimates[planes[i]], in_w * 4, hipMemcpyHostToDevice, g_scr.s), -1);
-  HCK(oai4g_launch_idft_strided(d_in, d_out, l2, np, in_w, 8, n, 1, g_tw, g_scr.s), -1);   /* words 8 .. N + 7 */
-  for (int i = 0; i < np; i++)
-    HCK(hipMemcpyAsync(dl_ch_estimates_time[planes[i]], d_out + i * n, n * 4, hipMemcpyDeviceToHost, g_scr.s), -1);
-  HCK(hipStreamSynchronize(g_scr.s), -1);
+  stage_t st("dl_ch_estimates_time");
+  const int r_in = st.add(ib), r_out = st.add(ob, 256);
+  if (!st.open()) return -1;
+  for (int i = 0; i < np; i++) HCK(st.up(r_in, dl_ch_estimates[planes[i]], in_w * 4, i * in_w * 4), -1);
+  HCK(oai4g_launch_idft_strided(st.ptr<int32_t>(r_in), st.ptr<int32_t>(r_out), l2, np, in_w, 8, n, 1, g_tw, g_scr.s),
+      -1);                                    /* words 8 .. N + 7 */
+  for (int i = 0; i < np; i++) HCK(st.down(dl_ch_estimates_time[planes[i]], r_out, n * 4, i * n * 4), -1);
+  HCK(st.sync(), -1);
   return 0;
 }
 
@@ -4881,8 +4887,6 @@ extern "C" int oai4g_dl_ch_estimates_time(const oai4g_frame_parms_t *fp, int nb_
  * d[3 (32 row + bitrev_cc[col] - ND) + s] */
 static void cc_rx_plan_h(uint32_t D, uint16_t *plan)
 {
-  static const uint8_t bitrev_cc[32] = {1, 17, 9, 25, 5, 21, 13, 29, 3, 19, 11, 27, 7, 23, 15, 31,
-                                        0, 16, 8, 24, 4, 20, 12, 28, 2, 18, 10, 26, 6, 22, 14, 30};
   const uint32_t R = (D + 31) >> 5, ND = 32 * R - D;
   for (uint32_t s = 0; s < 3; s++) {
     uint32_t j = 0;
@@ -4908,34 +4912,35 @@ static int cc_decode_one(const char *who, const int8_t *e, size_t e_bytes, cc_jo
                          uint32_t n_plan, const uint32_t *gold, uint32_t n_gold, uint8_t quarter, bool raw,
                          uint8_t rec[CC_REC], uint8_t *metrics)
 {
-  const size_t o_job = (e_bytes + 255) & ~(size_t)255, o_plan = o_job + 256, o_gold = o_plan + 2048, o_q = o_gold + 512,
-               o_rec = o_q + 256, o_met = o_rec + 256;
-  uint8_t *buf = scratch(o_met + 256);
-  if (!buf) { set_err("%s: scratch allocation failed", who); return -1; }
+  stage_t st(who);
+  const int r_e = st.add(e_bytes), r_job = st.add(sizeof(cc_job_t), 244);
+  const int r_plan = st.add(3 * 61 * 2, 1682), r_gold = st.add(60 * 4, 272);   /* the largest plan (D = 45 + 16), the PBCH's words */
+  const int r_q = st.add(1, 255), r_rec = st.add(CC_REC, 188), r_met = st.add(64, 192 + 256);
+  if (!st.open()) return -1;
   job.e_off = 0;
   job.plan_off = 0;
-  HCK(hipMemcpyAsync(buf, e, e_bytes, hipMemcpyHostToDevice, g_scr.s), -1);
-  HCK(hipMemcpyAsync(buf + o_job, &job, sizeof(job), hipMemcpyHostToDevice, g_scr.s), -1);
-  if (n_plan) HCK(hipMemcpyAsync(buf + o_plan, plan, (size_t)n_plan * 2, hipMemcpyHostToDevice, g_scr.s), -1);
-  if (n_gold) HCK(hipMemcpyAsync(buf + o_gold, gold, (size_t)n_gold * 4, hipMemcpyHostToDevice, g_scr.s), -1);
-  HCK(hipMemcpyAsync(buf + o_q, &quarter, 1, hipMemcpyHostToDevice, g_scr.s), -1);
+  HCK(st.up(r_e, e, e_bytes), -1);
+  HCK(st.up(r_job, &job, sizeof(job)), -1);
+  if (n_plan) HCK(st.up(r_plan, plan, (size_t)n_plan * 2), -1);
+  if (n_gold) HCK(st.up(r_gold, gold, (size_t)n_gold * 4), -1);
+  HCK(st.up(r_q, &quarter, 1), -1);
   cc_args_t a;
   memset(&a, 0, sizeof(a));
-  a.e = (const int8_t *)buf;
+  a.e = st.ptr<const int8_t>(r_e);
   a.e_stride = 0;
-  a.jobs = (const cc_job_t *)(buf + o_job);
+  a.jobs = st.ptr<const cc_job_t>(r_job);
   a.n_jobs = a.n_items = 1;
-  a.plan = (const uint16_t *)(buf + o_plan);
-  a.gold = n_gold ? (const uint32_t *)(buf + o_gold) : nullptr;
-  a.quarter = buf + o_q;
-  a.out = buf + o_rec;
+  a.plan = st.ptr<const uint16_t>(r_plan);
+  a.gold = n_gold ? st.ptr<const uint32_t>(r_gold) : nullptr;
+  a.quarter = st.ptr(r_q);
+  a.out = st.ptr(r_rec);
   a.out_stride = CC_REC;
-  a.metrics = metrics ? buf + o_met : nullptr;
+  a.metrics = metrics ? st.ptr(r_met) : nullptr;
   a.raw = raw ? 1 : 0;
   HCK(oai4g_launch_cc_decode(a, job.D, g_scr.s), -1);
-  HCK(hipMemcpyAsync(rec, buf + o_rec, CC_REC, hipMemcpyDeviceToHost, g_scr.s), -1);
-  if (metrics) HCK(hipMemcpyAsync(metrics, buf + o_met, 64, hipMemcpyDeviceToHost, g_scr.s), -1);
-  HCK(hipStreamSynchronize(g_scr.s), -1);
+  HCK(st.down(rec, r_rec, CC_REC), -1);
+  if (metrics) HCK(st.down(metrics, r_met, 64), -1);
+  HCK(st.sync(), -1);
   return 0;
 }
 
@@ -5001,14 +5006,8 @@ extern "C" int oai4g_dci_decoding(uint8_t DCI_LENGTH, uint8_t aggregation_level,
 /* lte_gold_generic words of c_init = Nid_cell over the PBCH's E soft bits (pbch_unscrambling, pbch.c:785) */
 static uint32_t pbch_gold_h(uint32_t Nid, uint32_t E, uint32_t w[60])
 {
-  uint32_t x1 = 1u + (1u << 31), x2 = Nid;
-  x2 = x2 ^ ((x2 ^ (x2 >> 1) ^ (x2 >> 2) ^ (x2 >> 3)) << 31);
-  for (int n = 1; n < 50; n++) gold_step_h(&x1, &x2);
   const uint32_t nw = (E + 31) / 32;
-  for (uint32_t i = 0; i < nw; i++) {
-    gold_step_h(&x1, &x2);
-    w[i] = x1 ^ x2;
-  }
+  gold_seq_h(Nid, w, nw);
   return nw;
 }
 
@@ -5104,8 +5103,6 @@ static int pdcch_rx_geometry_ok(const char *who, const oai4g_frame_parms_t *fp, 
 /* tab[i], soft bit i of e_rx: int16 index into rxdataF_comp | negate << 31, or OAI4G_PDCCH_NONE */
 static int pdcch_soft_table_h(const oai4g_frame_parms_t *fp, uint8_t subframe, uint8_t npd, std::vector<uint32_t> &tab)
 {
-  static const uint8_t bitrev_cc[32] = {1, 17, 9, 25, 5, 21, 13, 29, 3, 19, 11, 27, 7, 23, 15, 31,
-                                        0, 16, 8, 24, 4, 20, 12, 28, 2, 18, 10, 26, 6, 22, 14, 30};
   const uint8_t mi = oai4g_get_mi(fp, subframe);
   const uint32_t Mquad = oai4g_get_nquad(npd, fp, mi), NRE = (uint32_t)fp->N_RB_DL * 12;
   const int Msymb = ((2 * 33 + 22) * 72) / 2;
@@ -5163,18 +5160,13 @@ static int pdcch_soft_table_h(const oai4g_frame_parms_t *fp, uint8_t subframe, u
       }
   /* pdcch_unscrambling (:1932-1961) over 72 nCCE soft bits */
   const uint32_t n = 8 * Mquad, nuns = 72u * (Mquad / 9);
-  uint32_t x1 = 1u + (1u << 31), x2 = ((uint32_t)subframe << 9) + fp->Nid_cell, sw = 0;
-  x2 = x2 ^ ((x2 ^ (x2 >> 1) ^ (x2 >> 2) ^ (x2 >> 3)) << 31);
-  for (int q = 1; q < 50; q++) gold_step_h(&x1, &x2);
+  std::vector<uint32_t> sw((n + 31) / 32);
+  gold_seq_h(((uint32_t)subframe << 9) + fp->Nid_cell, sw.data(), sw.size());
   tab.assign(n, OAI4G_PDCCH_NONE);
   for (uint32_t i = 0; i < n; i++) {
-    if ((i & 31) == 0) {
-      gold_step_h(&x1, &x2);
-      sw = x1 ^ x2;
-    }
     const uint32_t re = z[i >> 1];
     if (re == OAI4G_PDCCH_NONE) continue;
-    const uint32_t neg = (i < nuns && ((sw >> (i & 31)) & 1u) == 0) ? 1u : 0u;
+    const uint32_t neg = (i < nuns && ((sw[i >> 5] >> (i & 31)) & 1u) == 0) ? 1u : 0u;
     tab[i] = (2 * re + (i & 1)) | (neg << 31);
   }
   return (int)n;
@@ -5199,15 +5191,16 @@ extern "C" int oai4g_pdcch_soft_bits(const int32_t *rxdataF_comp, const oai4g_fr
   NEED_INIT(-1);
   std::vector<uint32_t> tab;
   const int n = pdcch_soft_table_h(fp, subframe, npd, tab);
-  const size_t cb = (size_t)npd * fp->N_RB_DL * 12 * 4, o_tab = (cb + 255) & ~(size_t)255,
-               o_e = o_tab + (((size_t)n * 4 + 255) & ~(size_t)255);
-  uint8_t *buf = scratch(o_e + (size_t)n + 256);
-  if (!buf) { set_err("pdcch_soft_bits: scratch allocation failed"); return -1; }
-  HCK(hipMemcpyAsync(buf, rxdataF_comp, cb, hipMemcpyHostToDevice, g_scr.s), -1);
-  HCK(hipMemcpyAsync(buf + o_tab, tab.data(), (size_t)n * 4, hipMemcpyHostToDevice, g_scr.s), -1);
-  HCK(oai4g_launch_pdcch_soft((const int16_t *)buf, (const uint32_t *)(buf + o_tab), (uint32_t)n, (int8_t *)(buf + o_e), g_scr.s), -1);
-  HCK(hipMemcpyAsync(e_rx, buf + o_e, (size_t)n, hipMemcpyDeviceToHost, g_scr.s), -1);
-  HCK(hipStreamSynchronize(g_scr.s), -1);
+  const size_t cb = (size_t)npd * fp->N_RB_DL * 12 * 4;
+  stage_t st("pdcch_soft_bits");
+  const int r_comp = st.add(cb), r_tab = st.add((size_t)n * 4), r_e = st.add((size_t)n, 256);
+  if (!st.open()) return -1;
+  HCK(st.up(r_comp, rxdataF_comp, cb), -1);
+  HCK(st.up(r_tab, tab.data(), (size_t)n * 4), -1);
+  HCK(oai4g_launch_pdcch_soft(st.ptr<const int16_t>(r_comp), st.ptr<const uint32_t>(r_tab), (uint32_t)n,
+                              st.ptr<int8_t>(r_e), g_scr.s), -1);
+  HCK(st.down(e_rx, r_e, (size_t)n), -1);
+  HCK(st.sync(), -1);
   return n;
 }
 
@@ -5280,25 +5273,26 @@ extern "C" int oai4g_dci_decoding_procedure0(const int8_t *e_rx, uint8_t npd, ui
   }
   uint16_t plan[3 * 61];
   cc_rx_plan_h(D, plan);
-  const size_t o_job = (eb + 255) & ~(size_t)255, o_plan = o_job + 1024, o_rec = o_plan + 512;
-  uint8_t *buf = scratch(o_rec + 1024);
-  if (!buf) { set_err("dci_decoding_procedure0: scratch allocation failed"); return -1; }
   uint8_t rec[16 * OAI4G_PDCCH_REC];
-  HCK(hipMemcpyAsync(buf, e_rx, eb, hipMemcpyHostToDevice, g_scr.s), -1);
-  HCK(hipMemcpyAsync(buf + o_job, jobs.data(), nc * sizeof(cc_job_t), hipMemcpyHostToDevice, g_scr.s), -1);
-  HCK(hipMemcpyAsync(buf + o_plan, plan, (size_t)3 * D * 2, hipMemcpyHostToDevice, g_scr.s), -1);
+  stage_t sg("dci_decoding_procedure0");   /* room for the 16 candidates of rec and the largest plan, D = 45 + 16 */
+  const int r_e = sg.add(eb), r_job = sg.add(sizeof(cc_job_t) * 16, 832);
+  const int r_plan = sg.add(3 * 61 * 2, 146), r_rec = sg.add(sizeof(rec), 768);
+  if (!sg.open()) return -1;
+  HCK(sg.up(r_e, e_rx, eb), -1);
+  HCK(sg.up(r_job, jobs.data(), nc * sizeof(cc_job_t)), -1);
+  HCK(sg.up(r_plan, plan, (size_t)3 * D * 2), -1);
   cc_args_t a;
   memset(&a, 0, sizeof(a));
-  a.e = (const int8_t *)buf;
-  a.jobs = (const cc_job_t *)(buf + o_job);
+  a.e = sg.ptr<const int8_t>(r_e);
+  a.jobs = sg.ptr<const cc_job_t>(r_job);
   a.n_jobs = nc;
   a.n_items = 1;
-  a.plan = (const uint16_t *)(buf + o_plan);
-  a.out = buf + o_rec;
+  a.plan = sg.ptr<const uint16_t>(r_plan);
+  a.out = sg.ptr(r_rec);
   a.out_stride = OAI4G_PDCCH_REC;
   HCK(oai4g_launch_cc_decode(a, D, g_scr.s), -1);
-  HCK(hipMemcpyAsync(rec, buf + o_rec, (size_t)nc * OAI4G_PDCCH_REC, hipMemcpyDeviceToHost, g_scr.s), -1);
-  HCK(hipStreamSynchronize(g_scr.s), -1);
+  HCK(sg.down(rec, r_rec, (size_t)nc * OAI4G_PDCCH_REC), -1);
+  HCK(sg.sync(), -1);
   pdcch_state_t st = {};
   st.map[0] = *CCEmap0;
   st.map[1] = *CCEmap1;
@@ -5391,13 +5385,12 @@ extern "C" oai4g_pdcch_rx_config_t *oai4g_pdcch_rx_config_create(const oai4g_fra
   }
   if (cfg->n_jobs == 0) cfg->n_jobs = 1;
   const uint32_t nj = cfg->n_jobs;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  cfg->o_jobs = up((size_t)10 * cfg->tab_stride * 4);
-  cfg->o_cands = cfg->o_jobs + up((size_t)10 * nj * sizeof(cc_job_t));
-  cfg->o_ncand = cfg->o_cands + up((size_t)10 * nj * sizeof(pdcch_cand_t));
-  cfg->o_plans = cfg->o_ncand + 256;
-  cfg->o_ccplan = cfg->o_plans + up((size_t)n_plan * sizeof(oai4g_pdcch_plan_t));
-  const size_t total = cfg->o_ccplan + up(ccplan.size() * 2);
+  cfg->o_jobs = up256((size_t)10 * cfg->tab_stride * 4);
+  cfg->o_cands = cfg->o_jobs + up256((size_t)10 * nj * sizeof(cc_job_t));
+  cfg->o_ncand = cfg->o_cands + up256((size_t)10 * nj * sizeof(pdcch_cand_t));
+  cfg->o_plans = cfg->o_ncand + up256(10 * 4);
+  cfg->o_ccplan = cfg->o_plans + up256((size_t)n_plan * sizeof(oai4g_pdcch_plan_t));
+  const size_t total = cfg->o_ccplan + up256(ccplan.size() * 2);
   std::vector<uint8_t> h(total, 0);
   for (uint32_t sf = 0; sf < 10; sf++) {
     uint32_t *t = (uint32_t *)h.data() + (size_t)sf * cfg->tab_stride;
@@ -5436,6 +5429,50 @@ extern "C" int oai4g_pdcch_rx_candidates(const oai4g_pdcch_rx_config_t *cfg, uin
   return (int)v.size();
 }
 
+/* the record buffer of a PDCCH batch, kept in `own`: grown when `need` bytes do not fit, then cleared together
+ * with the results (unwritten fields and slots read as 0) */
+static int pdcch_batch_clear(oai4g_pdcch_rx_config_t *own, size_t need, oai4g_pdcch_rx_result_t *d_out, int n_sf, hipStream_t s)
+{
+  if (need > own->rec_cap) {
+    HCK(hipDeviceSynchronize(), -1);
+    if (own->d_rec) hipFree(own->d_rec);
+    own->d_rec = nullptr;
+    own->rec_cap = 0;
+    HCK(hipMalloc(&own->d_rec, need), -1);
+    own->rec_cap = need;
+  }
+  HCK(hipMemsetAsync(own->d_rec, 0, need, s), -1);
+  HCK(hipMemsetAsync(d_out, 0, (size_t)n_sf * sizeof(oai4g_pdcch_rx_result_t), s), -1);
+  return 0;
+}
+
+/* what the decode and the resolve stage of both batches take from a configuration: its tables, jobs, candidates
+ * and plans, nj records per subframe, npd control symbols per compensated subframe */
+static void pdcch_batch_args(const oai4g_pdcch_rx_config_t *c, uint32_t nj, uint32_t npd, const int32_t *d_comp, int n_sf,
+                             int first_subframe, oai4g_pdcch_rx_result_t *d_out, cc_args_t &a, pdcch_resolve_args_t &r)
+{
+  a.jobs = (const cc_job_t *)(c->dev + c->o_jobs);
+  a.n_jobs = nj;
+  a.n_items = (uint32_t)n_sf;
+  a.plan = (const uint16_t *)(c->dev + c->o_ccplan);
+  a.out = c->d_rec;
+  a.out_stride = OAI4G_PDCCH_REC;
+  a.tab = (const uint32_t *)c->dev;
+  a.tab_stride = c->tab_stride;
+  a.comp = (const int16_t *)d_comp;
+  a.comp_stride = (size_t)npd * c->fp.N_RB_DL * 12 * 2;
+  a.first_row = (uint32_t)first_subframe;
+  r.rec = c->d_rec;
+  r.cands = (const pdcch_cand_t *)(c->dev + c->o_cands);
+  r.n_cand = (const uint32_t *)(c->dev + c->o_ncand);
+  r.plans = (const oai4g_pdcch_plan_t *)(c->dev + c->o_plans);
+  r.n_jobs = nj;
+  r.n_sf = (uint32_t)n_sf;
+  r.first_row = (uint32_t)first_subframe;
+  r.crnti = c->crnti, r.si_rnti = c->si_rnti, r.ra_rnti = c->ra_rnti;
+  r.out = d_out;
+}
+
 extern "C" int oai4g_pdcch_rx_batch(oai4g_pdcch_rx_config_t *cfg, const int32_t *d_comp, int n_sf, int first_subframe,
                                     oai4g_pdcch_rx_result_t *d_out, void *stream)
 {
@@ -5445,45 +5482,14 @@ extern "C" int oai4g_pdcch_rx_batch(oai4g_pdcch_rx_config_t *cfg, const int32_t 
   }
   NEED_INIT(-1);
   if (n_sf == 0) return 0;
-  const size_t need = (size_t)n_sf * cfg->n_jobs * OAI4G_PDCCH_REC;
-  if (need > cfg->rec_cap) {
-    HCK(hipDeviceSynchronize(), -1);
-    if (cfg->d_rec) hipFree(cfg->d_rec);
-    cfg->d_rec = nullptr;
-    cfg->rec_cap = 0;
-    HCK(hipMalloc(&cfg->d_rec, need), -1);
-    cfg->rec_cap = need;
-  }
   hipStream_t s = (hipStream_t)stream;
-  HCK(hipMemsetAsync(cfg->d_rec, 0, need, s), -1);
-  HCK(hipMemsetAsync(d_out, 0, (size_t)n_sf * sizeof(oai4g_pdcch_rx_result_t), s), -1);   /* unwritten fields and slots read as 0 */
+  if (pdcch_batch_clear(cfg, (size_t)n_sf * cfg->n_jobs * OAI4G_PDCCH_REC, d_out, n_sf, s) != 0) return -1;
   cc_args_t a;
-  memset(&a, 0, sizeof(a));
-  a.jobs = (const cc_job_t *)(cfg->dev + cfg->o_jobs);
-  a.n_jobs = cfg->n_jobs;
-  a.n_items = (uint32_t)n_sf;
-  a.plan = (const uint16_t *)(cfg->dev + cfg->o_ccplan);
-  a.out = cfg->d_rec;
-  a.out_stride = OAI4G_PDCCH_REC;
-  a.tab = (const uint32_t *)cfg->dev;
-  a.tab_stride = cfg->tab_stride;
-  a.comp = (const int16_t *)d_comp;
-  a.comp_stride = (size_t)cfg->npd * cfg->fp.N_RB_DL * 12 * 2;
-  a.first_row = (uint32_t)first_subframe;
-  HCK(oai4g_launch_cc_decode(a, 61, s), -1);
   pdcch_resolve_args_t r;
+  memset(&a, 0, sizeof(a));
   memset(&r, 0, sizeof(r));
-  r.rec = cfg->d_rec;
-  r.cands = (const pdcch_cand_t *)(cfg->dev + cfg->o_cands);
-  r.n_cand = (const uint32_t *)(cfg->dev + cfg->o_ncand);
-  r.plans = (const oai4g_pdcch_plan_t *)(cfg->dev + cfg->o_plans);
-  r.n_jobs = cfg->n_jobs;
-  r.n_sf = (uint32_t)n_sf;
-  r.first_row = (uint32_t)first_subframe;
-  r.crnti = cfg->crnti;
-  r.si_rnti = cfg->si_rnti;
-  r.ra_rnti = cfg->ra_rnti;
-  r.out = d_out;
+  pdcch_batch_args(cfg, cfg->n_jobs, cfg->npd, d_comp, n_sf, first_subframe, d_out, a, r);
+  HCK(oai4g_launch_cc_decode(a, 61, s), -1);
   HCK(oai4g_launch_pdcch_resolve(r, s), -1);
   return 0;
 }
@@ -5512,23 +5518,14 @@ extern "C" int oai4g_pdcch_rx_batch_detected(oai4g_pdcch_rx_config_t *const cfg[
   if (n_sf == 0) return 0;
   uint32_t nj = 0;
   for (int i = 0; i < 3; i++) nj = std::max(nj, cfg[i]->n_jobs);
-  oai4g_pdcch_rx_config_t *own = cfg[2];
-  const size_t need = (size_t)n_sf * nj * OAI4G_PDCCH_REC;
-  if (need > own->rec_cap) {
-    HCK(hipDeviceSynchronize(), -1);
-    if (own->d_rec) hipFree(own->d_rec);
-    own->d_rec = nullptr;
-    own->rec_cap = 0;
-    HCK(hipMalloc(&own->d_rec, need), -1);
-    own->rec_cap = need;
-  }
+  oai4g_pdcch_rx_config_t *own = cfg[2];   /* holds the records; its tables are the base arguments' */
   hipStream_t s = (hipStream_t)stream;
-  HCK(hipMemsetAsync(own->d_rec, 0, need, s), -1);
-  HCK(hipMemsetAsync(d_out, 0, (size_t)n_sf * sizeof(oai4g_pdcch_rx_result_t), s), -1);
+  if (pdcch_batch_clear(own, (size_t)n_sf * nj * OAI4G_PDCCH_REC, d_out, n_sf, s) != 0) return -1;
   cc_det_args_t a;
   pdcch_resolve_det_args_t r;
   memset(&a, 0, sizeof(a));
   memset(&r, 0, sizeof(r));
+  pdcch_batch_args(own, nj, 3, d_comp, n_sf, first_subframe, d_out, a, r);
   for (int i = 0; i < 3; i++) {
     const oai4g_pdcch_rx_config_t *c = cfg[i];
     pdcch_det_set_t &t = a.set[i];
@@ -5541,32 +5538,9 @@ extern "C" int oai4g_pdcch_rx_batch_detected(oai4g_pdcch_rx_config_t *const cfg[
     t.tab_stride = c->tab_stride;
     r.set[i] = t;
   }
-  a.jobs = a.set[2].jobs;
-  a.tab = a.set[2].tab;
-  a.plan = a.set[2].plan;
-  a.n_jobs = nj;
-  a.n_items = (uint32_t)n_sf;
-  a.out = own->d_rec;
-  a.out_stride = OAI4G_PDCCH_REC;
-  a.comp = (const int16_t *)d_comp;
-  a.comp_stride = (size_t)3 * own->fp.N_RB_DL * 12 * 2;
-  a.first_row = (uint32_t)first_subframe;
-  a.cfi = d_cfi;
-  a.sf_step = (uint32_t)subframe_step;
+  a.cfi = r.cfi = d_cfi;
+  a.sf_step = r.sf_step = (uint32_t)subframe_step;
   HCK(oai4g_launch_cc_decode_detected(a, s), -1);
-  r.rec = own->d_rec;
-  r.cands = r.set[2].cands;
-  r.n_cand = r.set[2].n_cand;
-  r.plans = (const oai4g_pdcch_plan_t *)(own->dev + own->o_plans);
-  r.n_jobs = nj;
-  r.n_sf = (uint32_t)n_sf;
-  r.first_row = (uint32_t)first_subframe;
-  r.crnti = own->crnti;
-  r.si_rnti = own->si_rnti;
-  r.ra_rnti = own->ra_rnti;
-  r.out = d_out;
-  r.cfi = d_cfi;
-  r.sf_step = (uint32_t)subframe_step;
   HCK(oai4g_launch_pdcch_resolve_detected(r, s), -1);
   return 0;
 }
@@ -5595,11 +5569,18 @@ static int pdcch_front_ok(const char *who, const oai4g_frame_parms_t *fp, int nb
 /* the first Gold word of pcfich_unscrambling (pcfich.c:122) */
 static uint32_t pcfich_gold_h(const oai4g_frame_parms_t *fp, uint32_t subframe)
 {
-  uint32_t x1 = 1u + (1u << 31), x2 = ((((2u * fp->Nid_cell) + 1u) * (1u + subframe)) << 9) + fp->Nid_cell;
-  x2 = x2 ^ ((x2 ^ (x2 >> 1) ^ (x2 >> 2) ^ (x2 >> 3)) << 31);
-  for (int q = 1; q < 50; q++) gold_step_h(&x1, &x2);
-  gold_step_h(&x1, &x2);
-  return x1 ^ x2;
+  uint32_t w;
+  gold_seq_h(((((2u * fp->Nid_cell) + 1u) * (1u + subframe)) << 9) + fp->Nid_cell, &w, 1);
+  return w;
+}
+
+/* the four PCFICH REGs as word offsets into the packed symbol 0 (four words a REG) */
+static void pcfich_words_h(const oai4g_frame_parms_t *fp, uint32_t w[4])
+{
+  uint16_t reg[4];
+  uint8_t fi;
+  pcfich_regs(fp, reg, &fi);
+  for (int q = 0; q < 4; q++) w[q] = (uint32_t)reg[q] * 4u;
 }
 
 static void pdcch_front_fill(pdcch_front_args_t &a, const oai4g_frame_parms_t *fp, int nb_rx, uint8_t mimo_mode,
@@ -5616,10 +5597,7 @@ static void pdcch_front_fill(pdcch_front_args_t &a, const oai4g_frame_parms_t *f
   a.high_speed = high_speed_flag == 1;
   a.first_sf = first_sf;
   a.sf_step = sf_step;
-  uint16_t reg[4];
-  uint8_t fi;
-  pcfich_regs(fp, reg, &fi);
-  for (int q = 0; q < 4; q++) a.pcf_word[q] = (uint32_t)reg[q] * 4u;
+  pcfich_words_h(fp, a.pcf_word);
   for (uint32_t sf = 0; sf < 10; sf++) a.pcf_gold[sf] = pcfich_gold_h(fp, sf);
 }
 
@@ -5635,33 +5613,34 @@ extern "C" int oai4g_rx_pdcch_front(int32_t *const *rxdataF, int32_t *const *dl_
       if (!rxdataF[a] || !dl_ch_estimates[(p << 1) + a]) { set_err("rx_pdcch_front: null plane"); return -1; }
   NEED_INIT(-1);
   const size_t rows = (size_t)3 * fp->ofdm_symbol_size * 4, out_b = (size_t)36 * fp->N_RB_DL * 4;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t o_est = 2 * up(rows), o_comp = o_est + 4 * up(rows), o_pl = o_comp + up(out_b), o_b = o_pl + 4 * up(out_b);
-  uint8_t *buf = scratch(o_b + 256);
-  if (!buf) { set_err("rx_pdcch_front: scratch allocation failed"); return -1; }
+  const size_t row_s = up256(rows);           /* an antenna's / a plane's three rows, a stride apart */
+  stage_t st("rx_pdcch_front");
+  const int r_rx = st.add(2 * row_s), r_est = st.add(4 * row_s), r_comp = st.add(out_b);
+  const int r_pl = st.add(4 * up256(out_b)), r_b = st.add(2, 254);   /* four diagnostic planes, out_b apart; cfi, log2_maxh */
+  if (!st.open()) return -1;
   pdcch_front_args_t a;
   pdcch_front_fill(a, fp, nb_antennas_rx, mimo_mode, high_speed_flag, subframe, 0);
   a.n_sf = 1;
-  a.rxF = (const int32_t *)buf;
-  a.rx_ant_stride = up(rows) / 4;
+  a.rxF = st.ptr<const int32_t>(r_rx);
+  a.rx_ant_stride = row_s / 4;
   for (int rx = 0; rx < nb_antennas_rx; rx++) {
-    HCK(hipMemcpyAsync(buf + rx * up(rows), rxdataF[rx], rows, hipMemcpyHostToDevice, g_scr.s), -1);
+    HCK(st.up(r_rx, rxdataF[rx], rows, rx * row_s), -1);
     for (int p = 0; p < nb_tx; p++) {
       const int pl = (p << 1) + rx;
-      HCK(hipMemcpyAsync(buf + o_est + pl * up(rows), dl_ch_estimates[pl], rows, hipMemcpyHostToDevice, g_scr.s), -1);
-      a.est[pl] = (const int32_t *)(buf + o_est + pl * up(rows));
+      HCK(st.up(r_est, dl_ch_estimates[pl], rows, pl * row_s), -1);
+      a.est[pl] = st.ptr<const int32_t>(r_est, pl * row_s);
     }
   }
-  a.comp = (int32_t *)(buf + o_comp);
-  a.planes = diag_planes ? (int32_t *)(buf + o_pl) : nullptr;
-  a.cfi = buf + o_b;
-  a.log2_maxh = buf + o_b + 1;
+  a.comp = st.ptr<int32_t>(r_comp);
+  a.planes = diag_planes ? st.ptr<int32_t>(r_pl) : nullptr;
+  a.cfi = st.ptr(r_b);
+  a.log2_maxh = st.ptr(r_b, 1);
   HCK(oai4g_launch_pdcch_front(a, g_scr.s), -1);
   uint8_t two[2] = {0, 0};
-  HCK(hipMemcpyAsync(rxdataF_comp, a.comp, out_b, hipMemcpyDeviceToHost, g_scr.s), -1);
-  if (diag_planes) HCK(hipMemcpy2DAsync(diag_planes, out_b, a.planes, out_b, out_b, 4, hipMemcpyDeviceToHost, g_scr.s), -1);
-  HCK(hipMemcpyAsync(two, buf + o_b, 2, hipMemcpyDeviceToHost, g_scr.s), -1);
-  HCK(hipStreamSynchronize(g_scr.s), -1);
+  HCK(st.down(rxdataF_comp, r_comp, out_b), -1);
+  if (diag_planes) HCK(st.down(diag_planes, r_pl, 4 * out_b), -1);
+  HCK(st.down(two, r_b, 2), -1);
+  HCK(st.sync(), -1);
   if (num_pdcch_symbols) *num_pdcch_symbols = two[0];
   if (log2_maxh) *log2_maxh = two[1];
   return 0;
@@ -5673,18 +5652,16 @@ extern "C" int oai4g_rx_pcfich(const oai4g_frame_parms_t *fp, uint8_t subframe, 
   if (subframe > 9 || !rxdataF_comp) { set_err("rx_pcfich: bad arguments"); return -1; }
   NEED_INIT(-1);
   const size_t cb = (size_t)8 * fp->N_RB_DL * 4;              /* the packed symbol 0 */
-  uint8_t *buf = scratch(cb + 512);
-  if (!buf) { set_err("rx_pcfich: scratch allocation failed"); return -1; }
-  uint16_t reg[4];
-  uint8_t fi, n = 0;
+  stage_t st("rx_pcfich");
+  const int r_comp = st.add(cb), r_n = st.add(1, 511);
+  if (!st.open()) return -1;
+  uint8_t n = 0;
   uint32_t w[4];
-  pcfich_regs(fp, reg, &fi);
-  for (int q = 0; q < 4; q++) w[q] = (uint32_t)reg[q] * 4u;
-  uint8_t *d_n = buf + ((cb + 255) & ~(size_t)255);
-  HCK(hipMemcpyAsync(buf, rxdataF_comp, cb, hipMemcpyHostToDevice, g_scr.s), -1);
-  HCK(oai4g_launch_rx_pcfich((const int32_t *)buf, w, pcfich_gold_h(fp, subframe), d_n, g_scr.s), -1);
-  HCK(hipMemcpyAsync(&n, d_n, 1, hipMemcpyDeviceToHost, g_scr.s), -1);
-  HCK(hipStreamSynchronize(g_scr.s), -1);
+  pcfich_words_h(fp, w);
+  HCK(st.up(r_comp, rxdataF_comp, cb), -1);
+  HCK(oai4g_launch_rx_pcfich(st.ptr<const int32_t>(r_comp), w, pcfich_gold_h(fp, subframe), st.ptr(r_n), g_scr.s), -1);
+  HCK(st.down(&n, r_n, 1), -1);
+  HCK(st.sync(), -1);
   return n;
 }
 

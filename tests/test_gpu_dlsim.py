@@ -23,14 +23,22 @@ def _ref_energy():
     return L
 
 
-@pytest.mark.parametrize("length,scale", [(7680, 600), (30720, 300), (1920, 32767), (7680, 32767), (15360, 9000)])
+GROWN = (16 << 20) + 4096      # samples: 64 MB + 16 KB of staging, past the drop-in scratch buffer's 64 MB floor
+
+
+@pytest.mark.parametrize("length,scale", [(7680, 600), (30720, 300), (1920, 32767), (7680, 32767), (15360, 9000),
+                                          (GROWN, 32767)])
 def test_gpu_signal_energy(gpu, length, scale):
     """k_signal_energy (batch and drop-in) = orc_signal_energy = the reference's signal_energy
     (compiled here when the reference tree was present) on random vectors, including full-scale
-    samples whose pmaddwd / sums wrap."""
+    samples whose pmaddwd / sums wrap.  The GROWN length makes the drop-in's scratch buffer grow
+    (the arithmetic wraps, so equality stays exact); a short call afterwards runs in the grown buffer."""
     rng = np.random.default_rng(length + scale)
-    n = 6
-    x = (rng.integers(-scale, scale + 1, (n, length, 2)).astype(np.int16)).view(np.int32).reshape(n, length)
+    n = 6 if length < GROWN else 3                       # 64 MB a vector: rows 1 and 2 are the ones with a role
+    if length < GROWN:
+        x = (rng.integers(-scale, scale + 1, (n, length, 2)).astype(np.int16)).view(np.int32).reshape(n, length)
+    else:                                                # drawn as int16: no 64-bit intermediate of 800 MB
+        x = rng.integers(-scale, scale + 1, (n, length, 2), dtype=np.int16).view(np.int32).reshape(n, length)
     x[1, :] = x[1, 0]                                    # a strong DC component
     want = [O.orc().orc_signal_energy(O.P(np.ascontiguousarray(x[i])), length) for i in range(n)]
     R = _ref_energy()
@@ -46,6 +54,9 @@ def test_gpu_signal_energy(gpu, length, scale):
     L.oai4g_dev_free(d_e)
     assert got.tolist() == [int(np.int32(w)) for w in want]
     assert L.oai4g_signal_energy(gpu._ptr(np.ascontiguousarray(x[2])), length) == np.int32(want[2])
+    if length == GROWN:
+        short = np.ascontiguousarray(x[2, :7680])
+        assert L.oai4g_signal_energy(gpu._ptr(short), 7680) == np.int32(O.orc().orc_signal_energy(O.P(short), 7680))
 
 
 def test_gpu_awgn_statistics(gpu):

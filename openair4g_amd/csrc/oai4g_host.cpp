@@ -25,6 +25,7 @@
 #include "../../include/oai4g_qpp.h"
 #include "../../include/oai4g_tbs.h"
 #include "oai4g_internal.h"
+#include "oai4g_dev_buf.h"
 
 /* ------------------------------------------------------------------------------------------
  * errors
@@ -229,17 +230,19 @@ static void do_init(void)
     h_gx1[l] = x1;
     for (int b = 0; b < 32; b++) h_gx2j[OAI4G_GOLD_LANES * b + l] = cols[b];   /* [b][lane]: coalesced */
   }
-  if (hipMalloc(&g_tw, tw.size() * 4) != hipSuccess || hipMalloc(&g_twf, twf.size() * 4) != hipSuccess ||
-      hipMemcpy(g_twf, twf.data(), twf.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMalloc(&g_gx1, sizeof(h_gx1)) != hipSuccess ||
-      hipMalloc(&g_gx2j, sizeof(h_gx2j)) != hipSuccess ||
-      hipMemcpy(g_tw, tw.data(), tw.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(g_gx1, h_gx1, sizeof(h_gx1), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(g_gx2j, h_gx2j, sizeof(h_gx2j), hipMemcpyHostToDevice) != hipSuccess) {
+  dev_buf<uint32_t> d_tw, d_twf, d_gx1, d_gx2j;
+  if (d_tw.upload(tw) != hipSuccess || d_twf.upload(twf) != hipSuccess ||
+      d_gx1.upload(h_gx1, OAI4G_GOLD_LANES) != hipSuccess ||
+      d_gx2j.upload(h_gx2j, OAI4G_GOLD_LANES * 32) != hipSuccess) {
     snprintf(g_init_err, sizeof(g_init_err), "device table upload failed");
     g_init_status = -3;
     return;
   }
+  /* process lifetime: released, never freed (the HIP runtime may be gone when statics are destroyed) */
+  g_tw = d_tw.release();
+  g_twf = d_twf.release();
+  g_gx1 = d_gx1.release();
+  g_gx2j = d_gx2j.release();
   g_init_status = 0;
 }
 
@@ -856,17 +859,17 @@ struct oai4g_tx_config {
   oai4g_tx_params_t p;
   oai4g_frame_parms_t fp;
   cfg_dev_t h;                      /* host mirror */
-  cfg_dev_t *d = nullptr;           /* device copy */
-  uint16_t *d_remap = nullptr;
+  dev_buf<cfg_dev_t> d;             /* device copy */
+  dev_buf<uint16_t> d_remap;
   std::vector<uint16_t> h_remap;
-  uint32_t *d_gold = nullptr;           /* [10][n_cw][ebits_words] scrambling words */
-  enc_rv_tab_t *d_rvtab = nullptr;      /* [4][n_cw] per-rv plan tables (oai4g_tx_config_enable_tb_rv), else null */
+  dev_buf<uint32_t> d_gold;             /* [10][n_cw][ebits_words] scrambling words */
+  dev_buf<enc_rv_tab_t> d_rvtab;        /* [4][n_cw] per-rv plan tables (oai4g_tx_config_enable_tb_rv), else empty */
   /* build_stat_tm's inputs (host only) */
   std::vector<uint32_t> h_crs;          /* [10][6][200] packed CRS IQ of pilot entry i, index m (empty without CRS) */
   std::vector<uint32_t> h_ctl;          /* [10][14][ctl_planes][N] packed IQ of the static REs of set_control /
                                            set_common per antenna (empty without them) */
   uint32_t ctl_planes = 2;              /* 2, or the TX antennas when there are more */
-  uint32_t *d_stat = nullptr;           /* cfg_dev_t::stat_tm */
+  dev_buf<uint32_t> d_stat;             /* cfg_dev_t::stat_tm */
   int ctl_vmax = 0;                     /* largest I / Q magnitude in the static-RE table (mod_nosat_ok) */
   std::vector<oai4g_dci_alloc_t> dci;   /* oai4g_tx_config_set_control's DCI set */
   uint8_t n_ue_dci = 0, n_common_dci = 0;
@@ -881,6 +884,13 @@ struct oai4g_tx_config {
   hipEvent_t ev_enc[OAI4G_PIPE_MAX_CHUNKS] = {};
   hipEvent_t ev_done = nullptr;
   int pipe_chunk = 0;
+  ~oai4g_tx_config()
+  {
+    for (auto &e : ev_enc)
+      if (e) hipEventDestroy(e);
+    if (ev_done) hipEventDestroy(ev_done);
+    if (s_mod) hipStreamDestroy(s_mod);
+  }
 };
 
 /* The sub-block interleaver + rate matcher plan of block size ki (k_encode phase 4;
@@ -1367,11 +1377,12 @@ static int derive_cfg(oai4g_tx_config *cfg, const oai4g_tx_params_t *p, const ui
  * PSS and SSS every antenna).  k_modofdm ORs the plane over its data path. */
 static int build_stat_tm(oai4g_tx_config *cfg)
 {
-  if (cfg->d_stat) hipFree(cfg->d_stat);
-  cfg->d_stat = nullptr;
-  cfg->h.stat_tm = nullptr;
-  cfg->h.stat_planes = 0;
-  if (cfg->h_remap.empty() || (cfg->h_crs.empty() && cfg->h_ctl.empty())) return 0;
+  if (cfg->h_remap.empty() || (cfg->h_crs.empty() && cfg->h_ctl.empty())) {
+    cfg->d_stat.reset();
+    cfg->h.stat_tm = nullptr;
+    cfg->h.stat_planes = 0;
+    return 0;
+  }
   const size_t N = cfg->h.N, T = N >> 4, nsl = cfg->h_remap.size() / N;
   const uint32_t planes = cfg->h.mimo_mode == OAI4G_SISO ? 1u : cfg->h.n_ant;
   std::vector<uint32_t> st(nsl * planes * N, 0u);
@@ -1392,20 +1403,18 @@ static int build_stat_tm(oai4g_tx_config *cfg)
       }
     }
   }
-  HCK(hipMalloc(&cfg->d_stat, st.size() * 4), -1);
-  HCK(hipMemcpy(cfg->d_stat, st.data(), st.size() * 4, hipMemcpyHostToDevice), -1);
-  cfg->h.stat_tm = cfg->d_stat;
+  HCK(cfg->d_stat.upload(st), -1);
+  cfg->h.stat_tm = cfg->d_stat.get();
   cfg->h.stat_planes = planes;
   return 0;
 }
 
 static int upload_remap(oai4g_tx_config *cfg)
 {
-  if (cfg->d_remap) hipFree(cfg->d_remap);
-  cfg->d_remap = nullptr;
-  if (!cfg->h_remap.empty()) {
+  const size_t n = cfg->h_remap.size();
+  if (n) {
     /* the natural layout k_modulate_bytes reads, then k_modofdm's thread-major copy */
-    const size_t n = cfg->h_remap.size(), N = cfg->h.N, T = N >> 4;
+    const size_t N = cfg->h.N, T = N >> 4;
     for (int sf = 0; sf < 10; sf++)
       for (int l = 0; l < 14; l++)
         if (!oai4g_mod_nre_fits(cfg->h.symnre[sf][l], (uint32_t)N)) { set_err("too many data REs per symbol for the modulator"); return -1; }
@@ -1434,15 +1443,13 @@ static int upload_remap(oai4g_tx_config *cfg)
           }
           both[n + sl * N + t * 16 + k] = code < OAI4G_CTL_CODE ? code : sentinel;
         }
-    HCK(hipMalloc(&cfg->d_remap, both.size() * 2), -1);
-    HCK(hipMemcpy(cfg->d_remap, both.data(), both.size() * 2, hipMemcpyHostToDevice), -1);
-    cfg->h.remap_tm = cfg->d_remap + n;
+    HCK(cfg->d_remap.upload(both), -1);
   } else {
-    cfg->h.remap_tm = nullptr;
+    cfg->d_remap.reset();
   }
-  if (build_stat_tm(cfg) != 0) return -1;
-  cfg->h.remap = cfg->d_remap;
-  return 0;
+  cfg->h.remap = cfg->d_remap.get();
+  cfg->h.remap_tm = n ? cfg->d_remap.get() + n : nullptr;
+  return build_stat_tm(cfg);
 }
 
 /* the scrambling words of every (subframe index, codeword): lte_gold_generic (lte_gold.c:151-177)
@@ -1458,11 +1465,8 @@ static int upload_gold(oai4g_tx_config *cfg)
       const size_t nw = std::min(stride, (size_t)(h.cw[cw].G[sf] + 31) / 32);
       gold_seq_h(c_init, g.data() + ((size_t)sf * h.n_cw + cw) * stride, nw);
     }
-  if (cfg->d_gold) hipFree(cfg->d_gold);
-  cfg->d_gold = nullptr;
-  HCK(hipMalloc(&cfg->d_gold, g.size() * 4), -1);
-  HCK(hipMemcpy(cfg->d_gold, g.data(), g.size() * 4, hipMemcpyHostToDevice), -1);
-  cfg->h.gold_tab = cfg->d_gold;
+  HCK(cfg->d_gold.upload(g), -1);
+  cfg->h.gold_tab = cfg->d_gold.get();
   return 0;
 }
 
@@ -1477,38 +1481,17 @@ static int upload_cfg(oai4g_tx_config *cfg)
   cfg->h.gold_x1 = g_gx1;
   cfg->h.gold_x2j = g_gx2j;
   cfg->h.tw = g_tw;
-  HCK(hipMalloc(&cfg->d, sizeof(cfg_dev_t)), -1);
-  HCK(hipMemcpy(cfg->d, &cfg->h, sizeof(cfg_dev_t), hipMemcpyHostToDevice), -1);
+  HCK(cfg->d.upload(&cfg->h, 1), -1);
   return 0;
 }
 
-static void release_cfg(oai4g_tx_config *cfg)
-{
-  for (auto &e : cfg->ev_enc)
-    if (e) hipEventDestroy(e);
-  if (cfg->ev_done) hipEventDestroy(cfg->ev_done);
-  if (cfg->s_mod) hipStreamDestroy(cfg->s_mod);
-  cfg->s_mod = nullptr;
-  cfg->ev_done = nullptr;
-  if (cfg->d) hipFree(cfg->d);
-  if (cfg->d_remap) hipFree(cfg->d_remap);
-  if (cfg->d_stat) hipFree(cfg->d_stat);
-  if (cfg->d_gold) hipFree(cfg->d_gold);
-  if (cfg->d_rvtab) hipFree(cfg->d_rvtab);
-  cfg->d_rvtab = nullptr;
-  cfg->d_stat = nullptr;
-  cfg->d_gold = nullptr;
-  cfg->d = nullptr;
-  cfg->d_remap = nullptr;
-}
-
-/* releases a drop-in's stack configuration on every path out of it.  Unless the caller has already
- * synchronised (done), it waits for the scratch stream first: a launched kernel may still read it. */
+/* declared after a drop-in's stack configuration, so that it goes first on every path out: unless the
+ * caller has already synchronised (done), it waits for the scratch stream before the configuration's
+ * device memory is freed: a launched kernel may still read it. */
 namespace {
 struct cfg_scope_t {
-  oai4g_tx_config *cfg;
   bool done = false;
-  ~cfg_scope_t() { if (!done && g_scr.s) hipStreamSynchronize(g_scr.s); release_cfg(cfg); }
+  ~cfg_scope_t() { if (!done && g_scr.s) hipStreamSynchronize(g_scr.s); }
 };
 }  // namespace
 
@@ -1523,31 +1506,24 @@ extern "C" oai4g_tx_config_t *oai4g_tx_config_create(const oai4g_tx_params_t *p)
     set_err("single-layer precoding (mimo_mode %u) requires one codeword, 2 TX antennas and mode1_flag 0", p->mimo_mode);
     return nullptr;
   }
-  oai4g_tx_config *cfg = new oai4g_tx_config();
+  std::unique_ptr<oai4g_tx_config> cfg(new oai4g_tx_config());
   uint8_t Nl[2] = {1, 1};
-  if (derive_cfg(cfg, p, Nl, true, -1) != 0 || upload_cfg(cfg) != 0) {   /* RM condition (-2) is an error here */
-    release_cfg(cfg);
-    delete cfg;
-    return nullptr;
-  }
+  /* RM condition (-2) is an error here */
+  if (derive_cfg(cfg.get(), p, Nl, true, -1) != 0 || upload_cfg(cfg.get()) != 0) return nullptr;
   bool ok = hipStreamCreateWithFlags(&cfg->s_mod, hipStreamNonBlocking) == hipSuccess &&
             hipEventCreateWithFlags(&cfg->ev_done, hipEventDisableTiming) == hipSuccess;
   for (auto &e : cfg->ev_enc) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
   if (!ok) {
     set_err("stream/event creation failed");
-    release_cfg(cfg);
-    delete cfg;
     return nullptr;
   }
   if (const char *pc = getenv("OAI4G_PIPE_CHUNK")) cfg->pipe_chunk = atoi(pc);
-  return cfg;
+  return cfg.release();
 }
 
 extern "C" void oai4g_tx_config_destroy(oai4g_tx_config_t *cfg)
 {
-  if (!cfg) return;
-  release_cfg(cfg);
-  delete cfg;
+  if (cfg) delete cfg;
 }
 
 extern "C" uint32_t oai4g_tx_G(const oai4g_tx_config_t *cfg, int cw, int subframe)
@@ -1565,7 +1541,7 @@ extern "C" int oai4g_tx_encode(const oai4g_tx_config_t *cfg, int n_sf, const uin
                                void *stream)
 {
   NEED_INIT(-1);
-  HCK(oai4g_launch_encode(cfg->d, &cfg->h, 0, n_sf, d_payload, (uint32_t *)d_work, (hipStream_t)stream), -1);
+  HCK(oai4g_launch_encode(cfg->d.get(), &cfg->h, 0, n_sf, d_payload, (uint32_t *)d_work, (hipStream_t)stream), -1);
   return 0;
 }
 
@@ -1621,14 +1597,10 @@ extern "C" int oai4g_tx_config_enable_tb_rv(oai4g_tx_config_t *cfg)
       memcpy(t.rm_wrapt, c->rm_wrapt, sizeof(t.rm_wrapt));
       memcpy(t.k0ck, c->k0ck, sizeof(t.k0ck));
     }
-  enc_rv_tab_t *d = nullptr;
-  HCK(hipMalloc(&d, tabs.size() * sizeof(enc_rv_tab_t)), -1);
-  if (hipMemcpy(d, tabs.data(), tabs.size() * sizeof(enc_rv_tab_t), hipMemcpyHostToDevice) != hipSuccess) {
-    hipFree(d);
+  if (cfg->d_rvtab.upload(tabs) != hipSuccess) {
     set_err("tx_config_enable_tb_rv: upload failed");
     return -1;
   }
-  cfg->d_rvtab = d;
   return 0;
 }
 
@@ -1646,7 +1618,7 @@ extern "C" int oai4g_tx_encode_rv(const oai4g_tx_config_t *cfg, int n_sf, const 
 {
   NEED_INIT(-1);
   if (!tb_rv_ready(cfg, d_rv, "tx_encode_rv")) return -1;
-  HCK(oai4g_launch_encode_rv(cfg->d, &cfg->h, n_sf, d_payload, d_rv, cfg->d_rvtab, (uint32_t *)d_work,
+  HCK(oai4g_launch_encode_rv(cfg->d.get(), &cfg->h, n_sf, d_payload, d_rv, cfg->d_rvtab.get(), (uint32_t *)d_work,
                              (hipStream_t)stream), -1);
   return 0;
 }
@@ -1659,8 +1631,8 @@ extern "C" int oai4g_tx_batch_rv(const oai4g_tx_config_t *cfg, int n_sf, const u
   if (n_sf <= 0) return 0;
   if (!iq_aligned(d_iq)) return -1;
   hipStream_t s = (hipStream_t)stream;
-  HCK(oai4g_launch_encode_rv(cfg->d, &cfg->h, n_sf, d_payload, d_rv, cfg->d_rvtab, (uint32_t *)d_work, s), -1);
-  HCK(oai4g_launch_modofdm(cfg->d, &cfg->h, 0, n_sf, (const uint32_t *)d_work, d_iq, s), -1);
+  HCK(oai4g_launch_encode_rv(cfg->d.get(), &cfg->h, n_sf, d_payload, d_rv, cfg->d_rvtab.get(), (uint32_t *)d_work, s), -1);
+  HCK(oai4g_launch_modofdm(cfg->d.get(), &cfg->h, 0, n_sf, (const uint32_t *)d_work, d_iq, s), -1);
   return 0;
 }
 
@@ -1684,8 +1656,8 @@ extern "C" int oai4g_tx_batch(const oai4g_tx_config_t *cfg, int n_sf, const uint
   uint32_t *ew = (uint32_t *)d_work;
   int chunk = cfg->pipe_chunk;
   if (chunk <= 0 || n_sf < 2 * chunk) {
-    HCK(oai4g_launch_encode(cfg->d, &cfg->h, 0, n_sf, d_payload, ew, s), -1);
-    HCK(oai4g_launch_modofdm(cfg->d, &cfg->h, 0, n_sf, ew, d_iq, s), -1);
+    HCK(oai4g_launch_encode(cfg->d.get(), &cfg->h, 0, n_sf, d_payload, ew, s), -1);
+    HCK(oai4g_launch_modofdm(cfg->d.get(), &cfg->h, 0, n_sf, ew, d_iq, s), -1);
     return 0;
   }
   int nch = (n_sf + chunk - 1) / chunk;
@@ -1698,10 +1670,10 @@ extern "C" int oai4g_tx_batch(const oai4g_tx_config_t *cfg, int n_sf, const uint
   HCK(hipStreamWaitEvent(cfg->s_mod, cfg->ev_done, 0), -1);
   for (int i = 0; i < nch; i++) {
     const int sf0 = i * chunk, n = n_sf - sf0 < chunk ? n_sf - sf0 : chunk;
-    HCK(oai4g_launch_encode(cfg->d, &cfg->h, sf0, n, d_payload, ew, s), -1);
+    HCK(oai4g_launch_encode(cfg->d.get(), &cfg->h, sf0, n, d_payload, ew, s), -1);
     HCK(hipEventRecord(cfg->ev_enc[i], s), -1);
     HCK(hipStreamWaitEvent(cfg->s_mod, cfg->ev_enc[i], 0), -1);
-    HCK(oai4g_launch_modofdm(cfg->d, &cfg->h, sf0, n, ew, d_iq, cfg->s_mod), -1);
+    HCK(oai4g_launch_modofdm(cfg->d.get(), &cfg->h, sf0, n, ew, d_iq, cfg->s_mod), -1);
   }
   HCK(hipEventRecord(cfg->ev_done, cfg->s_mod), -1);
   HCK(hipStreamWaitEvent(s, cfg->ev_done, 0), -1);
@@ -1717,9 +1689,9 @@ extern "C" int oai4g_tx_batch_timed(const oai4g_tx_config_t *cfg, int n_sf, cons
   hipEvent_t ev[3];
   for (int i = 0; i < 3; i++) HCK(hipEventCreate(&ev[i]), -1);
   HCK(hipEventRecord(ev[0], s), -1);
-  HCK(oai4g_launch_encode(cfg->d, &cfg->h, 0, n_sf, d_payload, (uint32_t *)d_work, s), -1);
+  HCK(oai4g_launch_encode(cfg->d.get(), &cfg->h, 0, n_sf, d_payload, (uint32_t *)d_work, s), -1);
   HCK(hipEventRecord(ev[1], s), -1);
-  HCK(oai4g_launch_modofdm(cfg->d, &cfg->h, 0, n_sf, (const uint32_t *)d_work, d_iq, s), -1);
+  HCK(oai4g_launch_modofdm(cfg->d.get(), &cfg->h, 0, n_sf, (const uint32_t *)d_work, d_iq, s), -1);
   HCK(hipEventRecord(ev[2], s), -1);
   HCK(hipEventSynchronize(ev[2]), -1);
   HCK(hipEventElapsedTime(&kernel_ms[0], ev[0], ev[1]), -1);
@@ -1733,7 +1705,7 @@ extern "C" int oai4g_tx_modulate(const oai4g_tx_config_t *cfg, int n_sf, const v
 {
   NEED_INIT(-1);
   if (!cfg || !iq_aligned(d_iq)) return -1;
-  HCK(oai4g_launch_modofdm(cfg->d, &cfg->h, 0, n_sf, (const uint32_t *)d_work, d_iq, (hipStream_t)stream), -1);
+  HCK(oai4g_launch_modofdm(cfg->d.get(), &cfg->h, 0, n_sf, (const uint32_t *)d_work, d_iq, (hipStream_t)stream), -1);
   return 0;
 }
 
@@ -1749,10 +1721,10 @@ extern "C" int oai4g_diag_encode_phase_ms(const oai4g_tx_config_t *cfg, int n_sf
   hipEvent_t a, b;
   HCK(hipEventCreate(&a), -1);
   HCK(hipEventCreate(&b), -1);
-  HCK(oai4g_launch_encode_phase(cfg->d, &cfg->h, n_sf, d_payload, (uint32_t *)d_work, stop_phase, nullptr), -1);
+  HCK(oai4g_launch_encode_phase(cfg->d.get(), &cfg->h, n_sf, d_payload, (uint32_t *)d_work, stop_phase, nullptr), -1);
   HCK(hipEventRecord(a, nullptr), -1);
   for (int i = 0; i < reps; i++)
-    HCK(oai4g_launch_encode_phase(cfg->d, &cfg->h, n_sf, d_payload, (uint32_t *)d_work, stop_phase, nullptr), -1);
+    HCK(oai4g_launch_encode_phase(cfg->d.get(), &cfg->h, n_sf, d_payload, (uint32_t *)d_work, stop_phase, nullptr), -1);
   HCK(hipEventRecord(b, nullptr), -1);
   HCK(hipEventSynchronize(b), -1);
   HCK(hipEventElapsedTime(ms, a, b), -1);
@@ -2181,7 +2153,7 @@ extern "C" int oai4g_dlsch_encoding(uint8_t *a, const oai4g_frame_parms_t *frame
   int rc = derive_cfg(&cfg, &p, Nl, false, -1);
   bool rm_fail = rc == -2; /* reference: every block's rate matcher returns E = 0, e untouched */
   if (rc != 0 && !rm_fail) return -1;
-  cfg_scope_t scope = {&cfg};
+  cfg_scope_t scope;
   if (upload_cfg(&cfg) != 0) return -1;
   cw_dev_t &c = cfg.h.cw[0];
   uint32_t G = c.G[subframe % 10];
@@ -2194,7 +2166,7 @@ extern "C" int oai4g_dlsch_encoding(uint8_t *a, const oai4g_frame_parms_t *frame
   if (!st.open()) return -1;
   HCK(st.up(r_pay, a, c.A_bytes), -1);
   enc_debug_t dbg = {st.ptr(r_c), st.ptr(r_d), st.ptr(r_w), rm_fail ? nullptr : st.ptr(r_e), st.ptr(r_b)};
-  HCK(oai4g_launch_encode_debug(cfg.d, &cfg.h, 0, subframe % 10, st.ptr(r_pay), dbg, g_scr.s), -1);
+  HCK(oai4g_launch_encode_debug(cfg.d.get(), &cfg.h, 0, subframe % 10, st.ptr(r_pay), dbg, g_scr.s), -1);
   std::vector<uint8_t> hb(off_e + G);
   HCK(st.down(hb.data(), r_pay, off_e + G, 0, r_e), -1);
   HCK(st.sync(), -1);
@@ -2263,7 +2235,7 @@ extern "C" int oai4g_dlsch_modulation(int32_t **txdataF, int16_t amp, uint32_t s
   }
   int rc = derive_cfg(&cfg, &p, Nl, true, (int)(subframe_offset % 10));
   if (rc != 0 && rc != -2) return -1;
-  cfg_scope_t scope = {&cfg};
+  cfg_scope_t scope;
   if (upload_cfg(&cfg) != 0) return -1;
   int sf = (int)(subframe_offset % 10);
   uint32_t N = cfg.h.N, nsymb = cfg.h.nsymb, nant = cfg.h.n_ant;
@@ -2279,7 +2251,7 @@ extern "C" int oai4g_dlsch_modulation(int32_t **txdataF, int16_t amp, uint32_t s
   for (uint32_t aa = 0; aa < nant; aa++) HCK(st.up(r_grid, txdataF[aa] + sym_off, ant_bytes, aa * ant_bytes), -1);
   HCK(st.up(r_e0, h0->e, e0_bytes), -1);
   if (p.n_cw > 1) HCK(st.up(r_e1, dlsch1->harq_processes[dlsch0->current_harq_pid]->e, e1_bytes), -1);
-  HCK(oai4g_launch_modulate_bytes(cfg.d, &cfg.h, sf, st.ptr(r_e0), p.n_cw > 1 ? st.ptr(r_e1) : nullptr,
+  HCK(oai4g_launch_modulate_bytes(cfg.d.get(), &cfg.h, sf, st.ptr(r_e0), p.n_cw > 1 ? st.ptr(r_e1) : nullptr,
                                   st.ptr<int32_t>(r_grid), g_scr.s), -1);
   for (uint32_t aa = 0; aa < nant; aa++) HCK(st.down(txdataF[aa] + sym_off, r_grid, ant_bytes, aa * ant_bytes), -1);
   HCK(st.sync(), -1);
@@ -2451,49 +2423,21 @@ extern "C" int oai4g_lte_dl_cell_spec(int32_t *output, int16_t amp, const oai4g_
 /* ------------------------------------------------------------------------------------------
  * Uplink turbo decoding (3gpplte_turbo_decoder_sse_16bit.c, lte_rate_matching.c)
  * ---------------------------------------------------------------------------------------- */
-/* init_td16 (:898-943) for block size K: pi4 | pi5 | pi6 as uint16, uploaded once per K */
-static const uint16_t *td_tables(uint32_t K)
+/* init_td16 (:898-943; 8 windows) and init_td8 (3gpplte_turbo_decoder_sse_8bit.c:846-892; 16 windows,
+ * K % 16 == 0) for block size K: pi4 | pi5 | pi6 as uint16.  Window w holds the K / windows positions
+ * w, w + windows, …; uploaded once per (K, windows) and kept as long as the process. */
+static const uint16_t *td_tables(uint32_t K, uint32_t windows = 8)
 {
   static std::mutex mu;
-  static std::map<uint32_t, uint16_t *> cache;
+  static std::map<std::pair<uint32_t, uint32_t>, uint16_t *> cache;
   std::lock_guard<std::mutex> lk(mu);
-  auto it = cache.find(K);
+  auto it = cache.find({K, windows});
   if (it != cache.end()) return it->second;
   const int qi = oai4g_qpp_index(K);
-  if (qi < 0) return nullptr;
+  if (qi < 0 || K % windows) return nullptr;
   const uint64_t f1 = oai4g_qpp_table[qi].f1, f2 = oai4g_qpp_table[qi].f2;
   std::vector<uint32_t> pi2(K);
-  for (uint32_t i = 0, i2 = 0; i2 < 8; i2++)
-    for (uint32_t i3 = 0, j = i2; i3 < K / 8; i3++, i++, j += 8) pi2[i] = j;
-  std::vector<uint16_t> t(3 * (size_t)K);
-  for (uint32_t i = 0; i < K; i++) {
-    const uint32_t pi = (uint32_t)((f1 * i + f2 * (uint64_t)i * i) % K), pi3 = pi2[pi];
-    t[pi2[i]] = (uint16_t)pi3;          /* pi4 */
-    t[K + pi3] = (uint16_t)pi2[i];      /* pi5 */
-    t[2 * K + pi] = (uint16_t)pi2[i];   /* pi6 */
-  }
-  uint16_t *d = nullptr;
-  if (hipMalloc(&d, t.size() * 2) != hipSuccess || hipMemcpy(d, t.data(), t.size() * 2, hipMemcpyHostToDevice) != hipSuccess) {
-    set_err("decoder table upload failed");
-    return nullptr;
-  }
-  cache[K] = d;
-  return d;
-}
-
-/* init_td8 (3gpplte_turbo_decoder_sse_8bit.c:846-892) for K % 16 == 0: 16 windows */
-static const uint16_t *td8_tables(uint32_t K)
-{
-  static std::mutex mu;
-  static std::map<uint32_t, uint16_t *> cache;
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = cache.find(K);
-  if (it != cache.end()) return it->second;
-  const int qi = oai4g_qpp_index(K);
-  if (qi < 0 || (K & 15)) return nullptr;
-  const uint64_t f1 = oai4g_qpp_table[qi].f1, f2 = oai4g_qpp_table[qi].f2;
-  std::vector<uint32_t> pi2(K);
-  for (uint32_t i = 0, j = 0; i < K; i++, j += 16) {
+  for (uint32_t i = 0, j = 0; i < K; i++, j += windows) {
     if (j >= K) j -= (K - 1);
     pi2[i] = j;
   }
@@ -2504,14 +2448,14 @@ static const uint16_t *td8_tables(uint32_t K)
     t[K + pi3] = (uint16_t)pi2[i];      /* pi5 */
     t[2 * K + pi] = (uint16_t)pi2[i];   /* pi6 */
   }
-  uint16_t *d = nullptr;
-  if (hipMalloc(&d, t.size() * 2) != hipSuccess || hipMemcpy(d, t.data(), t.size() * 2, hipMemcpyHostToDevice) != hipSuccess) {
-    set_err("decoder8 table upload failed");
+  dev_buf<uint16_t> d;
+  if (d.upload(t) != hipSuccess) {
+    set_err("decoder table upload failed");
     return nullptr;
   }
-  cache[K] = d;
-  return d;
+  return cache[{K, windows}] = d.release();
 }
+static const uint16_t *td8_tables(uint32_t K) { return td_tables(K, 16); }
 
 extern "C" size_t oai4g_td8_scratch_bytes(uint16_t K, int n_cb) { return (size_t)((n_cb + 3) / 4) * oai4g_td8_wave_bytes(K); }
 
@@ -2616,37 +2560,31 @@ extern "C" uint32_t oai4g_generate_dummy_w(uint32_t D, uint8_t *w, uint8_t F)
  * ---------------------------------------------------------------------------------------- */
 struct oai4g_ul_config {
   ul_dev_t h;
-  ul_dev_t *d = nullptr;
+  dev_buf<ul_dev_t> d;
   uint32_t B, G, C, Cminus, Kminus, Kplus, F, max_it;
-  std::vector<void *> dev;
+  dev_buf<uint8_t> d_dummy[3];    /* ul_pat_t::dummy / cidx of each pattern */
+  dev_buf<uint32_t> d_cidx[3];
   size_t d_stride = 0;
-  int cap = 0;
-  int16_t *d_dfull = nullptr;
-  uint8_t *d_td = nullptr;
+  dev_buf<int16_t> d_dfull;       /* the work buffers, sized by the largest batch so far (ul_reserve) */
+  dev_buf<uint8_t> d_td;
   int bits = 16;                  /* 16: phy_threegpplte_turbo_decoder16; 8: the 8-bit decoder (llr8_flag) */
 };
 
 extern "C" void oai4g_ul_config_destroy(oai4g_ul_config_t *cfg)
 {
-  if (!cfg) return;
-  for (void *p : cfg->dev) hipFree(p);
-  if (cfg->d_dfull) hipFree(cfg->d_dfull);
-  if (cfg->d_td) hipFree(cfg->d_td);
-  if (cfg->d) hipFree(cfg->d);
-  delete cfg;
+  if (cfg) delete cfg;
 }
 
 extern "C" oai4g_ul_config_t *oai4g_ul_config_create(uint32_t B, uint32_t G, uint8_t Qm, uint8_t rvidx, uint8_t Mdlharq,
                                                      uint32_t Nsoft, uint8_t max_iterations)
 {
   NEED_INIT(nullptr);
-  auto *cfg = new oai4g_ul_config();
+  std::unique_ptr<oai4g_ul_config> cfg(new oai4g_ul_config());
   uint32_t Cplus, L;
   if (Qm == 0 || Mdlharq == 0 || rvidx > 3 ||
       seg_params(B, &cfg->C, &Cplus, &cfg->Cminus, &cfg->Kplus, &cfg->Kminus, &cfg->F, &L) < 0 ||
       cfg->C > OAI4G_UL_MAX_C || (cfg->F & 7) || cfg->F + 24 > cfg->Kplus) {
     set_err("ul_config: unsupported (B %u, Qm %u, rv %u, Mdlharq %u)", B, Qm, rvidx, Mdlharq);
-    delete cfg;
     return nullptr;
   }
   cfg->B = B;
@@ -2667,6 +2605,8 @@ extern "C" oai4g_ul_config_t *oai4g_ul_config_create(uint32_t B, uint32_t G, uin
     if (pi == npat) {
       keyK[npat] = K;
       keyF[npat] = Fr;
+      dev_buf<uint8_t> &dd = cfg->d_dummy[npat];
+      dev_buf<uint32_t> &dc = cfg->d_cidx[npat];
       ul_pat_t &P = h.pat[npat++];
       std::vector<uint8_t> dw;
       P.D = K + 4;
@@ -2692,33 +2632,22 @@ extern "C" oai4g_ul_config_t *oai4g_ul_config_create(uint32_t B, uint32_t G, uin
         P.k0cr[rv] = k0r >= P.Ncb ? 0 : c;
       }
       if (P.R > h.Rmax) h.Rmax = P.R;
-      uint8_t *dd = nullptr;
-      uint32_t *dc = nullptr;
-      if (hipMalloc(&dd, dw.size()) != hipSuccess || hipMalloc(&dc, cidx.size() * 4) != hipSuccess ||
-          hipMemcpy(dd, dw.data(), dw.size(), hipMemcpyHostToDevice) != hipSuccess ||
-          hipMemcpy(dc, cidx.data(), cidx.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-        if (dd) cfg->dev.push_back(dd);
-        if (dc) cfg->dev.push_back(dc);
+      if (dd.upload(dw) != hipSuccess || dc.upload(cidx) != hipSuccess) {
         set_err("ul_config: device allocation failed");
-        oai4g_ul_config_destroy(cfg);
         return nullptr;
       }
-      cfg->dev.push_back(dd);
-      cfg->dev.push_back(dc);
-      P.dummy = dd;
-      P.cidx = dc;
+      P.dummy = dd.get();
+      P.cidx = dc.get();
     }
     h.pat_of[r] = pi;
   }
-  if (!td_tables(cfg->Kplus) || (cfg->Cminus && !td_tables(cfg->Kminus))) { oai4g_ul_config_destroy(cfg); return nullptr; }
+  if (!td_tables(cfg->Kplus) || (cfg->Cminus && !td_tables(cfg->Kminus))) return nullptr;
   cfg->d_stride = (96 + 3 * (size_t)cfg->Kplus + 12 + 15) & ~(size_t)15;
-  if (hipMalloc(&cfg->d, sizeof(ul_dev_t)) != hipSuccess ||
-      hipMemcpy(cfg->d, &h, sizeof(ul_dev_t), hipMemcpyHostToDevice) != hipSuccess) {
+  if (cfg->d.upload(&h, 1) != hipSuccess) {
     set_err("ul_config: upload failed");
-    oai4g_ul_config_destroy(cfg);
     return nullptr;
   }
-  return cfg;
+  return cfg.release();
 }
 
 extern "C" int oai4g_ul_config_set_decoder(oai4g_ul_config_t *cfg, int bits)
@@ -2730,11 +2659,8 @@ extern "C" int oai4g_ul_config_set_decoder(oai4g_ul_config_t *cfg, int bits)
     return -1;
   }
   if (bits != cfg->bits) {          /* the scratch size differs: reallocate on the next batch */
-    if (cfg->d_dfull) hipFree(cfg->d_dfull);
-    if (cfg->d_td) hipFree(cfg->d_td);
-    cfg->d_dfull = nullptr;
-    cfg->d_td = nullptr;
-    cfg->cap = 0;
+    cfg->d_dfull.reset();
+    cfg->d_td.reset();
   }
   cfg->bits = bits;
   return 0;
@@ -2746,20 +2672,15 @@ extern "C" uint32_t oai4g_ul_config_E(const oai4g_ul_config_t *cfg, int r) { ret
 
 static int ul_reserve(oai4g_ul_config_t *cfg, int n_tb)
 {
-  if (n_tb <= cfg->cap) return 0;
-  if (cfg->d_dfull) hipFree(cfg->d_dfull);
-  if (cfg->d_td) hipFree(cfg->d_td);
-  cfg->d_dfull = nullptr;
-  cfg->d_td = nullptr;
   const size_t nb = (size_t)n_tb * cfg->C;
   const size_t td = cfg->bits == 8 ? oai4g_td8_scratch_bytes((uint16_t)cfg->Kplus, (int)nb)
                                    : oai4g_td_scratch_bytes((uint16_t)cfg->Kplus, (int)nb);
-  if (hipMalloc(&cfg->d_dfull, nb * cfg->d_stride * 2) != hipSuccess || hipMalloc(&cfg->d_td, td) != hipSuccess) {
+  /* the two grow together: free both before either is allocated anew */
+  if (nb * cfg->d_stride > cfg->d_dfull.count()) cfg->d_td.reset();
+  if (cfg->d_dfull.reserve(nb * cfg->d_stride) != hipSuccess || cfg->d_td.reserve(td) != hipSuccess) {
     set_err("ul_decode_batch: device allocation failed");
-    cfg->cap = 0;
     return -1;
   }
-  cfg->cap = n_tb;
   return 0;
 }
 
@@ -2768,20 +2689,20 @@ static int ul_decode_rows(oai4g_ul_config_t *cfg, int n_tb, uint8_t *d_c, size_t
                           hipStream_t s)
 {
   const uint32_t crc = cfg->C == 1 ? OAI4G_CRC24_A : OAI4G_CRC24_B, F = cfg->C == 1 ? cfg->F : 0;
-  const int16_t *y = cfg->d_dfull + 96;
+  const int16_t *y = cfg->d_dfull.get() + 96;
   if (cfg->bits == 8) {
     /* every block of one size (set_decoder checked), rows (tb, r) in the d_c / d_iters order */
     const uint16_t *pi = td8_tables(cfg->Kplus);
     if (!pi) return -1;
     HCK(oai4g_launch_td8(n_tb * (int)cfg->C, cfg->Kplus, y, cfg->d_stride, d_c, c_stride, d_iters, cfg->max_it, crc, F,
-                         pi, cfg->d_td, s), -1);
+                         pi, cfg->d_td.get(), s), -1);
     return 0;
   }
   if (cfg->Cminus)
     HCK(oai4g_launch_td16(n_tb * (int)cfg->Cminus, cfg->Kminus, y, cfg->d_stride, d_c, c_stride, d_iters, cfg->max_it,
-                          crc, F, td_tables(cfg->Kminus), cfg->d_td, s, cfg->Cminus, cfg->C, 0), -1);
+                          crc, F, td_tables(cfg->Kminus), cfg->d_td.get(), s, cfg->Cminus, cfg->C, 0), -1);
   HCK(oai4g_launch_td16(n_tb * (int)(cfg->C - cfg->Cminus), cfg->Kplus, y, cfg->d_stride, d_c, c_stride, d_iters,
-                        cfg->max_it, crc, F, td_tables(cfg->Kplus), cfg->d_td, s, cfg->C - cfg->Cminus, cfg->C,
+                        cfg->max_it, crc, F, td_tables(cfg->Kplus), cfg->d_td.get(), s, cfg->C - cfg->Cminus, cfg->C,
                         cfg->Cminus), -1);
   return 0;
 }
@@ -2794,7 +2715,7 @@ extern "C" int oai4g_ul_decode_batch(oai4g_ul_config_t *cfg, int n_tb, const int
   if (c_stride < cfg->Kplus / 8 || e_stride < cfg->G) { set_err("ul_decode_batch: strides too small"); return -1; }
   if (ul_reserve(cfg, n_tb) != 0) return -1;
   hipStream_t s = (hipStream_t)stream;
-  HCK(oai4g_launch_ul_rm_deint(cfg->d, &cfg->h, n_tb, d_e, e_stride, cfg->d_dfull, cfg->d_stride, s), -1);
+  HCK(oai4g_launch_ul_rm_deint(cfg->d.get(), &cfg->h, n_tb, d_e, e_stride, cfg->d_dfull.get(), cfg->d_stride, s), -1);
   return ul_decode_rows(cfg, n_tb, d_c, c_stride, d_iters, s);
 }
 
@@ -2815,7 +2736,7 @@ extern "C" int oai4g_ul_decode_batch_harq(oai4g_ul_config_t *cfg, int n_tb, cons
   }
   if (ul_reserve(cfg, n_tb) != 0) return -1;
   hipStream_t s = (hipStream_t)stream;
-  HCK(oai4g_launch_ul_rm_harq(cfg->d, &cfg->h, n_tb, d_e, e_stride, d_w, w_stride, rvidx, clear, cfg->d_dfull,
+  HCK(oai4g_launch_ul_rm_harq(cfg->d.get(), &cfg->h, n_tb, d_e, e_stride, d_w, w_stride, rvidx, clear, cfg->d_dfull.get(),
                               cfg->d_stride, s), -1);
   return ul_decode_rows(cfg, n_tb, d_c, c_stride, d_iters, s);
 }
@@ -2834,7 +2755,7 @@ extern "C" int oai4g_ul_decode_batch_harq_tb(oai4g_ul_config_t *cfg, int n_tb, c
   }
   if (ul_reserve(cfg, n_tb) != 0) return -1;
   hipStream_t s = (hipStream_t)stream;
-  HCK(oai4g_launch_ul_rm_harq_tb(cfg->d, &cfg->h, n_tb, d_e, e_stride, d_w, w_stride, d_rv, d_clear, cfg->d_dfull,
+  HCK(oai4g_launch_ul_rm_harq_tb(cfg->d.get(), &cfg->h, n_tb, d_e, e_stride, d_w, w_stride, d_rv, d_clear, cfg->d_dfull.get(),
                                  cfg->d_stride, s), -1);
   return ul_decode_rows(cfg, n_tb, d_c, c_stride, d_iters, s);
 }
@@ -3547,7 +3468,7 @@ static int rebuild_static(oai4g_tx_config_t *cfg)
   cfg->h.mod_nosat = mod_nosat_ok(cfg->h, std::max(packed_iq_max(cfg->h_crs), cfg->ctl_vmax));
   mod_items_setup(cfg->h);
   if (upload_remap(cfg) != 0) return -1;
-  HCK(hipMemcpy(cfg->d, &cfg->h, sizeof(cfg_dev_t), hipMemcpyHostToDevice), -1);
+  HCK(hipMemcpy(cfg->d.get(), &cfg->h, sizeof(cfg_dev_t), hipMemcpyHostToDevice), -1);
   return 0;
 }
 
@@ -3806,10 +3727,9 @@ struct oai4g_rx_config {
   oai4g_frame_parms_t fp;
   rx_mode_t mode;
   rx_dev_t h;
-  rx_dev_t *d = nullptr;
-  uint32_t *d_map = nullptr, *d_gold = nullptr;
-  uint8_t *d_shift = nullptr;
-  int shift_cap = 0;
+  dev_buf<rx_dev_t> d;
+  dev_buf<uint32_t> d_map, d_gold;
+  dev_buf<uint8_t> d_shift;       /* one entry per subframe of the largest batch so far (rx_prepare) */
   uint32_t llr_count[10];
   bool bad[10];                   /* subframe index whose LLR stream would read unwritten ext slots */
 };
@@ -4115,7 +4035,7 @@ static oai4g_rx_config_t *rx_config_build(const oai4g_frame_parms_t *fp, const u
     set_err("rx_config: the first PDSCH symbol carries pilots (dlsch_channel_level would read past the extracted REs)");
     return nullptr;
   }
-  auto *cfg = new oai4g_rx_config();
+  std::unique_ptr<oai4g_rx_config> cfg(new oai4g_rx_config());
   cfg->fp = *fp;
   cfg->mode = mode;
   rx_dev_t &h = cfg->h;
@@ -4191,7 +4111,7 @@ static oai4g_rx_config_t *rx_config_build(const oai4g_frame_parms_t *fp, const u
         cfg->bad[sf] = true;
         h.len[sf][k] = h.len[sf][k] < n ? h.len[sf][k] : n;
       }
-      if (h.len[sf][k] > 1280) { set_err("rx_config: > 1280 REs in a symbol (k_rx_llr covers 256 x 5)"); delete cfg; return nullptr; }
+      if (h.len[sf][k] > 1280) { set_err("rx_config: > 1280 REs in a symbol (k_rx_llr covers 256 x 5)"); return nullptr; }
       h.llr_off[sf][k] = off;
       off += h.len[sf][k] * Qm;
       if (k == 0) {
@@ -4210,22 +4130,17 @@ static oai4g_rx_config_t *rx_config_build(const oai4g_frame_parms_t *fp, const u
   std::vector<uint32_t> gold((size_t)10 * h.gold_words);
   for (uint32_t sf = 0; sf < 10; sf++)
     gold_seq_h(((uint32_t)rnti << 14) + (sf << 9) + fp->Nid_cell, gold.data() + (size_t)sf * h.gold_words, h.gold_words);
-  if (hipMalloc(&cfg->d_map, map.size() * 4) != hipSuccess || hipMalloc(&cfg->d_gold, gold.size() * 4) != hipSuccess ||
-      hipMalloc(&cfg->d, sizeof(rx_dev_t)) != hipSuccess) {
-    set_err("rx_config: device allocation failed");
-    oai4g_rx_config_destroy(cfg);
+  if (cfg->d_map.upload(map) != hipSuccess || cfg->d_gold.upload(gold) != hipSuccess) {
+    set_err("rx_config: table upload failed");
     return nullptr;
   }
-  h.map = cfg->d_map;
-  h.gold = cfg->d_gold;
-  if (hipMemcpy(cfg->d_map, map.data(), map.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(cfg->d_gold, gold.data(), gold.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(cfg->d, &h, sizeof(rx_dev_t), hipMemcpyHostToDevice) != hipSuccess) {
+  h.map = cfg->d_map.get();
+  h.gold = cfg->d_gold.get();
+  if (cfg->d.upload(&h, 1) != hipSuccess) {
     set_err("rx_config: upload failed");
-    oai4g_rx_config_destroy(cfg);
     return nullptr;
   }
-  return cfg;
+  return cfg.release();
 }
 
 extern "C" oai4g_rx_config_t *oai4g_rx_config_create(const oai4g_frame_parms_t *fp, const uint32_t rb_alloc[4], uint8_t Qm,
@@ -4269,12 +4184,7 @@ extern "C" oai4g_rx_config_t *oai4g_rx_config_create_tm56(const oai4g_frame_parm
 
 extern "C" void oai4g_rx_config_destroy(oai4g_rx_config_t *cfg)
 {
-  if (!cfg) return;
-  if (cfg->d) hipFree(cfg->d);
-  if (cfg->d_map) hipFree(cfg->d_map);
-  if (cfg->d_gold) hipFree(cfg->d_gold);
-  if (cfg->d_shift) hipFree(cfg->d_shift);
-  delete cfg;
+  if (cfg) delete cfg;
 }
 
 extern "C" int oai4g_rx_llr_count(const oai4g_rx_config_t *cfg, int subframe_index)
@@ -4309,11 +4219,7 @@ static int rx_prepare(oai4g_rx_config_t *cfg, int n_sf, rx_mode_t mode, const ch
   if (not_2cw && (cfg->h.Qm != 2 || cfg->h.qm1 != 2)) { set_err("%s", not_2cw); return -1; }
   if (n_sf <= 0) return 0;
   if (rx_check_batch(cfg, n_sf) != 0) return -1;
-  if (n_sf > cfg->shift_cap) {
-    if (cfg->d_shift) hipFree(cfg->d_shift);
-    HCK(hipMalloc(&cfg->d_shift, (size_t)n_sf), -1);
-    cfg->shift_cap = n_sf;
-  }
+  HCK(cfg->d_shift.reserve((size_t)n_sf), -1);
   return 1;
 }
 
@@ -4333,8 +4239,8 @@ static int rx_batch(oai4g_rx_config_t *cfg, int n_sf, rx_mode_t mode, const char
 {
   const int go = rx_prepare(cfg, n_sf, mode, refusal, not_2cw);
   if (go <= 0) return go;
-  HCK(oai4g_launch_rx(mode, cfg->d, &cfg->h, n_sf, d_rxdataF, d_est, rx_plane(cfg, n_sf, pil), d_llr0, d_llr1,
-                      cfg->d_shift, unscramble, (hipStream_t)stream, pil), -1);
+  HCK(oai4g_launch_rx(mode, cfg->d.get(), &cfg->h, n_sf, d_rxdataF, d_est, rx_plane(cfg, n_sf, pil), d_llr0, d_llr1,
+                      cfg->d_shift.get(), unscramble, (hipStream_t)stream, pil), -1);
   return 0;
 }
 
@@ -4465,7 +4371,7 @@ int rx_pdsch_run(oai4g_rx_config_t *cfg, const char *who, uint8_t subframe, int 
   if (batch(st.ptr<const int32_t>(r_y), st.ptr<const int32_t>(r_e), dl, dl + cfg->h.llr_stride) != 0) return -1;
   for (int i = 0; i < n_out; i++) HCK(st.down(llr[i], r_l, (size_t)n * 2, i * lb), -1);
   /* the shift lives in the configuration, not in the staging buffer */
-  if (log2_maxh) HCK(hipMemcpyAsync(log2_maxh, cfg->d_shift, 1, hipMemcpyDeviceToHost, g_scr.s), -1);
+  if (log2_maxh) HCK(hipMemcpyAsync(log2_maxh, cfg->d_shift.get(), 1, hipMemcpyDeviceToHost, g_scr.s), -1);
   HCK(st.sync(), -1);
   return n;
 }
@@ -4617,7 +4523,7 @@ extern "C" void oai4g_chest_dc_filters(uint8_t k, int16_t out[2][24])
 
 struct oai4g_chest_config {
   chest_dev_t h;
-  chest_dev_t *d = nullptr;
+  dev_buf<chest_dev_t> d;
 };
 
 static int chest_fill(const oai4g_frame_parms_t *fp, uint8_t p, chest_dev_t &h)
@@ -4652,17 +4558,15 @@ extern "C" oai4g_chest_config_t *oai4g_chest_config_create(const oai4g_frame_par
                                                            uint8_t first_subframe, uint8_t subframe_step)
 {
   NEED_INIT(nullptr);
-  auto *cfg = new oai4g_chest_config();
-  if (chest_fill(fp, p, cfg->h) != 0) { delete cfg; return nullptr; }
+  std::unique_ptr<oai4g_chest_config> cfg(new oai4g_chest_config());
+  if (chest_fill(fp, p, cfg->h) != 0) return nullptr;
   cfg->h.first_sf = first_subframe % 10;
   cfg->h.sf_step = subframe_step;
-  if (hipMalloc(&cfg->d, sizeof(chest_dev_t)) != hipSuccess ||
-      hipMemcpy(cfg->d, &cfg->h, sizeof(chest_dev_t), hipMemcpyHostToDevice) != hipSuccess) {
+  if (cfg->d.upload(&cfg->h, 1) != hipSuccess) {
     set_err("chest_config: device allocation / upload failed");
-    oai4g_chest_config_destroy(cfg);
     return nullptr;
   }
-  return cfg;
+  return cfg.release();
 }
 
 extern "C" int oai4g_chest_config_set_stride(oai4g_chest_config_t *cfg, uint32_t subframes_per_element,
@@ -4672,7 +4576,7 @@ extern "C" int oai4g_chest_config_set_stride(oai4g_chest_config_t *cfg, uint32_t
   if (!cfg || subframes_per_element < 1 || next_subframes < 1) { set_err("chest_config_set_stride: bad arguments"); return -1; }
   cfg->h.elem_syms = cfg->h.nsymb * subframes_per_element;
   cfg->h.next_syms = cfg->h.nsymb * next_subframes;
-  if (hipMemcpy(cfg->d, &cfg->h, sizeof(chest_dev_t), hipMemcpyHostToDevice) != hipSuccess) {
+  if (hipMemcpy(cfg->d.get(), &cfg->h, sizeof(chest_dev_t), hipMemcpyHostToDevice) != hipSuccess) {
     set_err("chest_config_set_stride: upload failed");
     return -1;
   }
@@ -4681,9 +4585,7 @@ extern "C" int oai4g_chest_config_set_stride(oai4g_chest_config_t *cfg, uint32_t
 
 extern "C" void oai4g_chest_config_destroy(oai4g_chest_config_t *cfg)
 {
-  if (!cfg) return;
-  if (cfg->d) hipFree(cfg->d);
-  delete cfg;
+  if (cfg) delete cfg;
 }
 
 extern "C" int oai4g_chest_batch(oai4g_chest_config_t *cfg, int n_sf, const int32_t *d_rxdataF, int32_t *d_est,
@@ -4691,7 +4593,7 @@ extern "C" int oai4g_chest_batch(oai4g_chest_config_t *cfg, int n_sf, const int3
 {
   NEED_INIT(-1);
   if (!cfg || n_sf < 0) { set_err("chest_batch: bad arguments"); return -1; }
-  HCK(oai4g_launch_chest(cfg->d, &cfg->h, n_sf, d_rxdataF, d_est, (hipStream_t)stream), -1);
+  HCK(oai4g_launch_chest(cfg->d.get(), &cfg->h, n_sf, d_rxdataF, d_est, (hipStream_t)stream), -1);
   return 0;
 }
 
@@ -4700,7 +4602,7 @@ extern "C" int oai4g_chest_batch_pilots(oai4g_chest_config_t *cfg, int n_sf, con
 {
   NEED_INIT(-1);
   if (!cfg || n_sf < 0) { set_err("chest_batch_pilots: bad arguments"); return -1; }
-  HCK(oai4g_launch_chest_pilots(cfg->d, &cfg->h, n_sf, d_rxdataF, d_pil, (hipStream_t)stream), -1);
+  HCK(oai4g_launch_chest_pilots(cfg->d.get(), &cfg->h, n_sf, d_rxdataF, d_pil, (hipStream_t)stream), -1);
   return 0;
 }
 
@@ -4718,7 +4620,7 @@ extern "C" int oai4g_rx_batch_estimated(oai4g_rx_config_t *rx, oai4g_chest_confi
   }
   const int go = rx_prepare(rx, n_sf, RX_SISO, "rx_batch_estimated: not a TM1 configuration (oai4g_rx_config_create)");
   if (go <= 0) return go;
-  HCK(oai4g_launch_rx_chest(ce->d, rx->d, &rx->h, n_sf, d_rxdataF, d_llr, rx->d_shift, unscramble,
+  HCK(oai4g_launch_rx_chest(ce->d.get(), rx->d.get(), &rx->h, n_sf, d_rxdataF, d_llr, rx->d_shift.get(), unscramble,
                             (hipStream_t)stream), -1);
   return 0;
 }
@@ -5049,7 +4951,11 @@ extern "C" int oai4g_pbch_decode_batch(const int8_t *d_llr, int n, const oai4g_f
    * synchronisation that then covers this launch */
   std::lock_guard<std::mutex> lk(g_pbch_rx_mu);
   {
-    if (!g_pbch_rx_dev) HCK(hipMalloc(&g_pbch_rx_dev, 1024), -1);
+    if (!g_pbch_rx_dev) {             /* allocated once and kept as long as the process */
+      dev_buf<uint8_t> b;
+      HCK(b.reserve(1024), -1);
+      g_pbch_rx_dev = b.release();
+    }
     if (g_pbch_rx_key != key) {
       uint8_t h[1024] = {};
       cc_job_t job = {};
@@ -5324,18 +5230,14 @@ struct oai4g_pdcch_rx_config {
   std::vector<oai4g_pdcch_plan_t> plan;
   std::vector<pdcch_cand_t> cands[10];
   uint32_t n_jobs = 0, tab_stride = 0;
-  uint8_t *dev = nullptr;            /* tables, jobs, candidates, counts, plans, receive plans */
+  dev_buf<uint8_t> dev;              /* tables, jobs, candidates, counts, plans, receive plans */
   size_t o_jobs = 0, o_cands = 0, o_ncand = 0, o_plans = 0, o_ccplan = 0;
-  uint8_t *d_rec = nullptr;
-  size_t rec_cap = 0;
+  dev_buf<uint8_t> d_rec;            /* the records of the largest batch so far (pdcch_batch_clear) */
 };
 
 extern "C" void oai4g_pdcch_rx_config_destroy(oai4g_pdcch_rx_config_t *cfg)
 {
-  if (!cfg) return;
-  if (cfg->dev) hipFree(cfg->dev);
-  if (cfg->d_rec) hipFree(cfg->d_rec);
-  delete cfg;
+  if (cfg) delete cfg;
 }
 
 extern "C" oai4g_pdcch_rx_config_t *oai4g_pdcch_rx_config_create(const oai4g_frame_parms_t *fp, uint8_t npd, uint16_t crnti,
@@ -5347,8 +5249,7 @@ extern "C" oai4g_pdcch_rx_config_t *oai4g_pdcch_rx_config_create(const oai4g_fra
   for (int i = 0; i < n_plan; i++)
     if (!pdcch_plan_ok("pdcch_rx_config_create", plan[i].L, plan[i].sizeof_bits, plan[i].sizeof_bytes)) return nullptr;
   NEED_INIT(nullptr);
-  std::unique_ptr<oai4g_pdcch_rx_config_t, void (*)(oai4g_pdcch_rx_config_t *)> cfg(new oai4g_pdcch_rx_config_t,
-                                                                                    oai4g_pdcch_rx_config_destroy);
+  std::unique_ptr<oai4g_pdcch_rx_config_t> cfg(new oai4g_pdcch_rx_config_t);
   cfg->fp = *fp;
   cfg->npd = npd;
   cfg->crnti = crnti;
@@ -5412,8 +5313,7 @@ extern "C" oai4g_pdcch_rx_config_t *oai4g_pdcch_rx_config_create(const oai4g_fra
   }
   memcpy(h.data() + cfg->o_plans, plan, (size_t)n_plan * sizeof(oai4g_pdcch_plan_t));
   memcpy(h.data() + cfg->o_ccplan, ccplan.data(), ccplan.size() * 2);
-  HCK(hipMalloc(&cfg->dev, total), nullptr);
-  HCK(hipMemcpy(cfg->dev, h.data(), total, hipMemcpyHostToDevice), nullptr);
+  HCK(cfg->dev.upload(h), nullptr);
   return cfg.release();
 }
 
@@ -5433,15 +5333,11 @@ extern "C" int oai4g_pdcch_rx_candidates(const oai4g_pdcch_rx_config_t *cfg, uin
  * with the results (unwritten fields and slots read as 0) */
 static int pdcch_batch_clear(oai4g_pdcch_rx_config_t *own, size_t need, oai4g_pdcch_rx_result_t *d_out, int n_sf, hipStream_t s)
 {
-  if (need > own->rec_cap) {
+  if (need > own->d_rec.count()) {
     HCK(hipDeviceSynchronize(), -1);
-    if (own->d_rec) hipFree(own->d_rec);
-    own->d_rec = nullptr;
-    own->rec_cap = 0;
-    HCK(hipMalloc(&own->d_rec, need), -1);
-    own->rec_cap = need;
+    HCK(own->d_rec.reserve(need), -1);
   }
-  HCK(hipMemsetAsync(own->d_rec, 0, need, s), -1);
+  HCK(hipMemsetAsync(own->d_rec.get(), 0, need, s), -1);
   HCK(hipMemsetAsync(d_out, 0, (size_t)n_sf * sizeof(oai4g_pdcch_rx_result_t), s), -1);
   return 0;
 }
@@ -5451,21 +5347,21 @@ static int pdcch_batch_clear(oai4g_pdcch_rx_config_t *own, size_t need, oai4g_pd
 static void pdcch_batch_args(const oai4g_pdcch_rx_config_t *c, uint32_t nj, uint32_t npd, const int32_t *d_comp, int n_sf,
                              int first_subframe, oai4g_pdcch_rx_result_t *d_out, cc_args_t &a, pdcch_resolve_args_t &r)
 {
-  a.jobs = (const cc_job_t *)(c->dev + c->o_jobs);
+  a.jobs = (const cc_job_t *)(c->dev.get() + c->o_jobs);
   a.n_jobs = nj;
   a.n_items = (uint32_t)n_sf;
-  a.plan = (const uint16_t *)(c->dev + c->o_ccplan);
-  a.out = c->d_rec;
+  a.plan = (const uint16_t *)(c->dev.get() + c->o_ccplan);
+  a.out = c->d_rec.get();
   a.out_stride = OAI4G_PDCCH_REC;
-  a.tab = (const uint32_t *)c->dev;
+  a.tab = (const uint32_t *)c->dev.get();
   a.tab_stride = c->tab_stride;
   a.comp = (const int16_t *)d_comp;
   a.comp_stride = (size_t)npd * c->fp.N_RB_DL * 12 * 2;
   a.first_row = (uint32_t)first_subframe;
-  r.rec = c->d_rec;
-  r.cands = (const pdcch_cand_t *)(c->dev + c->o_cands);
-  r.n_cand = (const uint32_t *)(c->dev + c->o_ncand);
-  r.plans = (const oai4g_pdcch_plan_t *)(c->dev + c->o_plans);
+  r.rec = c->d_rec.get();
+  r.cands = (const pdcch_cand_t *)(c->dev.get() + c->o_cands);
+  r.n_cand = (const uint32_t *)(c->dev.get() + c->o_ncand);
+  r.plans = (const oai4g_pdcch_plan_t *)(c->dev.get() + c->o_plans);
   r.n_jobs = nj;
   r.n_sf = (uint32_t)n_sf;
   r.first_row = (uint32_t)first_subframe;
@@ -5529,11 +5425,11 @@ extern "C" int oai4g_pdcch_rx_batch_detected(oai4g_pdcch_rx_config_t *const cfg[
   for (int i = 0; i < 3; i++) {
     const oai4g_pdcch_rx_config_t *c = cfg[i];
     pdcch_det_set_t &t = a.set[i];
-    t.jobs = (const cc_job_t *)(c->dev + c->o_jobs);
-    t.tab = (const uint32_t *)c->dev;
-    t.cands = (const pdcch_cand_t *)(c->dev + c->o_cands);
-    t.n_cand = (const uint32_t *)(c->dev + c->o_ncand);
-    t.plan = (const uint16_t *)(c->dev + c->o_ccplan);
+    t.jobs = (const cc_job_t *)(c->dev.get() + c->o_jobs);
+    t.tab = (const uint32_t *)c->dev.get();
+    t.cands = (const pdcch_cand_t *)(c->dev.get() + c->o_cands);
+    t.n_cand = (const uint32_t *)(c->dev.get() + c->o_ncand);
+    t.plan = (const uint16_t *)(c->dev.get() + c->o_ccplan);
     t.n_jobs = c->n_jobs;
     t.tab_stride = c->tab_stride;
     r.set[i] = t;

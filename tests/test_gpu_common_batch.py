@@ -74,3 +74,34 @@ def test_batch_full_grid(gpu, name, nid, fm4, dci):
                               dci=items or None, n_common=n_common)
     assert np.array_equal(pipe.iq()[0], txd)
     pipe.close()
+
+
+def test_second_set_control_equals_a_pipeline_configured_once(gpu):
+    """set_control, set_common, then set_control with another DCI set: every call rebuilds and re-uploads the
+    RE map and the static-RE plane; the IQ is that of a pipeline that was given the final settings alone"""
+    p = gpu.make_params("C1", subframe=0, subframe_step=1, Nid_cell=2, with_crs=1)
+    first, n_common = _items(gpu, "C1", p, False)
+    final = [(nbits, L, cce, rnti, pdu ^ np.uint8(0x5A)) for (nbits, L, cce, rnti, pdu) in first]
+    common = dict(pss_sss=True, pbch_pdu=np.array([0x12, 0x34, 0x56], np.uint8), frame_mod4=1,
+                  phich=[(0, 0, 0, 1), (3, 0, 5, 0)])
+    pay = np.random.default_rng(29).integers(0, 256, size=(10, p.n_cw, p.payload_stride), dtype=np.uint8)
+    iq = []
+    for steps in ((first, final), (final,)):
+        pipe = gpu.TxPipeline(p, 10)
+        try:
+            if len(steps) == 2:
+                pipe.set_control(steps[0], n_common)
+            pipe.set_common(**common)
+            pipe.set_control(steps[-1], n_common)
+            pipe.upload_payload(pay)
+            pipe.run()
+            pipe.sync()
+            iq.append(pipe.iq())
+            if len(steps) == 2:        # and the first set did leave its mark while it was in place
+                pipe.set_control(steps[0], n_common)
+                pipe.run()
+                pipe.sync()
+                assert not np.array_equal(pipe.iq(), iq[0])
+        finally:
+            pipe.close()
+    assert iq[0].tobytes() == iq[1].tobytes()

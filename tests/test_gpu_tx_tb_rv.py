@@ -144,6 +144,27 @@ def test_rv_values_are_masked(gpu):
     assert iq.tobytes() == iq_hi.tobytes()
 
 
+def test_enable_twice_returns_0_and_keeps_the_output(gpu):
+    """the second oai4g_tx_config_enable_tb_rv finds the tables in place: 0 again, the same e bits and IQ"""
+    p = _params(gpu, "C1")
+    rv = _rv_mixed(1)
+    pipe = gpu.TxPipeline(p, N_SF)
+    try:
+        pipe.upload_payload(_payload(p, "C1"))
+        L = gpu.lib()
+        out = []
+        for _ in range(2):
+            assert L.oai4g_tx_config_enable_tb_rv(pipe.cfg) == 0
+            pipe.run_rv(rv)
+            pipe.sync()
+            out.append((pipe.ebits(), pipe.iq()))
+        assert out[0][0].tobytes() == out[1][0].tobytes()
+        assert out[0][1].tobytes() == out[1][1].tobytes()
+    finally:
+        pipe.close()
+    assert _per_tb(gpu, "C1", rv)[1].tobytes() == out[1][1].tobytes()     # and that of a pipeline enabled once
+
+
 def test_batch_rv_needs_enable(gpu):
     p = _params(gpu, "C1")
     pipe = gpu.TxPipeline(p, N_SF)

@@ -436,6 +436,88 @@ int oai4g_pdcch_front_batch(const oai4g_pdcch_front_config_t *cfg, int n_sf, con
                             const int32_t *const d_est[4], int32_t *d_comp, uint8_t *d_cfi, uint8_t *d_log2_maxh,
                             void *stream);
 
+/* ---------------- UE PBCH receive front end: IQ and estimates to the MIB ---------------- */
+/* rx_pbch up to the quantised soft bits (PHY/LTE_TRANSPORT/pbch.c:876-973, normal prefix) on subframe 0:
+ * symbols 7..10, each with its own level and shift.  pbch_extract (:434: the 72 centre subcarriers, DC skipped
+ * on the receive side only; on symbols 7 and 8 the REs at nushift % 3 + {0, 3, 6, 9} of every 12 are dropped
+ * and 8 per RB packed, with one port too), pbch_channel_level (:537: all four ports' planes are looked at, the
+ * sum over a region's 72 words divided by 72 also where only 48 are defined), log2_maxh = 3 + log2_approx / 2,
+ * pbch_channel_compensation (:610), pbch_detection_mrc (:719), pbch_alamouti (:816) and pbch_quantize (:854).
+ * Argument conventions of oai4g_rx_pdcch_front: rxdataF[a] rows [nsymb][N] (rows 7..10 are read),
+ * dl_ch_estimates[(p << 1) + a] for the nb_ports (1 or 2) estimated ports (rows 7..10 when high_speed_flag == 1,
+ * else row 0).  nb_ports is the caller's, not frame_parms': the UE does not know the eNB's count before the
+ * MIB.  ALAMOUTI with one estimated port is accepted, as in the reference: port 1's plane is 0 and the result
+ * equals SISO.  Outputs, each may be null: rxdataF_comp, plane 0 after combining, 4 * 72 words (words 48..71
+ * of the first two regions, which the reference never writes, are 0); log2_maxh[4]; llr, the 480 soft bits
+ * (96 + 96 + 144 + 144); diag_planes, the four compensated planes [(p << 1) + a][288] before MRC.  Returns 0,
+ * or -1: the extended prefix (the reference's own quantise lengths overrun pbch_E there), more than 2
+ * estimated ports, more than 2 receive antennas, a mimo_mode other than SISO / ALAMOUTI. */
+int oai4g_rx_pbch_front(int32_t *const *rxdataF, int32_t *const *dl_ch_estimates, const oai4g_frame_parms_t *frame_parms,
+                        uint8_t nb_antennas_rx, uint8_t nb_ports, uint8_t mimo_mode, uint32_t high_speed_flag,
+                        int32_t *rxdataF_comp, uint8_t log2_maxh[4], int8_t *llr, int32_t *diag_planes);
+/* rx_pbch whole (pbch.c:876): the front end, its 480 soft bits at llr[frame_mod4 * 480] of a cleared
+ * 1920-byte buffer, then oai4g_pbch_decode.  Returns as oai4g_pbch_decode does (1 / 2 / 4, or -1 with
+ * oai4g_last_error() empty when the CRC matches none); also -1 for frame_mod4 > 3 and what the front refuses. */
+int oai4g_rx_pbch(int32_t *const *rxdataF, int32_t *const *dl_ch_estimates, const oai4g_frame_parms_t *frame_parms,
+                  uint8_t nb_antennas_rx, uint8_t nb_ports, uint8_t mimo_mode, uint32_t high_speed_flag,
+                  uint8_t frame_mod4, uint8_t decoded_output[3]);
+/* The batched front end, device pointers, one launch for n subframes 0: d_rxdataF [n][nb_antennas_rx][nsymb][N]
+ * as oai4g_fep_batch writes it, d_est[(p << 1) + a] [n][nsymb][N] as oai4g_chest_batch writes it -> d_llr
+ * [n][2][480], the soft bits under SISO and under ALAMOUTI (the combining is their only difference), and
+ * d_log2_maxh [n][4].  Asynchronous on `stream`.  Returns 0 or -1. */
+typedef struct oai4g_pbch_front_config oai4g_pbch_front_config_t;
+oai4g_pbch_front_config_t *oai4g_pbch_front_config_create(const oai4g_frame_parms_t *frame_parms, uint8_t nb_antennas_rx,
+                                                          uint8_t nb_ports, uint32_t high_speed_flag);
+void oai4g_pbch_front_config_destroy(oai4g_pbch_front_config_t *cfg);
+int oai4g_pbch_front_batch(const oai4g_pbch_front_config_t *cfg, int n, const int32_t *d_rxdataF,
+                           const int32_t *const d_est[4], int8_t *d_llr, uint8_t *d_log2_maxh, void *stream);
+/* pbch_detection's search (PHY/LTE_TRANSPORT/initial_sync.c:135-161) over d_llr as above: frame_mod4 0..3,
+ * for each SISO then ALAMOUTI; the first hypothesis whose CRC names 1 or 2 antennas wins (one naming 4 does
+ * not stop the search).  The eight decodes of every subframe run in one launch (a quarter's 480 soft bits
+ * alone: the rest of the reference's buffer is 0), a second, one lane per subframe, picks.  d_out [n]
+ * (device).  The configuration keeps the constants of its cell and the decode records; one launch at a time
+ * per configuration.  Asynchronous on `stream`, no host visit.  Returns 0 or -1. */
+typedef struct {
+  uint8_t tx_ant;            /* 1 / 2, or 0xFF: no hypothesis decoded */
+  uint8_t frame_mod4, mimo_mode;
+  uint8_t mib[3];            /* as oai4g_pbch_decode returns them */
+  uint8_t pad[2];
+} oai4g_pbch_detect_t;
+int oai4g_pbch_detect_batch(oai4g_pbch_front_config_t *cfg, int n, const int8_t *d_llr, oai4g_pbch_detect_t *d_out,
+                            void *stream);
+
+/* ---------------- UE PHICH reception ---------------- */
+/* rx_phich's numeric core (PHY/LTE_TRANSPORT/phich.c:1112-1346, normal prefix, normal duration): the 12
+ * scrambling signs of c_init = ((subframe + 1)(Nid_cell + 1) << 9) + Nid_cell, the 24 signs d of nseq_PHICH
+ * (:1131-1222), and HI16 += x d over the 8 int16 at word phich_reg[ngroup_PHICH][quad] * 4 of plane 0 of the
+ * PDCCH front's rxdataF_comp (the packed symbol 0, 8 * N_RB_DL words are read), accumulated in int16_t as the
+ * reference does: it wraps after every term.  *HI16, when not null, receives the sum.  Group and sequence come
+ * from oai4g_phich_group_seq; the HARQ bookkeeping behind the decision is the caller's.  Returns 1 (NACK:
+ * HI16 > 0), 0 (ACK), or -1: what oai4g_generate_phich refuses, a group outside
+ * oai4g_generate_phich_reg_mapping's, nseq_PHICH > 7. */
+int oai4g_rx_phich(const oai4g_frame_parms_t *frame_parms, uint8_t subframe, const int32_t *rxdataF_comp,
+                   uint8_t ngroup_PHICH, uint8_t nseq_PHICH, int16_t *HI16);
+/* The batched form behind oai4g_pdcch_front_batch: d_comp [n_sf][3 * 12 * N_RB_DL] as it writes it, subframe
+ * slot i of index (first_subframe + i * subframe_step) mod 10; d_items [n_items] (device) name a slot, a group
+ * and a sequence each; d_out [n_items] in one launch.  An item outside the batch, the mapping or nseq > 7
+ * gives {0, 0xFF}.  The signs and word offsets of every (subframe index, group, sequence) are a table of the
+ * configuration.  Asynchronous on `stream`.  Returns 0 or -1. */
+typedef struct {
+  uint32_t slot;
+  uint8_t ngroup, nseq, pad[2];
+} oai4g_phich_rx_item_t;
+typedef struct {
+  int16_t HI16;
+  uint8_t nack;              /* 1 NACK, 0 ACK, 0xFF: refused item */
+  uint8_t pad;
+} oai4g_phich_rx_out_t;
+typedef struct oai4g_phich_rx_config oai4g_phich_rx_config_t;
+oai4g_phich_rx_config_t *oai4g_phich_rx_config_create(const oai4g_frame_parms_t *frame_parms, uint8_t first_subframe,
+                                                      uint8_t subframe_step);
+void oai4g_phich_rx_config_destroy(oai4g_phich_rx_config_t *cfg);
+int oai4g_phich_rx_batch(const oai4g_phich_rx_config_t *cfg, const int32_t *d_comp, int n_sf,
+                         const oai4g_phich_rx_item_t *d_items, int n_items, oai4g_phich_rx_out_t *d_out, void *stream);
+
 /* ---------------- UE PDSCH demodulation (second half) ---------------- */
 /* rx_pdsch (PHY/LTE_TRANSPORT/dlsch_demodulation.c:82) over the PDSCH symbols of one subframe as
  * dlsim runs it (dlsim.c:3188-3260): dlsch_extract_rbs_single (:3167), dlsch_channel_level (:2777)

@@ -414,6 +414,27 @@ _SIGS = {
     "oai4g_pdcch_front_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                                ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_void_p, ctypes.c_void_p]),
+    "oai4g_rx_pbch_front": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+                                           ctypes.POINTER(FrameParms), ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint8,
+                                           ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_void_p]),
+    "oai4g_rx_pbch": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+                                     ctypes.POINTER(FrameParms), ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint8,
+                                     ctypes.c_uint32, ctypes.c_uint8, ctypes.c_void_p]),
+    "oai4g_pbch_front_config_create": (ctypes.c_void_p, [ctypes.POINTER(FrameParms), ctypes.c_uint8, ctypes.c_uint8,
+                                                         ctypes.c_uint32]),
+    "oai4g_pbch_front_config_destroy": (None, [ctypes.c_void_p]),
+    "oai4g_pbch_front_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                              ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p]),
+    "oai4g_pbch_detect_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p]),
+    "oai4g_rx_phich": (ctypes.c_int, [ctypes.POINTER(FrameParms), ctypes.c_uint8, ctypes.c_void_p, ctypes.c_uint8,
+                                      ctypes.c_uint8, ctypes.POINTER(ctypes.c_int16)]),
+    "oai4g_phich_rx_config_create": (ctypes.c_void_p, [ctypes.POINTER(FrameParms), ctypes.c_uint8, ctypes.c_uint8]),
+    "oai4g_phich_rx_config_destroy": (None, [ctypes.c_void_p]),
+    "oai4g_phich_rx_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                            ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 
@@ -1459,6 +1480,191 @@ class PdcchRxBatchDetected:
                 b.close()
             self.L.oai4g_dev_free(self.d_out)
             self.d_out = None
+
+
+def _pbch_planes(nb_ports, nb_rx, rxdataF, est):
+    keep = [np.ascontiguousarray(rxdataF[a], dtype=np.int32).ravel() for a in range(min(nb_rx, 2))]
+    rx = (ctypes.c_void_p * 2)(*[k.ctypes.data for k in keep])
+    ep = (ctypes.c_void_p * 4)()
+    for p in range(min(nb_ports, 2)):
+        for a in range(min(nb_rx, 2)):
+            keep.append(np.ascontiguousarray(est[(p, a)], dtype=np.int32).ravel())
+            ep[2 * p + a] = keep[-1].ctypes.data
+    return keep, rx, ep
+
+
+def rx_pbch_front(fp, rxdataF, est, nb_ports, mimo_mode, high_speed_flag=1, diag=False):
+    """oai4g_rx_pbch_front: rxdataF[a] and est[(p, a)] (rows [nsymb][N] of subframe 0) -> (plane 0 of rxdataF_comp
+    int32[288], log2_maxh uint8[4], the 480 soft bits int8), and with diag the four planes before MRC [4][288]."""
+    nb_rx = len(rxdataF)
+    comp = np.zeros(288, dtype=np.int32)
+    l2 = np.zeros(4, dtype=np.uint8)
+    llr = np.zeros(480, dtype=np.int8)
+    planes = np.zeros((4, 288), dtype=np.int32) if diag else None
+    keep, rx, ep = _pbch_planes(nb_ports, nb_rx, rxdataF, est)
+    _check(lib().oai4g_rx_pbch_front(rx, ep, ctypes.byref(fp), nb_rx, nb_ports, mimo_mode, high_speed_flag, _ptr(comp),
+                                     _ptr(l2), _ptr(llr), _ptr(planes) if diag else None) == 0)
+    return (comp, l2, llr) + ((planes,) if diag else ())
+
+
+def rx_pbch(fp, rxdataF, est, nb_ports, mimo_mode, frame_mod4, high_speed_flag=1):
+    """oai4g_rx_pbch: (1 / 2 / 4 eNB antennas or -1 when the CRC matches none, the three MIB bytes); a refused
+    call raises."""
+    nb_rx = len(rxdataF)
+    out = np.zeros(3, dtype=np.uint8)
+    keep, rx, ep = _pbch_planes(nb_ports, nb_rx, rxdataF, est)
+    r = lib().oai4g_rx_pbch(rx, ep, ctypes.byref(fp), nb_rx, nb_ports, mimo_mode, high_speed_flag, frame_mod4, _ptr(out))
+    _check(r >= 0 or not lib().oai4g_last_error())
+    return r, bytes(out)
+
+
+class PbchDetect(ctypes.Structure):
+    _fields_ = [("tx_ant", ctypes.c_uint8), ("frame_mod4", ctypes.c_uint8), ("mimo_mode", ctypes.c_uint8),
+                ("mib", ctypes.c_uint8 * 3), ("pad", ctypes.c_uint8 * 2)]
+
+
+class PbchFrontBatch:
+    """Device-resident PBCH front end and detection of n subframes 0 (oai4g_pbch_front_batch,
+    oai4g_pbch_detect_batch): the FEP output [n (+ 1)][nb_rx][nsymb][N] and the estimate planes of ports x antennas
+    -> d_llr [n][2][480], d_log2 [n][4], d_out [n] PbchDetect."""
+
+    def __init__(self, fp, n, nb_rx, nb_ports, high_speed_flag=1, first_subframe=0, subframe_step=0):
+        init()
+        self.L, self.fp, self.n, self.nb_rx, self.nb_ports = lib(), fp, n, nb_rx, nb_ports
+        self.first, self.step = first_subframe, subframe_step
+        self.cfg = self.L.oai4g_pbch_front_config_create(ctypes.byref(fp), nb_rx, nb_ports, high_speed_flag)
+        _check(bool(self.cfg))
+        self.plane = n * fp.symbols_per_tti * fp.ofdm_symbol_size
+        self.d_est = self.L.oai4g_dev_alloc(4 * self.plane * 4)
+        self.d_llr = self.L.oai4g_dev_alloc(n * 960)
+        self.d_log2 = self.L.oai4g_dev_alloc(n * 4)
+        self.d_out = self.L.oai4g_dev_alloc(n * ctypes.sizeof(PbchDetect))
+        _check(all(bool(p) for p in (self.d_est, self.d_llr, self.d_log2, self.d_out)))
+        self._chest = []
+
+    def est_plane(self, p, a):
+        return ctypes.c_void_p(self.d_est + (2 * p + a) * self.plane * 4)
+
+    def upload_estimates(self, est):
+        """est[(p, a)] = int32 [n][nsymb * N]"""
+        for (p, a), v in est.items():
+            v = np.ascontiguousarray(v, dtype=np.int32)
+            assert v.size == self.plane
+            _check(self.L.oai4g_memcpy_h2d(self.est_plane(p, a), _ptr(v), v.nbytes) == 0)
+
+    def upload_llr(self, llr):
+        """the soft bits themselves, int8 [n][2][480] (the detection alone)"""
+        llr = np.ascontiguousarray(llr, dtype=np.int8)
+        assert llr.size == self.n * 960
+        _check(self.L.oai4g_memcpy_h2d(self.d_llr, _ptr(llr), llr.nbytes) == 0)
+
+    def estimate(self, d_rxF, stream=None):
+        """oai4g_chest_batch per (port, antenna) over the FEP output [n + 1][nb_rx][nsymb][N]"""
+        if not self._chest:
+            for p in range(self.nb_ports):
+                cfg = self.L.oai4g_chest_config_create(ctypes.byref(self.fp), p, self.first, self.step)
+                _check(bool(cfg))
+                self._chest.append(cfg)
+                _check(self.L.oai4g_chest_config_set_stride(cfg, self.nb_rx, self.nb_rx) == 0)
+        grid = self.fp.symbols_per_tti * self.fp.ofdm_symbol_size
+        for p, cfg in enumerate(self._chest):
+            for a in range(self.nb_rx):
+                _check(self.L.oai4g_chest_batch(cfg, self.n, ctypes.c_void_p(d_rxF + a * grid * 4), self.est_plane(p, a),
+                                                stream) == 0)
+
+    def launch(self, d_rxF, stream=None):
+        ep = (ctypes.c_void_p * 4)(*[self.est_plane(i >> 1, i & 1).value for i in range(4)])
+        _check(self.L.oai4g_pbch_front_batch(self.cfg, self.n, d_rxF, ep, self.d_llr, self.d_log2, stream) == 0)
+
+    def detect(self, stream=None):
+        _check(self.L.oai4g_pbch_detect_batch(self.cfg, self.n, self.d_llr, self.d_out, stream) == 0)
+
+    def results(self):
+        """(llr int8 [n][2][480], log2_maxh uint8 [n][4])"""
+        _check(self.L.oai4g_sync() == 0)
+        llr, l2 = np.empty((self.n, 2, 480), dtype=np.int8), np.empty((self.n, 4), dtype=np.uint8)
+        _check(self.L.oai4g_memcpy_d2h(_ptr(llr), self.d_llr, llr.nbytes) == 0)
+        _check(self.L.oai4g_memcpy_d2h(_ptr(l2), self.d_log2, l2.nbytes) == 0)
+        return llr, l2
+
+    def estimates(self):
+        """est[(p, a)] = int32 [n][nsymb * N] as they stand on the device"""
+        _check(self.L.oai4g_sync() == 0)
+        est = {}
+        for p in range(self.nb_ports):
+            for a in range(self.nb_rx):
+                v = np.empty((self.n, self.plane // self.n), dtype=np.int32)
+                _check(self.L.oai4g_memcpy_d2h(_ptr(v), self.est_plane(p, a), v.nbytes) == 0)
+                est[(p, a)] = v
+        return est
+
+    def detected(self):
+        _check(self.L.oai4g_sync() == 0)
+        out = (PbchDetect * self.n)()
+        _check(self.L.oai4g_memcpy_d2h(ctypes.addressof(out), self.d_out, ctypes.sizeof(out)) == 0)
+        return out
+
+    def close(self):
+        if self.cfg:
+            self.L.oai4g_sync()
+            for cfg in self._chest:
+                self.L.oai4g_chest_config_destroy(cfg)
+            for ptr in (self.d_est, self.d_llr, self.d_log2, self.d_out):
+                self.L.oai4g_dev_free(ptr)
+            self.L.oai4g_pbch_front_config_destroy(self.cfg)
+            self.cfg = None
+
+
+def rx_phich(fp, subframe, comp, ngroup, nseq):
+    """oai4g_rx_phich on plane 0 of the PDCCH front's rxdataF_comp: (1 NACK / 0 ACK, HI16)"""
+    comp = np.ascontiguousarray(comp, dtype=np.int32)
+    assert comp.size >= 8 * fp.N_RB_DL
+    hi = ctypes.c_int16()
+    r = lib().oai4g_rx_phich(ctypes.byref(fp), subframe, _ptr(comp), ngroup, nseq, ctypes.byref(hi))
+    _check(r >= 0)
+    return r, hi.value
+
+
+class PhichRxItem(ctypes.Structure):
+    _fields_ = [("slot", ctypes.c_uint32), ("ngroup", ctypes.c_uint8), ("nseq", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 2)]
+
+
+class PhichRxOut(ctypes.Structure):
+    _fields_ = [("HI16", ctypes.c_int16), ("nack", ctypes.c_uint8), ("pad", ctypes.c_uint8)]
+
+
+class PhichRxBatch:
+    """oai4g_phich_rx_batch behind PdcchFrontBatch: items = [(slot, ngroup, nseq)] -> [(HI16, nack)]"""
+
+    def __init__(self, fp, items, first_subframe=0, subframe_step=1):
+        init()
+        self.L, self.n_items = lib(), len(items)
+        self.cfg = self.L.oai4g_phich_rx_config_create(ctypes.byref(fp), first_subframe, subframe_step)
+        _check(bool(self.cfg))
+        arr = (PhichRxItem * max(1, len(items)))()
+        for i, (slot, g, q) in enumerate(items):
+            arr[i].slot, arr[i].ngroup, arr[i].nseq = slot, g, q
+        self.d_items = self.L.oai4g_dev_alloc(ctypes.sizeof(arr))
+        self.d_out = self.L.oai4g_dev_alloc(max(1, len(items)) * ctypes.sizeof(PhichRxOut))
+        _check(bool(self.d_items) and bool(self.d_out))
+        _check(self.L.oai4g_memcpy_h2d(self.d_items, ctypes.addressof(arr), ctypes.sizeof(arr)) == 0)
+
+    def launch(self, d_comp, n_sf, stream=None):
+        _check(self.L.oai4g_phich_rx_batch(self.cfg, d_comp, n_sf, self.d_items, self.n_items, self.d_out, stream) == 0)
+
+    def results(self):
+        _check(self.L.oai4g_sync() == 0)
+        out = (PhichRxOut * max(1, self.n_items))()
+        _check(self.L.oai4g_memcpy_d2h(ctypes.addressof(out), self.d_out, ctypes.sizeof(out)) == 0)
+        return [(o.HI16, o.nack) for o in out[:self.n_items]]
+
+    def close(self):
+        if self.cfg:
+            self.L.oai4g_sync()
+            self.L.oai4g_dev_free(self.d_items)
+            self.L.oai4g_dev_free(self.d_out)
+            self.L.oai4g_phich_rx_config_destroy(self.cfg)
+            self.cfg = None
 
 
 def _upload_tiled(dec, base, chunk_bytes=64 << 20):

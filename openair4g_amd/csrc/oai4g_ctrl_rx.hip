@@ -49,11 +49,14 @@ static __device__ __forceinline__ uint32_t cc_rev(uint32_t i)
 }
 
 /* ARGS = cc_det_args_t: the PDCCH batch whose subframes carry a detected num_pdcch_symbols each; the jobs, the
- * gather table and the receive plans are then those of the subframe's own count */
+ * gather table and the receive plans are then those of the subframe's own count.
+ * ARGS = cc_hyp_args_t: pbch_detection's eight hypotheses of a subframe as its jobs; job j unscrambles all of its
+ * 480 soft bits with the Gold words of quarter j >> 1 */
 template <int NMAX, typename ARGS = cc_args_t>
 __global__ void __launch_bounds__(64) k_cc_decode(ARGS a)
 {
-  constexpr bool DET = !std::is_same<ARGS, cc_args_t>::value;
+  constexpr bool DET = std::is_same<ARGS, cc_det_args_t>::value;
+  constexpr bool HYP = std::is_same<ARGS, cc_hyp_args_t>::value;
   __shared__ int8_t s_d[3 * NMAX];
   __shared__ uint64_t s_tb[NMAX];
   __shared__ uint8_t s_out[NMAX / 8 + 8];
@@ -80,7 +83,8 @@ __global__ void __launch_bounds__(64) k_cc_decode(ARGS a)
   const int8_t *__restrict__ e = a.e + (size_t)item * a.e_stride + job.e_off;
   const uint32_t *__restrict__ tab = a.tab ? a.tab + (size_t)row * a.tab_stride + job.e_off : nullptr;
   const int16_t *__restrict__ comp = a.comp + (size_t)item * a.comp_stride;
-  const uint32_t qlo = a.gold ? (uint32_t)a.quarter[item] * (E >> 2) : 0u, qhi = a.gold ? qlo + (E >> 2) : 0u;
+  if constexpr (HYP) a.gold += 15u * ((dec - item * a.n_jobs) >> 1);
+  const uint32_t qlo = !HYP && a.gold ? (uint32_t)a.quarter[item] * (E >> 2) : 0u, qhi = HYP ? E : a.gold ? qlo + (E >> 2) : 0u;
   bool clamped = false;
   for (uint32_t q = lane; q < D3; q += 64) {
     int v = 0;
@@ -256,6 +260,14 @@ hipError_t oai4g_launch_cc_decode(const cc_args_t &a, uint32_t nmax, hipStream_t
     hipLaunchKernelGGL(k_cc_decode<64>, dim3(n), dim3(64), 0, s, a);
   else
     hipLaunchKernelGGL(k_cc_decode<512>, dim3(n), dim3(64), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t oai4g_launch_cc_decode_hyp(const cc_hyp_args_t &a, hipStream_t s)
+{
+  const uint32_t n = a.n_items * a.n_jobs;
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL((k_cc_decode<64, cc_hyp_args_t>), dim3(n), dim3(64), 0, s, a);
   return hipGetLastError();
 }
 

@@ -5623,3 +5623,304 @@ extern "C" int oai4g_pdcch_front_batch(const oai4g_pdcch_front_config_t *cfg, in
   HCK(oai4g_launch_pdcch_front(a, (hipStream_t)stream), -1);
   return 0;
 }
+
+/* ------------------------------------------------------------------------------------------
+ * PBCH receive front end: rx_pbch up to the quantised soft bits (pbch.c:876-973), k_pbch_front, and
+ * pbch_detection's hypothesis search (initial_sync.c:135-161) behind it.
+ * ---------------------------------------------------------------------------------------- */
+static int pbch_front_ok(const char *who, const oai4g_frame_parms_t *fp, int nb_rx, int nb_ports, uint8_t mimo_mode)
+{
+  if (!fp) { set_err("%s: null frame parameters", who); return 0; }
+  if (fp->Ncp != 0) { set_err("%s: only the normal cyclic prefix is supported (the reference's quantise lengths overrun pbch_E with the extended one)", who); return 0; }
+  if (nb_ports == 4) { set_err("%s: 4 estimated TX ports are not supported", who); return 0; }
+  if (nb_ports < 1 || nb_ports > 2) { set_err("%s: %d estimated TX ports (1 or 2)", who, nb_ports); return 0; }
+  if (nb_rx < 1 || nb_rx > 2) { set_err("%s: %d receive antennas (1 or 2)", who, nb_rx); return 0; }
+  if (mimo_mode != OAI4G_SISO && mimo_mode != OAI4G_ALAMOUTI) { set_err("%s: mimo_mode %u (SISO or ALAMOUTI)", who, mimo_mode); return 0; }
+  const uint32_t N = fp->ofdm_symbol_size;
+  if (fp->N_RB_DL < 6 || 6u * fp->N_RB_DL + 41u > N || fp->symbols_per_tti != 14) {   /* estimate words 6 N_RB - 31 .. 6 N_RB + 40 */
+    set_err("%s: N_RB_DL %u does not fit the symbol size %u", who, fp->N_RB_DL, N);
+    return 0;
+  }
+  return 1;
+}
+
+static void pbch_front_fill(pbch_front_args_t &a, const oai4g_frame_parms_t *fp, int nb_rx, int nb_ports, uint8_t mimo_mode,
+                            uint32_t high_speed_flag)
+{
+  memset(&a, 0, sizeof(a));
+  a.N = fp->ofdm_symbol_size;
+  a.N_RB = fp->N_RB_DL;
+  a.nushift3 = fp->nushift % 3u;
+  a.nb_tx = (uint32_t)nb_ports;
+  a.nb_rx = (uint32_t)nb_rx;
+  a.alamouti = mimo_mode == OAI4G_ALAMOUTI;
+  a.high_speed = high_speed_flag == 1;
+}
+
+extern "C" int oai4g_rx_pbch_front(int32_t *const *rxdataF, int32_t *const *dl_ch_estimates, const oai4g_frame_parms_t *fp,
+                                   uint8_t nb_antennas_rx, uint8_t nb_ports, uint8_t mimo_mode, uint32_t high_speed_flag,
+                                   int32_t *rxdataF_comp, uint8_t log2_maxh[4], int8_t *llr, int32_t *diag_planes)
+{
+  if (!pbch_front_ok("rx_pbch_front", fp, nb_antennas_rx, nb_ports, mimo_mode)) return -1;
+  if (!rxdataF || !dl_ch_estimates) { set_err("rx_pbch_front: bad arguments"); return -1; }
+  for (int a = 0; a < nb_antennas_rx; a++)
+    for (int p = 0; p < nb_ports; p++)
+      if (!rxdataF[a] || !dl_ch_estimates[(p << 1) + a]) { set_err("rx_pbch_front: null plane"); return -1; }
+  NEED_INIT(-1);
+  const size_t N = fp->ofdm_symbol_size, grid = 14 * N * 4, grid_s = up256(grid);
+  const size_t cb = OAI4G_PBCH_WORDS * 4, lb = 2 * OAI4G_PBCH_SOFT;
+  stage_t st("rx_pbch_front");
+  const int r_rx = st.add(2 * grid_s), r_est = st.add(4 * grid_s), r_comp = st.add(cb);
+  const int r_pl = st.add(4 * cb), r_llr = st.add(lb), r_l2 = st.add(4);
+  if (!st.open()) return -1;
+  pbch_front_args_t a;
+  pbch_front_fill(a, fp, nb_antennas_rx, nb_ports, mimo_mode, high_speed_flag);
+  a.n_sf = 1;
+  a.rxF = st.ptr<const int32_t>(r_rx);
+  a.rx_ant_stride = grid_s / 4;
+  const size_t e0 = high_speed_flag == 1 ? 7 * N * 4 : 0, eb = high_speed_flag == 1 ? 4 * N * 4 : N * 4;   /* the rows read */
+  for (int rx = 0; rx < nb_antennas_rx; rx++) {
+    HCK(st.up(r_rx, (const uint8_t *)rxdataF[rx] + 7 * N * 4, 4 * N * 4, rx * grid_s + 7 * N * 4), -1);
+    for (int p = 0; p < nb_ports; p++) {
+      const int pl = (p << 1) + rx;
+      HCK(st.up(r_est, (const uint8_t *)dl_ch_estimates[pl] + e0, eb, pl * grid_s + e0), -1);
+      a.est[pl] = st.ptr<const int32_t>(r_est, pl * grid_s);
+    }
+  }
+  a.comp = st.ptr<int32_t>(r_comp);
+  a.planes = diag_planes ? st.ptr<int32_t>(r_pl) : nullptr;
+  a.llr = st.ptr<int8_t>(r_llr);
+  a.log2_maxh = st.ptr(r_l2);
+  HCK(oai4g_launch_pbch_front(a, g_scr.s), -1);
+  if (rxdataF_comp) HCK(st.down(rxdataF_comp, r_comp, cb), -1);
+  if (diag_planes) HCK(st.down(diag_planes, r_pl, 4 * cb), -1);
+  if (llr) HCK(st.down(llr, r_llr, OAI4G_PBCH_SOFT, a.alamouti ? OAI4G_PBCH_SOFT : 0), -1);
+  if (log2_maxh) HCK(st.down(log2_maxh, r_l2, 4), -1);
+  HCK(st.sync(), -1);
+  return 0;
+}
+
+extern "C" int oai4g_rx_pbch(int32_t *const *rxdataF, int32_t *const *dl_ch_estimates, const oai4g_frame_parms_t *fp,
+                             uint8_t nb_antennas_rx, uint8_t nb_ports, uint8_t mimo_mode, uint32_t high_speed_flag,
+                             uint8_t frame_mod4, uint8_t decoded_output[3])
+{
+  if (frame_mod4 > 3 || !decoded_output) { set_err("rx_pbch: frame_mod4 %u or a null argument", frame_mod4); return -1; }
+  int8_t llr[1920];
+  memset(llr, 0, sizeof(llr));                                         /* pbch.c:908 */
+  if (oai4g_rx_pbch_front(rxdataF, dl_ch_estimates, fp, nb_antennas_rx, nb_ports, mimo_mode, high_speed_flag, nullptr, nullptr,
+                          llr + frame_mod4 * OAI4G_PBCH_SOFT, nullptr) != 0)
+    return -1;
+  return oai4g_pbch_decode(llr, fp, frame_mod4, decoded_output);
+}
+
+struct oai4g_pbch_front_config {
+  oai4g_frame_parms_t fp;
+  pbch_front_args_t a;
+  dev_buf<uint8_t> consts;   /* the detection's eight jobs | the receive plan at 256 | the cell's 60 Gold words at 512 */
+  dev_buf<uint8_t> rec;      /* [n][8][4] decode records of the last detection */
+};
+
+extern "C" oai4g_pbch_front_config_t *oai4g_pbch_front_config_create(const oai4g_frame_parms_t *fp, uint8_t nb_antennas_rx,
+                                                                     uint8_t nb_ports, uint32_t high_speed_flag)
+{
+  if (!pbch_front_ok("pbch_front_config_create", fp, nb_antennas_rx, nb_ports, OAI4G_SISO)) return nullptr;
+  NEED_INIT(nullptr);
+  std::unique_ptr<oai4g_pbch_front_config_t> cfg(new oai4g_pbch_front_config_t);
+  cfg->fp = *fp;
+  pbch_front_fill(cfg->a, fp, nb_antennas_rx, nb_ports, OAI4G_SISO, high_speed_flag);
+  std::vector<uint8_t> h(1024, 0);
+  for (uint32_t j = 0; j < 8; j++) {
+    cc_job_t job = {};
+    job.e_off = (j & 1u) * OAI4G_PBCH_SOFT;
+    job.E = OAI4G_PBCH_SOFT;
+    job.D = 40;
+    job.crc_bits = 24;
+    memcpy(h.data() + j * sizeof(job), &job, sizeof(job));
+  }
+  static_assert(8 * sizeof(cc_job_t) <= 256, "the jobs end before the plan");
+  cc_rx_plan_h(40, (uint16_t *)(h.data() + 256));
+  pbch_gold_h(fp->Nid_cell, 1920, (uint32_t *)(h.data() + 512));
+  HCK(cfg->consts.upload(h), nullptr);
+  return cfg.release();
+}
+
+extern "C" void oai4g_pbch_front_config_destroy(oai4g_pbch_front_config_t *cfg) { delete cfg; }
+
+extern "C" int oai4g_pbch_front_batch(const oai4g_pbch_front_config_t *cfg, int n, const int32_t *d_rxdataF,
+                                      const int32_t *const d_est[4], int8_t *d_llr, uint8_t *d_log2_maxh, void *stream)
+{
+  if (!cfg || n < 0 || (n > 0 && (!d_rxdataF || !d_est || !d_llr || !d_log2_maxh))) {
+    set_err("pbch_front_batch: bad arguments");
+    return -1;
+  }
+  pbch_front_args_t a = cfg->a;
+  for (uint32_t p = 0; p < a.nb_tx; p++)
+    for (uint32_t rx = 0; rx < a.nb_rx; rx++) {
+      if (n > 0 && !d_est[(p << 1) + rx]) { set_err("pbch_front_batch: null estimate plane %u", (p << 1) + rx); return -1; }
+      a.est[(p << 1) + rx] = n > 0 ? d_est[(p << 1) + rx] : nullptr;
+    }
+  NEED_INIT(-1);
+  if (n == 0) return 0;
+  const size_t grid = (size_t)cfg->fp.symbols_per_tti * cfg->fp.ofdm_symbol_size;
+  a.n_sf = (uint32_t)n;
+  a.rxF = d_rxdataF;
+  a.rx_ant_stride = grid;
+  a.rx_sf_stride = grid * a.nb_rx;
+  a.est_sf_stride = grid;
+  a.llr = d_llr;
+  a.log2_maxh = d_log2_maxh;
+  HCK(oai4g_launch_pbch_front(a, (hipStream_t)stream), -1);
+  return 0;
+}
+
+extern "C" int oai4g_pbch_detect_batch(oai4g_pbch_front_config_t *cfg, int n, const int8_t *d_llr, oai4g_pbch_detect_t *d_out,
+                                       void *stream)
+{
+  if (!cfg || n < 0 || (n > 0 && (!d_llr || !d_out))) { set_err("pbch_detect_batch: bad arguments"); return -1; }
+  NEED_INIT(-1);
+  if (n == 0) return 0;
+  if (cfg->rec.count() < (size_t)n * 32) {
+    HCK(hipDeviceSynchronize(), -1);                                   /* an earlier detection may still write the old records */
+    HCK(cfg->rec.reserve((size_t)n * 32), -1);
+  }
+  cc_hyp_args_t a;
+  memset(&a, 0, sizeof(a));
+  a.e = d_llr;
+  a.e_stride = 2 * OAI4G_PBCH_SOFT;
+  a.jobs = (const cc_job_t *)cfg->consts.get();
+  a.n_jobs = 8;
+  a.n_items = (uint32_t)n;
+  a.plan = (const uint16_t *)(cfg->consts.get() + 256);
+  a.gold = (const uint32_t *)(cfg->consts.get() + 512);
+  a.out = cfg->rec.get();
+  a.out_stride = 4;
+  a.pbch_out = 1;
+  HCK(oai4g_launch_cc_decode_hyp(a, (hipStream_t)stream), -1);
+  HCK(oai4g_launch_pbch_resolve(cfg->rec.get(), (uint32_t)n, d_out, (hipStream_t)stream), -1);
+  return 0;
+}
+
+/* ------------------------------------------------------------------------------------------
+ * PHICH reception: rx_phich's correlation (phich.c:1112-1346), k_phich_rx.
+ * ---------------------------------------------------------------------------------------- */
+/* the table entries of one subframe index: [ng][8].  Returns the number of groups, or -1 */
+static int phich_rx_table(const char *who, const oai4g_frame_parms_t *fp, uint32_t subframe, phich_rx_ent_t *ent)
+{
+  if (!fp) { set_err("%s: null frame parameters", who); return -1; }
+  if (fp->Ncp != 0 || fp->phich_duration != 0 || fp->nushift >= 3) {   /* as oai4g_generate_phich */
+    set_err("%s: only normal CP, normal duration and nushift < 3 are defined", who);
+    return -1;
+  }
+  if (subframe > 9 || fp->N_RB_DL < 6 || fp->N_RB_DL > 110) { set_err("%s: subframe %u / N_RB_DL %u", who, subframe, fp->N_RB_DL); return -1; }
+  uint16_t reg[56][3];
+  const int ng = oai4g_generate_phich_reg_mapping(fp, reg);
+  if (ng <= 0 || ng > 56) { set_err("%s: no PHICH groups", who); return -1; }
+  uint32_t s;
+  gold_seq_h(((((uint32_t)subframe + 1u) * (fp->Nid_cell + 1u)) << 9) + fp->Nid_cell, &s, 1);
+  static const uint8_t w_neg[4] = {0x0, 0xA, 0xC, 0x6};                 /* bit j: the orthogonal sequence's element j is -1 */
+  for (int g = 0; g < ng; g++)
+    for (uint32_t q = 0; q < 8; q++) {
+      phich_rx_ent_t &e = ent[g * 8 + q];
+      memset(&e, 0, sizeof(e));
+      for (uint32_t i = 0; i < 12; i++) {
+        const uint32_t cs_neg = (s >> i) & 1u, neg = cs_neg ^ ((w_neg[q & 3u] >> (i & 3u)) & 1u);
+        e.neg |= (q < 4 ? neg : neg ^ 1u) << (2 * i);                   /* sequences 4..7: -cs on re */
+        e.neg |= neg << (2 * i + 1);
+      }
+      for (int k = 0; k < 3; k++) {
+        if ((uint32_t)reg[g][k] * 4u + 4u > 8u * fp->N_RB_DL) { set_err("%s: PHICH REG %u outside symbol 0", who, reg[g][k]); return -1; }
+        e.word[k] = (uint16_t)(reg[g][k] * 4u);
+      }
+    }
+  return ng;
+}
+
+extern "C" int oai4g_rx_phich(const oai4g_frame_parms_t *fp, uint8_t subframe, const int32_t *rxdataF_comp,
+                              uint8_t ngroup_PHICH, uint8_t nseq_PHICH, int16_t *HI16)
+{
+  std::vector<phich_rx_ent_t> ent(56 * 8);
+  const int ng = phich_rx_table("rx_phich", fp, subframe, ent.data());
+  if (ng < 0) return -1;
+  if (ngroup_PHICH >= ng || nseq_PHICH > 7 || !rxdataF_comp) { set_err("rx_phich: group %u / seq %u or a null plane", ngroup_PHICH, nseq_PHICH); return -1; }
+  NEED_INIT(-1);
+  const size_t cb = (size_t)8 * fp->N_RB_DL * 4;                       /* the packed symbol 0 */
+  stage_t st("rx_phich");
+  const int r_comp = st.add(cb), r_tab = st.add((size_t)ng * 8 * sizeof(phich_rx_ent_t));
+  const int r_it = st.add(sizeof(oai4g_phich_rx_item_t)), r_out = st.add(sizeof(oai4g_phich_rx_out_t));
+  if (!st.open()) return -1;
+  oai4g_phich_rx_item_t it = {};
+  it.ngroup = ngroup_PHICH;
+  it.nseq = nseq_PHICH;
+  HCK(st.up(r_comp, rxdataF_comp, cb), -1);
+  HCK(st.up(r_tab, ent.data(), (size_t)ng * 8 * sizeof(phich_rx_ent_t)), -1);
+  HCK(st.up(r_it, &it, sizeof(it)), -1);
+  phich_rx_args_t a;
+  memset(&a, 0, sizeof(a));
+  a.comp = st.ptr<const int32_t>(r_comp);
+  a.tab = st.ptr<const phich_rx_ent_t>(r_tab);                          /* the one row of this subframe index: slot 0 of a batch from 0 */
+  a.ngroup = (uint32_t)ng;
+  a.n_sf = 1;
+  a.items = st.ptr<const oai4g_phich_rx_item_t>(r_it);
+  a.n_items = 1;
+  a.out = st.ptr<oai4g_phich_rx_out_t>(r_out);
+  HCK(oai4g_launch_phich_rx(a, g_scr.s), -1);
+  oai4g_phich_rx_out_t o = {};
+  HCK(st.down(&o, r_out, sizeof(o)), -1);
+  HCK(st.sync(), -1);
+  if (o.nack > 1) { set_err("rx_phich: the item was refused on the device"); return -1; }
+  if (HI16) *HI16 = o.HI16;
+  return o.nack;
+}
+
+struct oai4g_phich_rx_config {
+  oai4g_frame_parms_t fp;
+  uint32_t ngroup, first_sf, sf_step;
+  dev_buf<phich_rx_ent_t> tab;   /* [10][ngroup][8] */
+};
+
+extern "C" oai4g_phich_rx_config_t *oai4g_phich_rx_config_create(const oai4g_frame_parms_t *fp, uint8_t first_subframe,
+                                                                 uint8_t subframe_step)
+{
+  if (first_subframe > 9 || subframe_step > 9) { set_err("phich_rx_config_create: subframe %u / step %u", first_subframe, subframe_step); return nullptr; }
+  std::vector<phich_rx_ent_t> one(56 * 8), all;
+  int ng = 0;
+  for (uint32_t sf = 0; sf < 10; sf++) {
+    ng = phich_rx_table("phich_rx_config_create", fp, sf, one.data());
+    if (ng < 0) return nullptr;
+    all.insert(all.end(), one.begin(), one.begin() + ng * 8);
+  }
+  NEED_INIT(nullptr);
+  std::unique_ptr<oai4g_phich_rx_config_t> cfg(new oai4g_phich_rx_config_t);
+  cfg->fp = *fp;
+  cfg->ngroup = (uint32_t)ng;
+  cfg->first_sf = first_subframe;
+  cfg->sf_step = subframe_step;
+  HCK(cfg->tab.upload(all), nullptr);
+  return cfg.release();
+}
+
+extern "C" void oai4g_phich_rx_config_destroy(oai4g_phich_rx_config_t *cfg) { delete cfg; }
+
+extern "C" int oai4g_phich_rx_batch(const oai4g_phich_rx_config_t *cfg, const int32_t *d_comp, int n_sf,
+                                    const oai4g_phich_rx_item_t *d_items, int n_items, oai4g_phich_rx_out_t *d_out, void *stream)
+{
+  if (!cfg || n_sf < 0 || n_items < 0 || (n_items > 0 && (!d_comp || !d_items || !d_out))) {
+    set_err("phich_rx_batch: bad arguments");
+    return -1;
+  }
+  NEED_INIT(-1);
+  phich_rx_args_t a;
+  memset(&a, 0, sizeof(a));
+  a.comp = d_comp;
+  a.comp_stride = (size_t)36 * cfg->fp.N_RB_DL;
+  a.tab = cfg->tab.get();
+  a.ngroup = cfg->ngroup;
+  a.n_sf = (uint32_t)n_sf;
+  a.first_sf = cfg->first_sf;
+  a.sf_step = cfg->sf_step;
+  a.items = d_items;
+  a.n_items = (uint32_t)n_items;
+  a.out = d_out;
+  HCK(oai4g_launch_phich_rx(a, (hipStream_t)stream), -1);
+  return 0;
+}

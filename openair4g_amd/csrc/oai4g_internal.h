@@ -641,6 +641,50 @@ struct pdcch_front_args_t {
 hipError_t oai4g_launch_pdcch_front(const pdcch_front_args_t &a, hipStream_t s);
 /* rx_pcfich alone on a plane 0 in device memory: pcf_word as above, gold the subframe's scrambling word */
 hipError_t oai4g_launch_rx_pcfich(const int32_t *d_comp, const uint32_t pcf_word[4], uint32_t gold, uint8_t *d_out, hipStream_t s);
+
+/* The PBCH receive front end (oai4g_pbch_front.hip: k_pbch_front), one workgroup per subframe, one wave per
+ * PBCH symbol.  Every output pointer may be null. */
+#define OAI4G_PBCH_WORDS 288u    /* rxdataF_comp of the PBCH: four regions of 72 words */
+#define OAI4G_PBCH_SOFT 480u     /* 96 + 96 + 144 + 144 soft bits of one subframe 0 */
+struct pbch_front_args_t {
+  const int32_t *rxF;          /* [n_sf][nb_rx][nsymb][N] */
+  size_t rx_sf_stride, rx_ant_stride;   /* words */
+  const int32_t *est[4];       /* plane (p << 1) + a: [n_sf][nsymb][N]; null where the port was not estimated */
+  size_t est_sf_stride;        /* words */
+  uint32_t N, N_RB, nushift3;
+  uint32_t nb_tx, nb_rx, alamouti, high_speed;
+  uint32_t n_sf;
+  int32_t *comp;               /* [n_sf][288]: plane 0 after combining under `alamouti` */
+  int32_t *planes;             /* [n_sf][4][288]: the compensated planes before MRC */
+  int8_t *llr;                 /* [n_sf][2][480]: the soft bits under SISO and under ALAMOUTI */
+  uint8_t *log2_maxh;          /* [n_sf][4] */
+};
+hipError_t oai4g_launch_pbch_front(const pbch_front_args_t &a, hipStream_t s);
+/* pbch_detection's hypotheses through k_cc_decode: item i holds the two soft-bit rows of subframe i
+ * (e_stride = 2 * 480), job j = 2 frame_mod4 + mimo_mode decodes row j & 1 (its e_off) over E = 480 alone, with
+ * the Gold words of quarter j >> 1 (gold + 15 (j >> 1)); the rest of the reference's 1920-byte buffer is 0 and
+ * adds nothing to the rate-matching sums.  The records are those of pbch_out. */
+struct cc_hyp_args_t : cc_args_t {};
+hipError_t oai4g_launch_cc_decode_hyp(const cc_hyp_args_t &a, hipStream_t s);
+/* the first of the eight records of a subframe whose antenna count is 1 or 2 (initial_sync.c:135-161) */
+hipError_t oai4g_launch_pbch_resolve(const uint8_t *d_rec, uint32_t n_sf, oai4g_pbch_detect_t *d_out, hipStream_t s);
+
+/* rx_phich's correlation (oai4g_pbch_front.hip: k_phich_rx), one lane per item */
+struct phich_rx_ent_t {        /* one (subframe index, group, sequence) */
+  uint32_t neg;                /* bit i: d[i] == -1 (phich.c:1131-1222 on the subframe's scrambling word) */
+  uint16_t word[3];            /* phich_reg[ngroup][quad] * 4 */
+  uint16_t pad;
+};
+struct phich_rx_args_t {
+  const int32_t *comp;         /* [n_sf][comp_stride]: plane 0 as k_pdcch_front writes it */
+  size_t comp_stride;          /* words */
+  const phich_rx_ent_t *tab;   /* [10][ngroup][8] */
+  uint32_t ngroup, n_sf, first_sf, sf_step;
+  const oai4g_phich_rx_item_t *items;
+  uint32_t n_items;
+  oai4g_phich_rx_out_t *out;   /* [n_items] */
+};
+hipError_t oai4g_launch_phich_rx(const phich_rx_args_t &a, hipStream_t s);
 void oai4g_set_error(const char *fmt, ...);
 /* binds the calling thread to the device the library was initialised on (hipSetDevice is per thread) */
 int oai4g_bind_thread(void);

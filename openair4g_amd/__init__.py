@@ -481,6 +481,67 @@ def _ptr(a):
     return ctypes.c_void_p(a.ctypes.data)
 
 
+class _DeviceOwner:
+    """Base of every device-resident class, the one owner of its buffers, handles and child batches.  close()
+    synchronises once, destroys the handles newest first, then frees the buffers newest first, and leaves `cfg`
+    and every `d_*` None; a second close() makes no call, and a half-built object (a constructor raised) closes."""
+    _owned = ()                         # (0 handle / 1 buffer, release, its argument) in order of acquisition
+
+    def _dev(self, nbytes, zero=False):
+        """a device buffer (zero-filled on request) that close() frees: its address, a plain int"""
+        p = self.L.oai4g_dev_alloc(nbytes)
+        _check(bool(p))
+        self._owned += ((1, self.L.oai4g_dev_free, p),)
+        if zero:                        # the fill is complete on return, whichever stream uses the buffer first
+            _check(self.L.oai4g_memset_d(p, 0, nbytes) == 0 and self.L.oai4g_sync() == 0)
+        return p
+
+    def _own(self, handle, destroy=None):
+        """take over a handle with its destroy function, or a child batch: its handles go with ours, then its buffers"""
+        _check(bool(handle))
+        kid = destroy is None
+        self._owned += ((0, handle._release, 0), (1, handle._release, 1)) if kid else ((0, destroy, handle),)
+        return handle
+
+    def _release(self, rank):
+        for r, release, arg in reversed(self._owned):
+            if r == rank:
+                release(arg)
+        if rank:
+            self._owned = ()
+            vars(self).update({k: None for k in vars(self) if k == "cfg" or k.startswith("d_")})
+
+    def close(self):
+        if self._owned:
+            self.L.oai4g_sync()
+            self._release(0)
+            self._release(1)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _put(self, d_ptr, a):
+        """a contiguous host array to a device pointer"""
+        _check(self.L.oai4g_memcpy_h2d(d_ptr, _ptr(a), a.nbytes) == 0)
+
+    def _get(self, d_ptr, shape, dtype):
+        """synchronise, then a device pointer's contents as a new array (a ctypes array for a Structure dtype)"""
+        _check(self.L.oai4g_sync() == 0)
+        struct = isinstance(dtype, type(ctypes.Structure))
+        out = np.empty(shape * ctypes.sizeof(dtype), np.uint8) if struct else np.empty(shape, dtype)
+        _check(self.L.oai4g_memcpy_d2h(_ptr(out), d_ptr, out.nbytes) == 0)
+        return (dtype * shape).from_buffer(out) if struct else out
+
+
 def device_name():
     L = init()
     buf = ctypes.create_string_buffer(256)
@@ -707,55 +768,76 @@ def rx_pdsch_tm56(fp, rxF, est, rb_alloc, Qm, mimo_mode, pmi_alloc, dl_power_off
                     (Qm, mimo_mode, pmi_alloc, dl_power_off, num_pdcch, subframe))
 
 
-class _RxBatchDual:
-    """Device-resident batched demodulation of a two-port mode: the FEP output of nb_rx antennas and the
-    four estimate planes (ports 0 / 1 per antenna), or the pilot rows, to LLRs.  A subclass creates its
-    configuration and names its batch entry points (_pilots None: estimate planes only)."""
-    _batch = _pilots = None
+class _EstPlanes(_DeviceOwner):
+    """The estimate planes of a two-port receiver and their channel estimation, shared by _RxBatchDual,
+    PdcchFrontBatch and PbchFrontBatch: d_est holds four planes [2 p + a][n][nsymb * N] (port p at receive
+    antenna a) of n subframes; the user sets L, fp and nb_rx before _est_setup."""
 
-    def _setup(self, create, fp, rb_alloc, args, n_sf, nb_rx):
-        """create(fp, rb_alloc, *args) is the configuration; then the device buffers of n_sf subframes"""
-        init()
-        self.L = lib()
-        self.cfg = getattr(self.L, create)(ctypes.byref(fp), (ctypes.c_uint32 * 4)(*rb_alloc), *args)
-        _check(bool(self.cfg))
-        self.fp, self.n_sf, self.nb_rx = fp, n_sf, nb_rx
-        self.stride = self.L.oai4g_rx_llr_stride(self.cfg)
-        self.plane = n_sf * fp.symbols_per_tti * fp.ofdm_symbol_size
-        self.d_est = self.L.oai4g_dev_alloc(4 * self.plane * 4)
-        self.d_llr = self.L.oai4g_dev_alloc(n_sf * self.stride * 2)
-        self.d_llr1 = self.d_pil = None
-        _check(bool(self.d_est) and bool(self.d_llr))
-        self._chest = {}
-
-    def llr_count(self, sfi):
-        return self.L.oai4g_rx_llr_count(self.cfg, sfi)
+    def _est_setup(self, n, n_ports):
+        self._n_est, self._n_ports, self._chest = n, n_ports, {}
+        self.plane = n * self.fp.symbols_per_tti * self.fp.ofdm_symbol_size
+        self.d_est = self._dev(4 * self.plane * 4)
 
     def est_plane(self, p, a):
         """device pointer of the estimate plane of port p at receive antenna a"""
         return ctypes.c_void_p(self.d_est + (2 * p + a) * self.plane * 4)
 
+    def upload_estimates(self, est):
+        """est[(p, a)] = int32 [n][nsymb * N]"""
+        for (p, a), v in est.items():
+            v = np.ascontiguousarray(v, dtype=np.int32)
+            assert v.size == self.plane
+            self._put(self.est_plane(p, a), v)
+
+    def estimates(self):
+        """the four planes as they stand on the device: int32 [2 p + a][n][nsymb * N]"""
+        return self._get(self.d_est, (4, self._n_est, self.plane // self._n_est), np.int32)
+
     def _chest_cfgs(self, first_subframe, subframe_step):
-        """the ports' 0 / 1 estimation configurations (element stride nb_rx subframes), cached"""
+        """the ports' estimation configurations (element stride nb_rx subframes), created once and owned"""
         key = (first_subframe, subframe_step)
         if key not in self._chest:
             cfgs = []
-            for p in (0, 1):
-                cfg = self.L.oai4g_chest_config_create(ctypes.byref(self.fp), p, first_subframe, subframe_step)
-                _check(bool(cfg))
-                cfgs.append(cfg)
-                _check(self.L.oai4g_chest_config_set_stride(cfg, self.nb_rx, self.nb_rx) == 0)
+            for p in range(self._n_ports):
+                cfgs.append(self._own(self.L.oai4g_chest_config_create(ctypes.byref(self.fp), p, *key),
+                                      self.L.oai4g_chest_config_destroy))
+                _check(self.L.oai4g_chest_config_set_stride(cfgs[p], self.nb_rx, self.nb_rx) == 0)
             self._chest[key] = cfgs
         return self._chest[key]
 
-    def estimate(self, d_rxF, first_subframe=0, subframe_step=1, stream=None):
-        """The four channel-estimation batches over the FEP output [n_sf + 1][nb_rx][nsymb][N]
-        (the extra element's symbol 0 closes the last subframe's rows 12 / 13)."""
-        N, nsymb = self.fp.ofdm_symbol_size, self.fp.symbols_per_tti
+    def _estimate(self, batch, d_rxF, d_planes, plane, first_subframe, subframe_step, stream):
+        """batch (oai4g_chest_batch or _pilots) per (port, antenna) over the FEP output [n + 1][nb_rx][nsymb][N]
+        (the extra element's symbol 0 closes the last subframe's rows 12 / 13) into d_planes [2 p + a][plane]"""
+        grid = self.fp.symbols_per_tti * self.fp.ofdm_symbol_size
         for p, cfg in enumerate(self._chest_cfgs(first_subframe, subframe_step)):
             for a in range(self.nb_rx):
-                _check(self.L.oai4g_chest_batch(cfg, self.n_sf, ctypes.c_void_p(d_rxF + a * nsymb * N * 4),
-                                                self.est_plane(p, a), stream) == 0)
+                _check(batch(cfg, self._n_est, ctypes.c_void_p(d_rxF + a * grid * 4),
+                             ctypes.c_void_p(d_planes + (2 * p + a) * plane * 4), stream) == 0)
+
+
+class _RxBatchDual(_EstPlanes):
+    """Device-resident batched demodulation of a two-port mode: the FEP output of nb_rx antennas and the
+    four estimate planes (ports 0 / 1 per antenna, the shared code of _EstPlanes), or the pilot rows, to LLRs.
+    A subclass creates its configuration and names its batch entry points (_pilots None: estimate planes only)."""
+    _batch = _pilots = None
+
+    def _setup(self, create, fp, rb_alloc, args, n_sf, nb_rx):
+        """create(fp, rb_alloc, *args) is the configuration; then the device buffers of n_sf subframes"""
+        self.L = init()
+        self.cfg = self._own(getattr(self.L, create)(ctypes.byref(fp), (ctypes.c_uint32 * 4)(*rb_alloc), *args),
+                             self.L.oai4g_rx_config_destroy)
+        self.fp, self.n_sf, self.nb_rx = fp, n_sf, nb_rx
+        self.stride = self.L.oai4g_rx_llr_stride(self.cfg)
+        self._est_setup(n_sf, 2)
+        self.d_llr = self._dev(n_sf * self.stride * 2)
+        self.d_llr1 = self.d_pil = None
+
+    def llr_count(self, sfi):
+        return self.L.oai4g_rx_llr_count(self.cfg, sfi)
+
+    def estimate(self, d_rxF, first_subframe=0, subframe_step=1, stream=None):
+        """The four channel-estimation batches over the FEP output [n_sf + 1][nb_rx][nsymb][N]."""
+        self._estimate(self.L.oai4g_chest_batch, d_rxF, self.d_est, self.plane, first_subframe, subframe_step, stream)
 
     def launch(self, d_rxF, unscramble=1, stream=None):
         _check(getattr(self.L, self._batch)(self.cfg, self.n_sf, d_rxF, self.d_est, self.d_llr, unscramble, stream) == 0)
@@ -763,25 +845,18 @@ class _RxBatchDual:
     def _pil(self):
         if not self.d_pil:
             self.pil_plane = self.n_sf * 4 * self.fp.ofdm_symbol_size * 2
-            self.d_pil = self.L.oai4g_dev_alloc(4 * self.pil_plane * 4)
-            _check(bool(self.d_pil))
+            self.d_pil = self._dev(4 * self.pil_plane * 4)
         return self.d_pil
 
     def _llr1(self):
         if not self.d_llr1:
-            self.d_llr1 = self.L.oai4g_dev_alloc(self.n_sf * self.stride * 2)
-            _check(bool(self.d_llr1))
+            self.d_llr1 = self._dev(self.n_sf * self.stride * 2)
         return self.d_llr1
 
     def estimate_pilots(self, d_rxF, first_subframe=0, subframe_step=1, stream=None):
         """The four pilot-row estimations (oai4g_chest_batch_pilots): 5 rows per subframe instead of 14."""
-        N, nsymb = self.fp.ofdm_symbol_size, self.fp.symbols_per_tti
-        d_pil = self._pil()
-        for p, cfg in enumerate(self._chest_cfgs(first_subframe, subframe_step)):
-            for a in range(self.nb_rx):
-                _check(self.L.oai4g_chest_batch_pilots(cfg, self.n_sf, ctypes.c_void_p(d_rxF + a * nsymb * N * 4),
-                                                       ctypes.c_void_p(d_pil + (2 * p + a) * self.pil_plane * 4),
-                                                       stream) == 0)
+        self._estimate(self.L.oai4g_chest_batch_pilots, d_rxF, self._pil(), self.pil_plane, first_subframe,
+                       subframe_step, stream)
 
     def launch_pilots(self, d_rxF, unscramble=1, stream=None):
         """the demodulation from the pilot rows (estimate_pilots)"""
@@ -789,32 +864,8 @@ class _RxBatchDual:
             raise RuntimeError(f"{type(self).__name__} demodulates from the estimate planes only")
         _check(getattr(self.L, self._pilots)(self.cfg, self.n_sf, d_rxF, self._pil(), self.d_llr, unscramble, stream) == 0)
 
-    def _download(self, ptr):
-        _check(self.L.oai4g_sync() == 0)
-        out = np.empty((self.n_sf, self.stride), dtype=np.int16)
-        _check(self.L.oai4g_memcpy_d2h(_ptr(out), ptr, out.nbytes) == 0)
-        return out
-
     def llrs(self):
-        return self._download(self.d_llr)
-
-    def estimates(self):
-        _check(self.L.oai4g_sync() == 0)
-        out = np.empty((4, self.n_sf, self.plane // self.n_sf), dtype=np.int32)
-        _check(self.L.oai4g_memcpy_d2h(_ptr(out), self.d_est, out.nbytes) == 0)
-        return out
-
-    def close(self):
-        self.L.oai4g_sync()
-        for cfgs in self._chest.values():
-            for cfg in cfgs:
-                self.L.oai4g_chest_config_destroy(cfg)
-        self._chest = {}
-        for ptr in (self.d_est, self.d_llr, self.d_llr1, self.d_pil):
-            if ptr:
-                self.L.oai4g_dev_free(ptr)
-        self.d_llr1 = self.d_pil = None
-        self.L.oai4g_rx_config_destroy(self.cfg)
+        return self._get(self.d_llr, (self.n_sf, self.stride), np.int16)
 
 
 class RxBatchTM3(_RxBatchDual):
@@ -837,7 +888,7 @@ class RxBatchTM3(_RxBatchDual):
                                              unscramble, stream) == 0)
 
     def llrs1(self):
-        return self._download(self.d_llr1)
+        return self._get(self.d_llr1, (self.n_sf, self.stride), np.int16)
 
 
 class RxBatchTM2(_RxBatchDual):
@@ -925,19 +976,24 @@ def chest_filters(k):
     return out
 
 
-class ChestBatch:
+class _Scratch(_DeviceOwner):
+    """a short-lived owner of one call's temporaries: `with _Scratch(L) as t` frees them when the call raises too"""
+
+    def __init__(self, L):
+        self.L = L
+
+
+class ChestBatch(_DeviceOwner):
     """Device-resident batched channel estimation (oai4g_chest_batch) of n_sf consecutive subframes."""
 
     def __init__(self, fp, n_sf, p=0, first_subframe=0, subframe_step=1):
-        init()
-        self.L = lib()
-        self.cfg = self.L.oai4g_chest_config_create(ctypes.byref(fp), p, first_subframe, subframe_step)
-        _check(bool(self.cfg))
+        self.L = init()
+        self.cfg = self._own(self.L.oai4g_chest_config_create(ctypes.byref(fp), p, first_subframe, subframe_step),
+                             self.L.oai4g_chest_config_destroy)
         self.fp, self.n_sf = fp, n_sf
         self.n_grid = n_sf * fp.symbols_per_tti * fp.ofdm_symbol_size
-        self.d_rx = self.L.oai4g_dev_alloc((self.n_grid + fp.ofdm_symbol_size) * 4)
-        self.d_est = self.L.oai4g_dev_alloc(self.n_grid * 4)
-        _check(bool(self.d_rx) and bool(self.d_est))
+        self.d_rx = self._dev((self.n_grid + fp.ofdm_symbol_size) * 4)
+        self.d_est = self._dev(self.n_grid * 4)
 
     def run(self, rxdataF, next_symbol0, d_rxdataF=None):
         """rxdataF [n_sf][nsymb*N] and the N words of the following subframe's symbol 0."""
@@ -945,12 +1001,9 @@ class ChestBatch:
             y = np.concatenate([np.ascontiguousarray(rxdataF, dtype=np.int32).ravel(),
                                 np.ascontiguousarray(next_symbol0, dtype=np.int32).ravel()])
             assert y.size == self.n_grid + self.fp.ofdm_symbol_size
-            _check(self.L.oai4g_memcpy_h2d(self.d_rx, _ptr(y), y.nbytes) == 0)
+            self._put(self.d_rx, y)
         self.launch(d_rxdataF or self.d_rx)
-        _check(self.L.oai4g_sync() == 0)
-        out = np.empty((self.n_sf, self.n_grid // self.n_sf), dtype=np.int32)
-        _check(self.L.oai4g_memcpy_d2h(_ptr(out), self.d_est, out.nbytes) == 0)
-        return out
+        return self._get(self.d_est, (self.n_sf, self.n_grid // self.n_sf), np.int32)
 
     def launch(self, d_rxdataF, stream=None):
         """Device-only: estimates of d_rxdataF (n_sf grids + the next symbol 0) into self.d_est."""
@@ -959,70 +1012,45 @@ class ChestBatch:
     def time_estimates(self, stream=None):
         """dl_ch_estimates_time of every subframe's estimate plane in self.d_est: [n_sf][N] int32."""
         N, stride = self.fp.ofdm_symbol_size, self.n_grid // self.n_sf
-        d_t = self.L.oai4g_dev_alloc(self.n_sf * N * 4)
-        _check(bool(d_t))
-        try:
+        with _Scratch(self.L) as t:
+            d_t = t._dev(self.n_sf * N * 4)
             _check(self.L.oai4g_chest_time_batch(ctypes.byref(self.fp), self.n_sf, self.d_est, stride, d_t, N,
                                                  stream) == 0)
-            _check(self.L.oai4g_sync() == 0)
-            out = np.empty((self.n_sf, N), dtype=np.int32)
-            _check(self.L.oai4g_memcpy_d2h(_ptr(out), d_t, out.nbytes) == 0)
-        finally:
-            self.L.oai4g_dev_free(d_t)
-        return out
+            return t._get(d_t, (self.n_sf, N), np.int32)
 
     def freq_offset_omegas(self, l, stream=None):
         """lte_est_freq_offset's integer part (omega, re | im << 16) of every subframe's plane."""
-        d_o = self.L.oai4g_dev_alloc(max(4, self.n_sf * 4))
-        _check(bool(d_o))
-        try:
+        with _Scratch(self.L) as t:
+            d_o = t._dev(max(4, self.n_sf * 4))
             _check(self.L.oai4g_freq_offset_omega_batch(ctypes.byref(self.fp), self.n_sf, self.d_est,
                                                         self.n_grid // self.n_sf, l, d_o, stream) == 0)
-            _check(self.L.oai4g_sync() == 0)
-            out = np.empty(self.n_sf, dtype=np.int32)
-            _check(self.L.oai4g_memcpy_d2h(_ptr(out), d_o, out.nbytes) == 0)
-        finally:
-            self.L.oai4g_dev_free(d_o)
-        return out
-
-    def close(self):
-        self.L.oai4g_dev_free(self.d_rx)
-        self.L.oai4g_dev_free(self.d_est)
-        self.L.oai4g_chest_config_destroy(self.cfg)
+            return t._get(d_o, self.n_sf, np.int32)
 
 
-class RxBatch:
+class RxBatch(_DeviceOwner):
     """Device-resident batched PDSCH demodulation (oai4g_rx_batch)."""
 
     def __init__(self, fp, rb_alloc, Qm, num_pdcch, rnti, n_sf, first_subframe=0, subframe_step=1):
-        init()
-        self.L = lib()
+        self.L = init()
         ra = (ctypes.c_uint32 * 4)(*rb_alloc)
-        self.cfg = self.L.oai4g_rx_config_create(ctypes.byref(fp), ra, Qm, num_pdcch, rnti, first_subframe,
-                                                 subframe_step)
-        _check(bool(self.cfg))
+        self.cfg = self._own(self.L.oai4g_rx_config_create(ctypes.byref(fp), ra, Qm, num_pdcch, rnti, first_subframe,
+                                                           subframe_step), self.L.oai4g_rx_config_destroy)
         self.fp, self.n_sf = fp, n_sf
         self.stride = self.L.oai4g_rx_llr_stride(self.cfg)
         n_in = n_sf * fp.symbols_per_tti * fp.ofdm_symbol_size
-        self.d_y = self.L.oai4g_dev_alloc(n_in * 4)
-        self.d_h = self.L.oai4g_dev_alloc(n_in * 4)
-        self.d_llr = self.L.oai4g_dev_alloc(n_sf * self.stride * 2)
-        _check(bool(self.d_y) and bool(self.d_h) and bool(self.d_llr))
+        self.d_y = self._dev(n_in * 4)
+        self.d_h = self._dev(n_in * 4)
+        self.d_llr = self._dev(n_sf * self.stride * 2)
 
     def llr_count(self, sfi):
         return self.L.oai4g_rx_llr_count(self.cfg, sfi)
 
     def run(self, rxdataF, dl_ch, unscramble=1, d_rxdataF=None):
         if d_rxdataF is None:
-            y = np.ascontiguousarray(rxdataF, dtype=np.int32)
-            _check(self.L.oai4g_memcpy_h2d(self.d_y, _ptr(y), y.nbytes) == 0)
-        h = np.ascontiguousarray(dl_ch, dtype=np.int32)
-        _check(self.L.oai4g_memcpy_h2d(self.d_h, _ptr(h), h.nbytes) == 0)
+            self._put(self.d_y, np.ascontiguousarray(rxdataF, dtype=np.int32))
+        self._put(self.d_h, np.ascontiguousarray(dl_ch, dtype=np.int32))
         self.launch(d_rxdataF or self.d_y, self.d_h, unscramble)
-        _check(self.L.oai4g_sync() == 0)
-        out = np.empty((self.n_sf, self.stride), dtype=np.int16)
-        _check(self.L.oai4g_memcpy_d2h(_ptr(out), self.d_llr, out.nbytes) == 0)
-        return out
+        return self.llrs()
 
     def launch_estimated(self, chest, d_rxdataF, unscramble=1, stream=None):
         """Device-only, fused with the channel estimation of `chest` (a ChestBatch of the same
@@ -1031,52 +1059,35 @@ class RxBatch:
                                                stream) == 0)
 
     def llrs(self):
-        _check(self.L.oai4g_sync() == 0)
-        out = np.empty((self.n_sf, self.stride), dtype=np.int16)
-        _check(self.L.oai4g_memcpy_d2h(_ptr(out), self.d_llr, out.nbytes) == 0)
-        return out
+        return self._get(self.d_llr, (self.n_sf, self.stride), np.int16)
 
     def launch(self, d_rxdataF, d_est, unscramble=1, stream=None):
         """Device-only: LLRs of d_rxdataF / d_est into self.d_llr."""
         _check(self.L.oai4g_rx_batch(self.cfg, self.n_sf, d_rxdataF, d_est, self.d_llr, unscramble, stream) == 0)
 
-    def close(self):
-        for p in (self.d_y, self.d_h, self.d_llr):
-            self.L.oai4g_dev_free(p)
-        self.L.oai4g_rx_config_destroy(self.cfg)
 
-
-class FepBatch:
+class FepBatch(_DeviceOwner):
     """Device-resident batched FEP (oai4g_fep_batch): n_sf subframes x n_ant antennas."""
 
     def __init__(self, fp, n_sf, n_ant):
-        init()
-        self.L = lib()
+        self.L = init()
         self.fp, self.n_sf, self.n_ant = fp, n_sf, n_ant
         self.n_in = n_sf * n_ant * fp.samples_per_tti
         self.n_out = n_sf * n_ant * fp.symbols_per_tti * fp.ofdm_symbol_size
-        self.d_rx = self.L.oai4g_dev_alloc(self.n_in * 4)
-        self.d_rxF = self.L.oai4g_dev_alloc(self.n_out * 4)
-        _check(bool(self.d_rx) and bool(self.d_rxF))
+        self.d_rx = self._dev(self.n_in * 4)
+        self.d_rxF = self._dev(self.n_out * 4)
 
     def upload(self, rx):
         rx = np.ascontiguousarray(rx, dtype=np.int32)
         assert rx.size == self.n_in
-        _check(self.L.oai4g_memcpy_h2d(self.d_rx, _ptr(rx), rx.nbytes) == 0)
+        self._put(self.d_rx, rx)
 
     def run(self, stream=None):
         _check(self.L.oai4g_fep_batch(ctypes.byref(self.fp), self.n_sf, self.n_ant, self.d_rx, self.d_rxF,
                                       stream) == 0)
 
     def result(self):
-        _check(self.L.oai4g_sync() == 0)
-        out = np.empty((self.n_sf, self.n_ant, self.fp.symbols_per_tti, self.fp.ofdm_symbol_size), dtype=np.int32)
-        _check(self.L.oai4g_memcpy_d2h(_ptr(out), self.d_rxF, out.nbytes) == 0)
-        return out
-
-    def close(self):
-        self.L.oai4g_dev_free(self.d_rx)
-        self.L.oai4g_dev_free(self.d_rxF)
+        return self._get(self.d_rxF, (self.n_sf, self.n_ant, self.fp.symbols_per_tti, self.fp.ofdm_symbol_size), np.int32)
 
 
 def ofdm_mod(grid, log2n, nb_symbols, cp):
@@ -1192,23 +1203,19 @@ def pbch_decode(llr, fp, frame_mod4):
     return r, bytes(out)
 
 
-class PbchDecodeBatch:
+class PbchDecodeBatch(_DeviceOwner):
     """Device-resident batch of n PBCH decodes (oai4g_pbch_decode_batch)."""
 
     def __init__(self, fp, n):
-        init()
-        self.L, self.fp, self.n = lib(), fp, n
+        self.L, self.fp, self.n = init(), fp, n
         self.E = 1920 if fp.Ncp == 0 else 1728
-        self.d_llr = self.L.oai4g_dev_alloc(n * self.E)
-        self.d_q = self.L.oai4g_dev_alloc(n)
-        self.d_out = self.L.oai4g_dev_alloc(4 * n)
-        _check(all(bool(p) for p in (self.d_llr, self.d_q, self.d_out)))
+        self.d_llr = self._dev(n * self.E)
+        self.d_q = self._dev(n)
+        self.d_out = self._dev(4 * n)
 
     def upload(self, llr, frame_mod4):
-        llr = np.ascontiguousarray(llr, dtype=np.int8).reshape(self.n, self.E)
-        q = np.ascontiguousarray(frame_mod4, dtype=np.uint8).reshape(self.n)
-        _check(self.L.oai4g_memcpy_h2d(self.d_llr, _ptr(llr), llr.nbytes) == 0)
-        _check(self.L.oai4g_memcpy_h2d(self.d_q, _ptr(q), q.nbytes) == 0)
+        self._put(self.d_llr, np.ascontiguousarray(llr, dtype=np.int8).reshape(self.n, self.E))
+        self._put(self.d_q, np.ascontiguousarray(frame_mod4, dtype=np.uint8).reshape(self.n))
 
     def launch(self, stream=None):
         _check(self.L.oai4g_pbch_decode_batch(self.d_llr, self.n, ctypes.byref(self.fp), self.d_q, self.d_out,
@@ -1216,16 +1223,10 @@ class PbchDecodeBatch:
 
     def results(self):
         """(antenna counts int16[n] with -1 for none, MIB bytes uint8[n][3])"""
-        _check(self.L.oai4g_sync() == 0)
-        out = np.empty((self.n, 4), dtype=np.uint8)
-        _check(self.L.oai4g_memcpy_d2h(_ptr(out), self.d_out, out.nbytes) == 0)
+        out = self._get(self.d_out, (self.n, 4), np.uint8)
         cnt = out[:, 3].astype(np.int16)
         cnt[cnt == 0xFF] = -1
         return cnt, out[:, :3].copy()
-
-    def close(self):
-        for p in (self.d_llr, self.d_q, self.d_out):
-            self.L.oai4g_dev_free(p)
 
 
 def pdcch_soft_bit_table(fp, subframe, num_pdcch):
@@ -1290,20 +1291,18 @@ def dci_decoding_procedure0(state, e_rx, num_pdcch, crnti, do_common, subframe, 
         ctypes.addressof(st.maps[1]), ctypes.addressof(st.maps[2])) == 0)
 
 
-class PdcchRxBatch:
+class PdcchRxBatch(_DeviceOwner):
     """Device-resident DCI search over n_sf subframes (oai4g_pdcch_rx_config_create / oai4g_pdcch_rx_batch).
     plan: a list of (do_common, L, sizeof_bits, sizeof_bytes, format_si, format_ra, format_c, stop_if_found)."""
 
     def __init__(self, fp, num_pdcch, crnti, si_rnti, ra_rnti, plan, n_sf):
-        init()
-        self.L, self.fp, self.n_sf, self.num_pdcch = lib(), fp, n_sf, num_pdcch
+        self.L, self.fp, self.n_sf, self.num_pdcch = init(), fp, n_sf, num_pdcch
         arr = (PdcchPlan * len(plan))(*[PdcchPlan(*p) for p in plan])
-        self.cfg = self.L.oai4g_pdcch_rx_config_create(ctypes.byref(fp), num_pdcch, crnti, si_rnti, ra_rnti, arr, len(plan))
-        _check(bool(self.cfg))
+        self.cfg = self._own(self.L.oai4g_pdcch_rx_config_create(ctypes.byref(fp), num_pdcch, crnti, si_rnti, ra_rnti,
+                                                                 arr, len(plan)), self.L.oai4g_pdcch_rx_config_destroy)
         self.comp_words = num_pdcch * 12 * fp.N_RB_DL
-        self.d_comp = self.L.oai4g_dev_alloc(n_sf * self.comp_words * 4)
-        self.d_out = self.L.oai4g_dev_alloc(n_sf * ctypes.sizeof(PdcchRxResult))
-        _check(bool(self.d_comp) and bool(self.d_out))
+        self.d_comp = self._dev(n_sf * self.comp_words * 4)
+        self.d_out = self._dev(n_sf * ctypes.sizeof(PdcchRxResult))
 
     def candidates(self, subframe):
         """[(CCEind, plan entry)] of a subframe index, in plan order"""
@@ -1314,24 +1313,13 @@ class PdcchRxBatch:
         return list(zip(cce[:n].tolist(), pe[:n].tolist()))
 
     def upload(self, comp):
-        comp = np.ascontiguousarray(comp, dtype=np.int32).reshape(self.n_sf, self.comp_words)
-        _check(self.L.oai4g_memcpy_h2d(self.d_comp, _ptr(comp), comp.nbytes) == 0)
+        self._put(self.d_comp, np.ascontiguousarray(comp, dtype=np.int32).reshape(self.n_sf, self.comp_words))
 
     def launch(self, first_subframe=0, stream=None):
         _check(self.L.oai4g_pdcch_rx_batch(self.cfg, self.d_comp, self.n_sf, first_subframe, self.d_out, stream) == 0)
 
     def results(self):
-        _check(self.L.oai4g_sync() == 0)
-        out = (PdcchRxResult * self.n_sf)()
-        _check(self.L.oai4g_memcpy_d2h(ctypes.addressof(out), self.d_out, ctypes.sizeof(out)) == 0)
-        return out
-
-    def close(self):
-        if self.cfg:
-            self.L.oai4g_pdcch_rx_config_destroy(self.cfg)
-            self.L.oai4g_dev_free(self.d_comp)
-            self.L.oai4g_dev_free(self.d_out)
-            self.cfg = None
+        return self._get(self.d_out, self.n_sf, PdcchRxResult)
 
 
 def _front_planes(fp, nb_rx, rxdataF, est):
@@ -1380,51 +1368,27 @@ def rx_pdcch(fp, rxdataF, est, subframe, mimo_mode, high_speed_flag=1):
     return e[:cnt].copy(), n.value
 
 
-class PdcchFrontBatch:
+class PdcchFrontBatch(_EstPlanes):
     """Device-resident control front end of n_sf subframes (oai4g_pdcch_front_batch): the FEP output
     [n_sf (+ 1)][nb_rx][nsymb][N] and the estimate planes of ports x antennas -> d_comp [n_sf][36 N_RB_DL],
     d_cfi [n_sf], d_log2_maxh [n_sf].  estimate() runs the oai4g_chest_batch of every plane into the object's
-    own buffers; launch() takes them or the caller's."""
+    own buffers; launch() takes them or the caller's.  The planes and their estimation are _EstPlanes'."""
 
     def __init__(self, fp, n_sf, nb_rx, mimo_mode, high_speed_flag=1, first_subframe=0, subframe_step=1):
-        init()
-        self.L, self.fp, self.n_sf, self.nb_rx = lib(), fp, n_sf, nb_rx
+        self.L, self.fp, self.n_sf, self.nb_rx = init(), fp, n_sf, nb_rx
         self.first, self.step = first_subframe, subframe_step
-        self.cfg = self.L.oai4g_pdcch_front_config_create(ctypes.byref(fp), nb_rx, mimo_mode, high_speed_flag,
-                                                          first_subframe, subframe_step)
-        _check(bool(self.cfg))
+        self.cfg = self._own(self.L.oai4g_pdcch_front_config_create(ctypes.byref(fp), nb_rx, mimo_mode, high_speed_flag,
+                                                                    first_subframe, subframe_step),
+                             self.L.oai4g_pdcch_front_config_destroy)
         self.words = 36 * fp.N_RB_DL
-        self.plane = n_sf * fp.symbols_per_tti * fp.ofdm_symbol_size
-        self.d_est = self.L.oai4g_dev_alloc(4 * self.plane * 4)
-        self.d_comp = self.L.oai4g_dev_alloc(n_sf * self.words * 4)
-        self.d_cfi = self.L.oai4g_dev_alloc(max(4, n_sf))
-        self.d_log2 = self.L.oai4g_dev_alloc(max(4, n_sf))
-        _check(bool(self.d_est) and bool(self.d_comp) and bool(self.d_cfi) and bool(self.d_log2))
-        self._chest = []
-
-    def est_plane(self, p, a):
-        return ctypes.c_void_p(self.d_est + (2 * p + a) * self.plane * 4)
-
-    def upload_estimates(self, est):
-        """est[(p, a)] = int32 [n_sf][nsymb * N]"""
-        for (p, a), v in est.items():
-            v = np.ascontiguousarray(v, dtype=np.int32)
-            assert v.size == self.plane
-            _check(self.L.oai4g_memcpy_h2d(self.est_plane(p, a), _ptr(v), v.nbytes) == 0)
+        self._est_setup(n_sf, fp.nb_antennas_tx_eNB)
+        self.d_comp = self._dev(n_sf * self.words * 4)
+        self.d_cfi = self._dev(max(4, n_sf))
+        self.d_log2 = self._dev(max(4, n_sf))
 
     def estimate(self, d_rxF, stream=None):
         """oai4g_chest_batch per (port, antenna) over the FEP output [n_sf + 1][nb_rx][nsymb][N]"""
-        if not self._chest:
-            for p in range(self.fp.nb_antennas_tx_eNB):
-                cfg = self.L.oai4g_chest_config_create(ctypes.byref(self.fp), p, self.first, self.step)
-                _check(bool(cfg))
-                self._chest.append(cfg)
-                _check(self.L.oai4g_chest_config_set_stride(cfg, self.nb_rx, self.nb_rx) == 0)
-        grid = self.fp.symbols_per_tti * self.fp.ofdm_symbol_size
-        for p, cfg in enumerate(self._chest):
-            for a in range(self.nb_rx):
-                _check(self.L.oai4g_chest_batch(cfg, self.n_sf, ctypes.c_void_p(d_rxF + a * grid * 4), self.est_plane(p, a),
-                                                stream) == 0)
+        self._estimate(self.L.oai4g_chest_batch, d_rxF, self.d_est, self.plane, self.first, self.step, stream)
 
     def launch(self, d_rxF, stream=None):
         ep = (ctypes.c_void_p * 4)(*[self.est_plane(i >> 1, i & 1).value for i in range(4)])
@@ -1433,34 +1397,18 @@ class PdcchFrontBatch:
 
     def results(self):
         """(comp int32 [n_sf][36 N_RB_DL], cfi uint8 [n_sf], log2_maxh uint8 [n_sf])"""
-        _check(self.L.oai4g_sync() == 0)
-        comp = np.empty((self.n_sf, self.words), dtype=np.int32)
-        cfi, l2 = np.empty(self.n_sf, dtype=np.uint8), np.empty(self.n_sf, dtype=np.uint8)
-        _check(self.L.oai4g_memcpy_d2h(_ptr(comp), self.d_comp, comp.nbytes) == 0)
-        _check(self.L.oai4g_memcpy_d2h(_ptr(cfi), self.d_cfi, cfi.nbytes) == 0)
-        _check(self.L.oai4g_memcpy_d2h(_ptr(l2), self.d_log2, l2.nbytes) == 0)
-        return comp, cfi, l2
-
-    def close(self):
-        if self.cfg:
-            self.L.oai4g_sync()
-            for cfg in self._chest:
-                self.L.oai4g_chest_config_destroy(cfg)
-            for ptr in (self.d_est, self.d_comp, self.d_cfi, self.d_log2):
-                self.L.oai4g_dev_free(ptr)
-            self.L.oai4g_pdcch_front_config_destroy(self.cfg)
-            self.cfg = None
+        return (self._get(self.d_comp, (self.n_sf, self.words), np.int32), self._get(self.d_cfi, self.n_sf, np.uint8),
+                self._get(self.d_log2, self.n_sf, np.uint8))
 
 
-class PdcchRxBatchDetected:
+class PdcchRxBatchDetected(_DeviceOwner):
     """The DCI search behind PdcchFrontBatch (oai4g_pdcch_rx_batch_detected): the three configurations of 1, 2
     and 3 control symbols; every subframe is searched under the one its device-resident count selects."""
 
     def __init__(self, fp, crnti, si_rnti, ra_rnti, plan, n_sf):
-        self.by_count = [PdcchRxBatch(fp, n, crnti, si_rnti, ra_rnti, plan, 1) for n in (1, 2, 3)]
-        self.L, self.fp, self.n_sf = lib(), fp, n_sf
-        self.d_out = self.L.oai4g_dev_alloc(n_sf * ctypes.sizeof(PdcchRxResult))
-        _check(bool(self.d_out))
+        self.L, self.fp, self.n_sf = init(), fp, n_sf
+        self.by_count = [self._own(PdcchRxBatch(fp, n, crnti, si_rnti, ra_rnti, plan, 1)) for n in (1, 2, 3)]
+        self.d_out = self._dev(n_sf * ctypes.sizeof(PdcchRxResult))
 
     def launch(self, d_comp, d_cfi, first_subframe=0, subframe_step=1, stream=None):
         cfgs = (ctypes.c_void_p * 3)(*[b.cfg for b in self.by_count])
@@ -1468,18 +1416,7 @@ class PdcchRxBatchDetected:
                                                     self.d_out, stream) == 0)
 
     def results(self):
-        _check(self.L.oai4g_sync() == 0)
-        out = (PdcchRxResult * self.n_sf)()
-        _check(self.L.oai4g_memcpy_d2h(ctypes.addressof(out), self.d_out, ctypes.sizeof(out)) == 0)
-        return out
-
-    def close(self):
-        if self.d_out:
-            self.L.oai4g_sync()
-            for b in self.by_count:
-                b.close()
-            self.L.oai4g_dev_free(self.d_out)
-            self.d_out = None
+        return self._get(self.d_out, self.n_sf, PdcchRxResult)
 
 
 def _pbch_planes(nb_ports, nb_rx, rxdataF, est):
@@ -1523,54 +1460,30 @@ class PbchDetect(ctypes.Structure):
                 ("mib", ctypes.c_uint8 * 3), ("pad", ctypes.c_uint8 * 2)]
 
 
-class PbchFrontBatch:
+class PbchFrontBatch(_EstPlanes):
     """Device-resident PBCH front end and detection of n subframes 0 (oai4g_pbch_front_batch,
     oai4g_pbch_detect_batch): the FEP output [n (+ 1)][nb_rx][nsymb][N] and the estimate planes of ports x antennas
-    -> d_llr [n][2][480], d_log2 [n][4], d_out [n] PbchDetect."""
+    -> d_llr [n][2][480], d_log2 [n][4], d_out [n] PbchDetect.  The planes and their estimation are _EstPlanes'."""
 
     def __init__(self, fp, n, nb_rx, nb_ports, high_speed_flag=1, first_subframe=0, subframe_step=0):
-        init()
-        self.L, self.fp, self.n, self.nb_rx, self.nb_ports = lib(), fp, n, nb_rx, nb_ports
+        self.L, self.fp, self.n, self.nb_rx, self.nb_ports = init(), fp, n, nb_rx, nb_ports
         self.first, self.step = first_subframe, subframe_step
-        self.cfg = self.L.oai4g_pbch_front_config_create(ctypes.byref(fp), nb_rx, nb_ports, high_speed_flag)
-        _check(bool(self.cfg))
-        self.plane = n * fp.symbols_per_tti * fp.ofdm_symbol_size
-        self.d_est = self.L.oai4g_dev_alloc(4 * self.plane * 4)
-        self.d_llr = self.L.oai4g_dev_alloc(n * 960)
-        self.d_log2 = self.L.oai4g_dev_alloc(n * 4)
-        self.d_out = self.L.oai4g_dev_alloc(n * ctypes.sizeof(PbchDetect))
-        _check(all(bool(p) for p in (self.d_est, self.d_llr, self.d_log2, self.d_out)))
-        self._chest = []
-
-    def est_plane(self, p, a):
-        return ctypes.c_void_p(self.d_est + (2 * p + a) * self.plane * 4)
-
-    def upload_estimates(self, est):
-        """est[(p, a)] = int32 [n][nsymb * N]"""
-        for (p, a), v in est.items():
-            v = np.ascontiguousarray(v, dtype=np.int32)
-            assert v.size == self.plane
-            _check(self.L.oai4g_memcpy_h2d(self.est_plane(p, a), _ptr(v), v.nbytes) == 0)
+        self.cfg = self._own(self.L.oai4g_pbch_front_config_create(ctypes.byref(fp), nb_rx, nb_ports, high_speed_flag),
+                             self.L.oai4g_pbch_front_config_destroy)
+        self._est_setup(n, nb_ports)
+        self.d_llr = self._dev(n * 960)
+        self.d_log2 = self._dev(n * 4)
+        self.d_out = self._dev(n * ctypes.sizeof(PbchDetect))
 
     def upload_llr(self, llr):
         """the soft bits themselves, int8 [n][2][480] (the detection alone)"""
         llr = np.ascontiguousarray(llr, dtype=np.int8)
         assert llr.size == self.n * 960
-        _check(self.L.oai4g_memcpy_h2d(self.d_llr, _ptr(llr), llr.nbytes) == 0)
+        self._put(self.d_llr, llr)
 
     def estimate(self, d_rxF, stream=None):
         """oai4g_chest_batch per (port, antenna) over the FEP output [n + 1][nb_rx][nsymb][N]"""
-        if not self._chest:
-            for p in range(self.nb_ports):
-                cfg = self.L.oai4g_chest_config_create(ctypes.byref(self.fp), p, self.first, self.step)
-                _check(bool(cfg))
-                self._chest.append(cfg)
-                _check(self.L.oai4g_chest_config_set_stride(cfg, self.nb_rx, self.nb_rx) == 0)
-        grid = self.fp.symbols_per_tti * self.fp.ofdm_symbol_size
-        for p, cfg in enumerate(self._chest):
-            for a in range(self.nb_rx):
-                _check(self.L.oai4g_chest_batch(cfg, self.n, ctypes.c_void_p(d_rxF + a * grid * 4), self.est_plane(p, a),
-                                                stream) == 0)
+        self._estimate(self.L.oai4g_chest_batch, d_rxF, self.d_est, self.plane, self.first, self.step, stream)
 
     def launch(self, d_rxF, stream=None):
         ep = (ctypes.c_void_p * 4)(*[self.est_plane(i >> 1, i & 1).value for i in range(4)])
@@ -1581,38 +1494,15 @@ class PbchFrontBatch:
 
     def results(self):
         """(llr int8 [n][2][480], log2_maxh uint8 [n][4])"""
-        _check(self.L.oai4g_sync() == 0)
-        llr, l2 = np.empty((self.n, 2, 480), dtype=np.int8), np.empty((self.n, 4), dtype=np.uint8)
-        _check(self.L.oai4g_memcpy_d2h(_ptr(llr), self.d_llr, llr.nbytes) == 0)
-        _check(self.L.oai4g_memcpy_d2h(_ptr(l2), self.d_log2, l2.nbytes) == 0)
-        return llr, l2
+        return self._get(self.d_llr, (self.n, 2, 480), np.int8), self._get(self.d_log2, (self.n, 4), np.uint8)
 
     def estimates(self):
         """est[(p, a)] = int32 [n][nsymb * N] as they stand on the device"""
-        _check(self.L.oai4g_sync() == 0)
-        est = {}
-        for p in range(self.nb_ports):
-            for a in range(self.nb_rx):
-                v = np.empty((self.n, self.plane // self.n), dtype=np.int32)
-                _check(self.L.oai4g_memcpy_d2h(_ptr(v), self.est_plane(p, a), v.nbytes) == 0)
-                est[(p, a)] = v
-        return est
+        planes = super().estimates()
+        return {(p, a): planes[2 * p + a] for p in range(self.nb_ports) for a in range(self.nb_rx)}
 
     def detected(self):
-        _check(self.L.oai4g_sync() == 0)
-        out = (PbchDetect * self.n)()
-        _check(self.L.oai4g_memcpy_d2h(ctypes.addressof(out), self.d_out, ctypes.sizeof(out)) == 0)
-        return out
-
-    def close(self):
-        if self.cfg:
-            self.L.oai4g_sync()
-            for cfg in self._chest:
-                self.L.oai4g_chest_config_destroy(cfg)
-            for ptr in (self.d_est, self.d_llr, self.d_log2, self.d_out):
-                self.L.oai4g_dev_free(ptr)
-            self.L.oai4g_pbch_front_config_destroy(self.cfg)
-            self.cfg = None
+        return self._get(self.d_out, self.n, PbchDetect)
 
 
 def rx_phich(fp, subframe, comp, ngroup, nseq):
@@ -1633,38 +1523,26 @@ class PhichRxOut(ctypes.Structure):
     _fields_ = [("HI16", ctypes.c_int16), ("nack", ctypes.c_uint8), ("pad", ctypes.c_uint8)]
 
 
-class PhichRxBatch:
+class PhichRxBatch(_DeviceOwner):
     """oai4g_phich_rx_batch behind PdcchFrontBatch: items = [(slot, ngroup, nseq)] -> [(HI16, nack)]"""
 
     def __init__(self, fp, items, first_subframe=0, subframe_step=1):
-        init()
-        self.L, self.n_items = lib(), len(items)
-        self.cfg = self.L.oai4g_phich_rx_config_create(ctypes.byref(fp), first_subframe, subframe_step)
-        _check(bool(self.cfg))
+        self.L, self.n_items = init(), len(items)
+        self.cfg = self._own(self.L.oai4g_phich_rx_config_create(ctypes.byref(fp), first_subframe, subframe_step),
+                             self.L.oai4g_phich_rx_config_destroy)
         arr = (PhichRxItem * max(1, len(items)))()
         for i, (slot, g, q) in enumerate(items):
             arr[i].slot, arr[i].ngroup, arr[i].nseq = slot, g, q
-        self.d_items = self.L.oai4g_dev_alloc(ctypes.sizeof(arr))
-        self.d_out = self.L.oai4g_dev_alloc(max(1, len(items)) * ctypes.sizeof(PhichRxOut))
-        _check(bool(self.d_items) and bool(self.d_out))
-        _check(self.L.oai4g_memcpy_h2d(self.d_items, ctypes.addressof(arr), ctypes.sizeof(arr)) == 0)
+        self.d_items = self._dev(ctypes.sizeof(arr))
+        self.d_out = self._dev(max(1, len(items)) * ctypes.sizeof(PhichRxOut))
+        self._put(self.d_items, np.frombuffer(arr, dtype=np.uint8))
 
     def launch(self, d_comp, n_sf, stream=None):
         _check(self.L.oai4g_phich_rx_batch(self.cfg, d_comp, n_sf, self.d_items, self.n_items, self.d_out, stream) == 0)
 
     def results(self):
-        _check(self.L.oai4g_sync() == 0)
-        out = (PhichRxOut * max(1, self.n_items))()
-        _check(self.L.oai4g_memcpy_d2h(ctypes.addressof(out), self.d_out, ctypes.sizeof(out)) == 0)
+        out = self._get(self.d_out, max(1, self.n_items), PhichRxOut)
         return [(o.HI16, o.nack) for o in out[:self.n_items]]
-
-    def close(self):
-        if self.cfg:
-            self.L.oai4g_sync()
-            self.L.oai4g_dev_free(self.d_items)
-            self.L.oai4g_dev_free(self.d_out)
-            self.L.oai4g_phich_rx_config_destroy(self.cfg)
-            self.cfg = None
 
 
 def _upload_tiled(dec, base, chunk_bytes=64 << 20):
@@ -1678,48 +1556,47 @@ def _upload_tiled(dec, base, chunk_bytes=64 << 20):
     buf = np.zeros((per, dec.llr_stride), dtype=np.int16)
     buf[:, :base.shape[1]] = np.tile(base, (per // nb, 1))
     for r0 in range(0, dec.n_cb, per):
-        n = min(per, dec.n_cb - r0)
-        _check(dec.L.oai4g_memcpy_h2d(dec.d_llr + r0 * dec.llr_stride * 2, _ptr(buf), n * dec.llr_stride * 2) == 0)
+        dec._put(dec.d_llr + r0 * dec.llr_stride * 2, buf[:min(per, dec.n_cb - r0)])
 
 
-class TurboDecoder8Batch:
-    """Device-resident batch of n_cb blocks of size K through the 8-bit decoder (oai4g_td8_batch)."""
+class TurboDecoderBatch(_DeviceOwner):
+    """Device-resident batch of n_cb code blocks of size K (oai4g_td_batch)."""
+    # the entry point, its scratch-size function, the least size of d_it, and d_out zeroed at the start: the decoder
+    # writes d_out only once a hard decision is made (iteration >= 2), as the reference leaves decoded_bytes
+    # untouched at max_iterations = 1
+    _entry, _scratch_bytes, _min_it, _zero_out = "oai4g_td_batch", "oai4g_td_scratch_bytes", 256, True
 
     def __init__(self, K, n_cb):
-        init()
-        self.L = lib()
+        self.L = init()
         self.K, self.n_cb = K, n_cb
         self.llr_stride = 3 * K + 16
-        self.d_llr = self.L.oai4g_dev_alloc(n_cb * self.llr_stride * 2)
-        self.d_out = self.L.oai4g_dev_alloc(n_cb * (K // 8))
-        self.d_it = self.L.oai4g_dev_alloc(n_cb)
-        self.d_scr = self.L.oai4g_dev_alloc(self.L.oai4g_td8_scratch_bytes(K, n_cb))
-        _check(all(bool(p) for p in (self.d_llr, self.d_out, self.d_it, self.d_scr)))
+        self._batch = getattr(self.L, self._entry)
+        self.d_llr = self._dev(n_cb * self.llr_stride * 2)
+        self.d_out = self._dev(n_cb * (K // 8), zero=self._zero_out)
+        self.d_it = self._dev(max(self._min_it, n_cb))
+        self.d_scr = self._dev(getattr(self.L, self._scratch_bytes)(K, n_cb))
 
     def upload(self, llr):
         buf = np.zeros((self.n_cb, self.llr_stride), dtype=np.int16)
         llr = np.asarray(llr, dtype=np.int16)
-        buf[:, :llr.shape[1]] = llr
-        _check(self.L.oai4g_memcpy_h2d(self.d_llr, _ptr(buf), buf.nbytes) == 0)
+        buf[:, :llr.shape[-1]] = llr
+        self._put(self.d_llr, buf)
 
     def upload_tiled(self, base):
         _upload_tiled(self, base)
 
     def run(self, max_iterations=8, crc_type=0, F=0, stream=None):
-        _check(self.L.oai4g_td8_batch(self.n_cb, self.K, self.d_llr, self.llr_stride, self.d_out, self.K // 8,
-                                      self.d_it, max_iterations, crc_type, F, self.d_scr, stream) == 0)
+        _check(self._batch(self.n_cb, self.K, self.d_llr, self.llr_stride, self.d_out, self.K // 8,
+                           self.d_it, max_iterations, crc_type, F, self.d_scr, stream) == 0)
 
     def results(self):
-        _check(self.L.oai4g_sync() == 0)
-        out = np.empty((self.n_cb, self.K // 8), dtype=np.uint8)
-        it = np.empty(self.n_cb, dtype=np.uint8)
-        _check(self.L.oai4g_memcpy_d2h(_ptr(out), self.d_out, out.nbytes) == 0)
-        _check(self.L.oai4g_memcpy_d2h(_ptr(it), self.d_it, it.nbytes) == 0)
-        return it, out
+        out = self._get(self.d_out, (self.n_cb, self.K // 8), np.uint8)
+        return self._get(self.d_it, self.n_cb, np.uint8), out
 
-    def close(self):
-        for p in (self.d_llr, self.d_out, self.d_it, self.d_scr):
-            self.L.oai4g_dev_free(p)
+
+class TurboDecoder8Batch(TurboDecoderBatch):
+    """Device-resident batch of n_cb blocks of size K through the 8-bit decoder (oai4g_td8_batch)."""
+    _entry, _scratch_bytes, _min_it, _zero_out = "oai4g_td8_batch", "oai4g_td8_scratch_bytes", 0, False
 
 
 def generate_dummy_w(D, F=0):
@@ -1730,23 +1607,22 @@ def generate_dummy_w(D, F=0):
     return w
 
 
-class UlDecodeBatch:
+class UlDecodeBatch(_DeviceOwner):
     """Batched ulsch_decoding chain (oai4g_ul_decode_batch): n_tb transport blocks of B = TBS + 24
     bits, G soft bits each -> RM-rx + deinterleaving + 16-bit turbo decoding per code block."""
 
     def __init__(self, B, G, Qm, n_tb, rvidx=0, max_iterations=8, Mdlharq=8, Nsoft=1827072):
-        init()
-        self.L = lib()
-        self.cfg = self.L.oai4g_ul_config_create(B, G, Qm, rvidx, Mdlharq, Nsoft, max_iterations)
-        _check(bool(self.cfg))
+        self.L = init()
+        self.cfg = self._own(self.L.oai4g_ul_config_create(B, G, Qm, rvidx, Mdlharq, Nsoft, max_iterations),
+                             self.L.oai4g_ul_config_destroy)
         self.C = self.L.oai4g_ul_config_C(self.cfg)
         self.n_tb, self.G = n_tb, G
         self.e_stride = (G + 63) & ~63
         self.c_stride = 6144 // 8 + 8
-        self.d_e = self.L.oai4g_dev_alloc(n_tb * self.e_stride * 2)
-        self.d_c = self.L.oai4g_dev_alloc(n_tb * self.C * self.c_stride)
-        self.d_it = self.L.oai4g_dev_alloc(n_tb * self.C)
-        _check(bool(self.d_e) and bool(self.d_c) and bool(self.d_it))
+        self.d_e = self._dev(n_tb * self.e_stride * 2)
+        self.d_c = self._dev(n_tb * self.C * self.c_stride)
+        self.d_it = self._dev(n_tb * self.C)
+        self.d_w = self.d_rc = None
 
     def set_decoder(self, bits):
         """16: phy_threegpplte_turbo_decoder16 (the default); 8: the 8-bit decoder, for one block size
@@ -1762,7 +1638,7 @@ class UlDecodeBatch:
     def upload(self, e):
         buf = np.zeros((self.n_tb, self.e_stride), dtype=np.int16)
         buf[:, :self.G] = np.asarray(e, dtype=np.int16).reshape(self.n_tb, -1)[:, :self.G]
-        _check(self.L.oai4g_memcpy_h2d(self.d_e, _ptr(buf), buf.nbytes) == 0)
+        self._put(self.d_e, buf)
 
     def launch(self, stream=None):
         _check(self.L.oai4g_ul_decode_batch(self.cfg, self.n_tb, self.d_e, self.e_stride, self.d_c, self.c_stride,
@@ -1781,86 +1657,25 @@ class UlDecodeBatch:
         self._alloc_w()
         rc = np.ascontiguousarray(np.stack([np.asarray(rv, np.uint8).reshape(self.n_tb),
                                             np.asarray(clear, np.uint8).reshape(self.n_tb)]))
-        if getattr(self, "d_rc", None) is None:
-            self.d_rc = self.L.oai4g_dev_alloc(rc.nbytes)
-            _check(bool(self.d_rc))
-        _check(self.L.oai4g_memcpy_h2d(self.d_rc, _ptr(rc), rc.nbytes) == 0)
+        if self.d_rc is None:
+            self.d_rc = self._dev(rc.nbytes)
+        self._put(self.d_rc, rc)
         _check(self.L.oai4g_ul_decode_batch_harq_tb(self.cfg, self.n_tb, self.d_e, self.e_stride, self.d_w,
                                                     self.w_stride, self.d_rc, self.d_rc + self.n_tb, self.d_c,
                                                     self.c_stride, self.d_it, stream) == 0)
 
     def _alloc_w(self):
-        if getattr(self, "d_w", None) is None:
+        if self.d_w is None:
             self.w_stride = (self.L.oai4g_ul_config_w_entries(self.cfg) + 63) & ~63
-            nbytes = self.n_tb * self.C * self.w_stride * 2
-            self.d_w = self.L.oai4g_dev_alloc(nbytes)
-            _check(bool(self.d_w))
-            z = np.zeros(nbytes // 2, np.int16)
-            _check(self.L.oai4g_memcpy_h2d(self.d_w, _ptr(z), nbytes) == 0)
+            self.d_w = self._dev(self.n_tb * self.C * self.w_stride * 2, zero=True)
 
     def soft_buffers(self):
         """[n_tb][C][w_stride] int16 HARQ soft buffers (after launch_harq)."""
-        _check(self.L.oai4g_sync() == 0)
-        w = np.empty((self.n_tb, self.C, self.w_stride), dtype=np.int16)
-        _check(self.L.oai4g_memcpy_d2h(_ptr(w), self.d_w, w.nbytes) == 0)
-        return w
+        return self._get(self.d_w, (self.n_tb, self.C, self.w_stride), np.int16)
 
     def results(self):
-        _check(self.L.oai4g_sync() == 0)
-        c = np.empty((self.n_tb, self.C, self.c_stride), dtype=np.uint8)
-        it = np.empty((self.n_tb, self.C), dtype=np.uint8)
-        _check(self.L.oai4g_memcpy_d2h(_ptr(c), self.d_c, c.nbytes) == 0)
-        _check(self.L.oai4g_memcpy_d2h(_ptr(it), self.d_it, it.nbytes) == 0)
-        return it, c
-
-    def close(self):
-        for p in (self.d_e, self.d_c, self.d_it, getattr(self, "d_w", None), getattr(self, "d_rc", None)):
-            if p:
-                self.L.oai4g_dev_free(p)
-        self.L.oai4g_ul_config_destroy(self.cfg)
-
-
-class TurboDecoderBatch:
-    """Device-resident batch of n_cb code blocks of size K (oai4g_td_batch)."""
-
-    def __init__(self, K, n_cb):
-        init()
-        self.L = lib()
-        self.K, self.n_cb = K, n_cb
-        self.llr_stride = 3 * K + 16
-        self.d_llr = self.L.oai4g_dev_alloc(n_cb * self.llr_stride * 2)
-        self.d_out = self.L.oai4g_dev_alloc(n_cb * (K // 8))
-        self.d_it = self.L.oai4g_dev_alloc(max(256, n_cb))
-        self.d_scr = self.L.oai4g_dev_alloc(self.L.oai4g_td_scratch_bytes(K, n_cb))
-        _check(all([self.d_llr, self.d_out, self.d_it, self.d_scr]))
-        # the decoder writes d_out only once a hard decision is made (iteration >= 2), as the
-        # reference leaves decoded_bytes untouched at max_iterations = 1: start from a zeroed buffer
-        z = np.zeros(n_cb * (K // 8), dtype=np.uint8)
-        _check(self.L.oai4g_memcpy_h2d(self.d_out, _ptr(z), z.nbytes) == 0)
-
-    def upload(self, llr):
-        buf = np.zeros((self.n_cb, self.llr_stride), dtype=np.int16)
-        buf[:, :3 * self.K + 12] = llr
-        _check(self.L.oai4g_memcpy_h2d(self.d_llr, _ptr(buf), buf.nbytes) == 0)
-
-    def upload_tiled(self, base):
-        _upload_tiled(self, base)
-
-    def run(self, max_iterations=8, crc_type=0, F=0, stream=None):
-        _check(self.L.oai4g_td_batch(self.n_cb, self.K, self.d_llr, self.llr_stride, self.d_out, self.K // 8,
-                                     self.d_it, max_iterations, crc_type, F, self.d_scr, stream) == 0)
-
-    def results(self):
-        _check(self.L.oai4g_sync() == 0)
-        out = np.empty((self.n_cb, self.K // 8), dtype=np.uint8)
-        it = np.empty(self.n_cb, dtype=np.uint8)
-        _check(self.L.oai4g_memcpy_d2h(_ptr(out), self.d_out, out.nbytes) == 0)
-        _check(self.L.oai4g_memcpy_d2h(_ptr(it), self.d_it, it.nbytes) == 0)
-        return it, out
-
-    def close(self):
-        for p in (self.d_llr, self.d_out, self.d_it, self.d_scr):
-            self.L.oai4g_dev_free(p)
+        c = self._get(self.d_c, (self.n_tb, self.C, self.c_stride), np.uint8)
+        return self._get(self.d_it, (self.n_tb, self.C), np.uint8), c
 
 
 def dci_allocs(items):
@@ -1890,27 +1705,19 @@ def normal_prefix_mod(txdataF, fp, nsymb=7, out=None):
     return out
 
 
-class DlschHandle:
+class DlschHandle(_DeviceOwner):
     """Owns an oai4g_dlsch_t (new_eNB_dlsch) and exposes its HARQ-0 buffers as numpy views."""
 
     def __init__(self, Kmimo=1, Mdlharq=8, N_RB_DL=100):
-        init()
-        self.ptr = lib().oai4g_new_dlsch(Kmimo, Mdlharq, N_RB_DL)
-        if not self.ptr:
-            raise OAI4GError("new_dlsch failed")
+        self.L = init()
+        self.ptr = self._own(self.L.oai4g_new_dlsch(Kmimo, Mdlharq, N_RB_DL), self.L.oai4g_free_dlsch)
         self.d = self.ptr.contents
         self.h = self.d.harq_processes[0].contents
 
     def close(self):
-        if self.ptr:
-            lib().oai4g_free_dlsch(self.ptr)
-            self.ptr = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        """the views die with the structure: d, h and ptr are dropped with it"""
+        super().close()
+        self.ptr = self.d = self.h = None
 
     def view(self, field, n, r=None):
         p = getattr(self.h, field) if r is None else getattr(self.h, field)[r]
@@ -2019,16 +1826,14 @@ def make_params(name="C3", subframe=7, subframe_step=0, rnti=0x1234, Nid_cell=0,
     return p
 
 
-class TxPipeline:
+class TxPipeline(_DeviceOwner):
     """Batched device-resident transmit path for one configuration (oai4g_tx_*)."""
 
     def __init__(self, params, n_sf, alloc=True):
         self.L = init()
         self.params = params
         self.n_sf = n_sf
-        self.cfg = self.L.oai4g_tx_config_create(ctypes.byref(params))
-        if not self.cfg:
-            raise OAI4GError(self.L.oai4g_last_error().decode())
+        self.cfg = self._own(self.L.oai4g_tx_config_create(ctypes.byref(params)), self.L.oai4g_tx_config_destroy)
         self.n_cw = params.n_cw
         self.n_ant = params.nb_antennas_tx
         self.spt = self.L.oai4g_tx_iq_samples(self.cfg)
@@ -2038,15 +1843,9 @@ class TxPipeline:
         self.iq_samples = n_sf * self.n_ant * self.spt
         self.d_payload = self.d_work = self.d_iq = self.d_rv = None
         if alloc:
-            self.d_payload = self._alloc(self.payload_bytes)
-            self.d_work = self._alloc(self.work_bytes)
-            self.d_iq = self._alloc(self.iq_samples * 4)
-
-    def _alloc(self, n):
-        p = self.L.oai4g_dev_alloc(n)
-        if not p:
-            raise OAI4GError(self.L.oai4g_last_error().decode())
-        return p
+            self.d_payload = self._dev(self.payload_bytes)
+            self.d_work = self._dev(self.work_bytes)
+            self.d_iq = self._dev(self.iq_samples * 4)
 
     def G(self, cw, subframe):
         return self.L.oai4g_tx_G(self.cfg, cw, subframe)
@@ -2080,12 +1879,10 @@ class TxPipeline:
     def upload_payload(self, payload):
         payload = np.ascontiguousarray(payload, dtype=np.uint8)
         assert payload.nbytes == self.payload_bytes
-        _check(self.L.oai4g_memcpy_h2d(self.d_payload, _ptr(payload), payload.nbytes) == 0)
+        self._put(self.d_payload, payload)
 
     def download_payload(self):
-        out = np.empty(self.payload_bytes, dtype=np.uint8)
-        _check(self.L.oai4g_memcpy_d2h(_ptr(out), self.d_payload, out.nbytes) == 0)
-        return out.reshape(self.n_sf, self.n_cw, self.params.payload_stride)
+        return self._get(self.d_payload, (self.n_sf, self.n_cw, self.params.payload_stride), np.uint8)
 
     def run(self, stream=None):
         _check(self.L.oai4g_tx_batch(self.cfg, self.n_sf, self.d_payload, self.d_work, self.d_iq, stream) == 0)
@@ -2098,8 +1895,8 @@ class TxPipeline:
         """[n_sf][n_cw] redundancy versions (0..3) for run_rv / encode_only_rv."""
         rv = np.ascontiguousarray(np.asarray(rv, dtype=np.uint8).reshape(self.n_sf, self.n_cw))
         if self.d_rv is None:
-            self.d_rv = self._alloc(rv.nbytes)
-        _check(self.L.oai4g_memcpy_h2d(self.d_rv, _ptr(rv), rv.nbytes) == 0)
+            self.d_rv = self._dev(rv.nbytes)
+        self._put(self.d_rv, rv)
 
     def run_rv(self, rv=None, stream=None):
         """oai4g_tx_batch_rv: the batch with a redundancy version per transport block (rv: [n_sf][n_cw],
@@ -2137,7 +1934,7 @@ class TxPipeline:
         """Packed scrambled e-bit words [n_sf][n_cw][ebits_words] into the workspace."""
         words = np.ascontiguousarray(words, dtype=np.uint32)
         assert words.nbytes <= self.work_bytes
-        _check(self.L.oai4g_memcpy_h2d(self.d_work, _ptr(words), words.nbytes) == 0)
+        self._put(self.d_work, words)
 
     @property
     def mod_nosat(self):
@@ -2152,29 +1949,10 @@ class TxPipeline:
         _check(self.L.oai4g_sync() == 0)
 
     def ebits(self):
-        out = np.empty(self.work_bytes // 4, dtype=np.uint32)
-        _check(self.L.oai4g_memcpy_d2h(_ptr(out), self.d_work, out.nbytes) == 0)
-        return out.reshape(self.n_sf, self.n_cw, self.ebits_words)
+        return self._get(self.d_work, self.work_bytes // 4, np.uint32).reshape(self.n_sf, self.n_cw, self.ebits_words)
 
     def iq(self):
-        out = np.empty(self.iq_samples, dtype=np.int32)
-        _check(self.L.oai4g_memcpy_d2h(_ptr(out), self.d_iq, out.nbytes) == 0)
-        return out.reshape(self.n_sf, self.n_ant, self.spt)
-
-    def close(self):
-        for p in (self.d_payload, self.d_work, self.d_iq, self.d_rv):
-            if p:
-                self.L.oai4g_dev_free(p)
-        self.d_payload = self.d_work = self.d_iq = self.d_rv = None
-        if self.cfg:
-            self.L.oai4g_tx_config_destroy(self.cfg)
-            self.cfg = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._get(self.d_iq, (self.n_sf, self.n_ant, self.spt), np.int32)
 
 
 def unpack_bits(words, nbits):

@@ -34,7 +34,7 @@ import math
 
 import numpy as np
 
-from . import (FULL_ALLOC_25, ChestBatch, FepBatch, OAI4GError, RxBatch, TxPipeline, _check, _ptr, frame_parms,
+from . import (FULL_ALLOC_25, ChestBatch, FepBatch, OAI4GError, RxBatch, TxPipeline, _check, _DeviceOwner, frame_parms,
                init, lib, make_params, normal_prefix_mod, generate_pilots, UlDecodeBatch)
 
 DCI1_LEN = {6: 23, 15: 25, 25: 27, 50: 27, 100: 39}      # sizeof_DCI1_xMHz_FDD_t (PHY/LTE_TRANSPORT/dci.h)
@@ -47,7 +47,7 @@ def qm_of(mcs):
     return 2 if mcs < 10 else (4 if mcs < 17 else 6)
 
 
-class DlsimBler:
+class DlsimBler(_DeviceOwner):
     """Batched BLER trials of one (N_RB_DL, MCS) configuration; see the module docstring."""
 
     def __init__(self, mcs, N_RB_DL=25, batch=4096, subframe=7, num_pdcch_symbols=1, Nid_cell=0, rnti=0x1234,
@@ -61,7 +61,7 @@ class DlsimBler:
                              num_pdcch_symbols=num_pdcch_symbols)
         self.fp = frame_parms(N_RB_DL, Nid_cell=Nid_cell)
         self.spt, self.N = self.fp.samples_per_tti, self.fp.ofdm_symbol_size
-        self.tx = TxPipeline(self.p, batch)
+        self.tx = self._own(TxPipeline(self.p, batch))
         if with_dci:
             self.L.oai4g_init_nCCE_table()
             nCCE = self.L.oai4g_get_nCCE(num_pdcch_symbols, ctypes.byref(self.fp), 1)
@@ -78,18 +78,17 @@ class DlsimBler:
         normal_prefix_mod(grid[nxt * nsymb * self.N:], self.fp, nsymb // 2, tail)
         self.tail = tail
         L = self.L
-        self.d_tail = L.oai4g_dev_alloc(tail.nbytes)
-        self.d_lev = L.oai4g_dev_alloc(4 * batch)
-        self.fep = FepBatch(self.fp, 2 * batch, 1)
-        _check(bool(self.d_tail) and bool(self.d_lev))
-        _check(L.oai4g_memcpy_h2d(self.d_tail, _ptr(tail), tail.nbytes) == 0)
-        self.ce = ChestBatch(self.fp, batch, first_subframe=subframe, subframe_step=0)
+        self.d_tail = self._dev(tail.nbytes)
+        self.d_lev = self._dev(4 * batch)
+        self.fep = self._own(FepBatch(self.fp, 2 * batch, 1))
+        self._put(self.d_tail, tail)
+        self.ce = self._own(ChestBatch(self.fp, batch, first_subframe=subframe, subframe_step=0))
         _check(L.oai4g_chest_config_set_stride(self.ce.cfg, 2, 1) == 0)
-        self.rx = RxBatch(self.fp, list(FULL_ALLOC[N_RB_DL]), self.Qm, num_pdcch_symbols, rnti, batch,
-                          first_subframe=subframe, subframe_step=0)
+        self.rx = self._own(RxBatch(self.fp, list(FULL_ALLOC[N_RB_DL]), self.Qm, num_pdcch_symbols, rnti, batch,
+                                    first_subframe=subframe, subframe_step=0))
         self.G = self.rx.llr_count(subframe)
         self.TBS = self.p.TBS[0]
-        self.dec = UlDecodeBatch(self.TBS + 24, self.G, self.Qm, batch, max_iterations=max_iterations)
+        self.dec = self._own(UlDecodeBatch(self.TBS + 24, self.G, self.Qm, batch, max_iterations=max_iterations))
         if llr8:                              # dlsim -L: dlsch_decoding with the 8-bit decoder
             _check(self.L.oai4g_ul_config_set_decoder(self.dec.cfg, 8) == 0)
         self.C = self.dec.C
@@ -104,8 +103,7 @@ class DlsimBler:
             self.tx.enable_tb_rv()
             self.dec._alloc_w()
             nb = (4 * batch + 7) & ~7
-            self.d_state = L.oai4g_dev_alloc(nb + 4 * batch + 32)
-            _check(bool(self.d_state))
+            self.d_state = self._dev(nb + 4 * batch + 32)
             self.d_round, self.d_rv = self.d_state, self.d_state + batch
             self.d_clear, self.d_done = self.d_state + 2 * batch, self.d_state + 3 * batch
             self.d_trial, self.d_counters = self.d_state + nb, self.d_state + nb + 4 * batch
@@ -140,7 +138,7 @@ class DlsimBler:
         B = self.B
         st = np.zeros(self._state_bytes, np.uint8)
         st[2 * B:3 * B] = 1                                   # clear
-        _check(self.L.oai4g_memcpy_h2d(self.d_state, _ptr(st), st.nbytes) == 0)
+        self._put(self.d_state, st)
         self.tx.fill_payload(seed)
         self._seed, self._step = seed, 0
 
@@ -167,9 +165,7 @@ class DlsimBler:
     def round_state(self):
         """(round, rv, clear, done, trial, counters) after the steps enqueued so far (synchronises)."""
         B = self.B
-        st = np.empty(self._state_bytes, np.uint8)
-        _check(self.L.oai4g_sync() == 0)
-        _check(self.L.oai4g_memcpy_d2h(_ptr(st), self.d_state, st.nbytes) == 0)
+        st = self._get(self.d_state, self._state_bytes, np.uint8)
         nb = (4 * B + 7) & ~7
         u32 = st[nb:].view(np.uint32)
         return st[:B].copy(), st[B:2 * B].copy(), st[2 * B:3 * B].copy(), st[3 * B:4 * B].copy(), u32[:B].copy(), \
@@ -190,10 +186,7 @@ class DlsimBler:
                     throughput=self.TBS / self.G * eff)
 
     def tx_lev(self):
-        out = np.empty(self.B, np.int32)
-        _check(self.L.oai4g_sync() == 0)
-        _check(self.L.oai4g_memcpy_d2h(_ptr(out), self.d_lev, out.nbytes) == 0)
-        return out
+        return self._get(self.d_lev, self.B, np.int32)
 
     def run_point(self, snr_db, n_trials, seed=1):
         """(errors, trials) at one SNR over ceil(n_trials / batch) batches."""
@@ -206,15 +199,6 @@ class DlsimBler:
             trials += take
             b += 1
         return errs, trials
-
-    def close(self):
-        for o in (self.tx, self.fep, self.ce, self.rx, self.dec):
-            o.close()
-        self.L.oai4g_dev_free(self.d_tail)
-        self.L.oai4g_dev_free(self.d_lev)
-        if self.d_state:
-            self.L.oai4g_dev_free(self.d_state)
-            self.d_state = None
 
 
 def tb_bytes_from_blocks(c, TBS, C, K_list, F):

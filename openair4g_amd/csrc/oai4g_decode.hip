@@ -865,10 +865,50 @@ hipError_t oai4g_launch_td16(int n_cb, uint32_t K, const int16_t *d_llr, size_t 
 }
 
 /* ======================================================================================
- * RX rate matching + sub-block deinterleaving for one block, thread per w entry:
- * w[p] = sum of the soft inputs that the circular selection maps to p (int16 wrap, the
- * reference's `w[ind] += soft` in any order), then d = deinterleave(w).
+ * RX rate matching + sub-block deinterleaving.  Two maps carry every kernel below.
  * ==================================================================================== */
+
+/* lte_rate_matching_turbo_rx's sum for one circular-buffer position (the reference's `w[ind] += soft`
+ * in any order: int16 wrap-around is associative): acc plus every soft input the circular selection
+ * maps to the position with compact (non-NULL) index ci.  The selection starts at compact index k0c
+ * and wraps every Nnn inputs.  Inlined, so a `soft` in LDS is read with LDS instructions.  k0c and
+ * Nnn come as pointers to the caller's table entries, so each is loaded where the loop uses it and not
+ * ahead of the call: the kernels compile to the instructions of the written-out loop. */
+__device__ __forceinline__ int16_t rm_rx_gather(const int16_t *soft, uint32_t ci, uint32_t E, const uint32_t *k0c,
+                                                const uint32_t *Nnn, int16_t acc)
+{
+  for (uint32_t q = ci >= *k0c ? ci - *k0c : ci + *Nnn - *k0c; q < E; q += *Nnn) acc = (int16_t)(acc + soft[q]);
+  return acc;
+}
+
+/* The inverse of sub_block_deinterleaving_turbo (lte_rate_matching.c:193-243), which puts w[k] at
+ * d1[index3], w[Kpi + 2k] at d1[index3 + 1] and w[Kpi + 2k + 1] at d1[index3 + 5] (index3 =
+ * 3 bitrev5(col) + 96 row, k = col R + row, d1 = dfull + 96 - 3 ND): f(p) with the w position p of
+ * entry i of d1, and no call for an entry the reference never writes (d1[2], its prefix slot; rows
+ * past R; i past d1[3 Kpi + 2], the d[3D + 2] entry that the +5 of the last column produces). */
+template <typename F>
+__device__ __forceinline__ void ul_w_of_d(uint32_t i, uint32_t R, F f)
+{
+  const uint32_t Kpi = R << 5;
+  if (i >= 3 * Kpi + 3 || i == 2) return;
+  const uint32_t sft = i % 3, base = sft == 2 ? i - 5 : i, row = base / 96, cp = (base % 96) / 3;
+  if (row >= R) return;
+  const uint32_t k = (__builtin_bitreverse32(cp) >> 27) * R + row;
+  f(sft == 0 ? k : Kpi + 2 * k + (sft == 2 ? 1 : 0));
+}
+
+/* rows (tb, r) on gridDim.y, in chunks within its 65535 limit: launch(rows of the chunk, first row) */
+template <typename Launch>
+static hipError_t ul_row_chunks(uint32_t rows, Launch launch)
+{
+  for (uint32_t j0 = 0; j0 < rows; j0 += 65535u) {
+    const hipError_t err = launch(rows - j0 < 65535u ? rows - j0 : 65535u, j0);
+    if (err != hipSuccess) return err;
+  }
+  return hipSuccess;
+}
+
+/* one block, thread per w entry: w[p] = rm_rx_gather, then d = deinterleave(w) */
 __global__ void __launch_bounds__(256) k_rm_rx(const int16_t *__restrict__ soft, uint32_t E, int16_t *__restrict__ w,
                                                const uint8_t *__restrict__ dummy_w, const uint32_t *__restrict__ cidx,
                                                uint32_t Ncb, uint32_t Nnn, uint32_t k0c, int clear)
@@ -876,12 +916,7 @@ __global__ void __launch_bounds__(256) k_rm_rx(const int16_t *__restrict__ soft,
   const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= Ncb) return;
   int16_t acc = clear ? (int16_t)0 : w[p];
-  if (dummy_w[p] != OAI4G_LTE_NULL) {
-    /* compact index of p, then every selection round that lands on it */
-    const uint32_t c = cidx[p];
-    uint32_t k = c >= k0c ? c - k0c : c + Nnn - k0c;
-    for (; k < E; k += Nnn) acc = (int16_t)(acc + soft[k]);
-  }
+  if (dummy_w[p] != OAI4G_LTE_NULL) acc = rm_rx_gather(soft, cidx[p], E, &k0c, &Nnn, acc);
   w[p] = acc;
 }
 
@@ -902,31 +937,21 @@ __global__ void __launch_bounds__(256) k_subblock_deint(uint32_t D, int16_t *__r
 
 /* ulsch_decoding's per-block RX chain fused (ulsch_decoding.c:1208-1287), one thread per entry i of
  * code block j's deinterleaved d buffer (blockIdx.y = j: tb = j / C, r = j % C), so the stores are
- * contiguous.  sub_block_deinterleaving_turbo puts w[k] at d1[index3], w[Kpi + 2k] at
- * d1[index3 + 1] and w[Kpi + 2k + 1] at d1[index3 + 5] (index3 = 3 bitrev5(col) + 96 row,
- * k = col R + row, d1 = dfull + 96 - 3 ND); inverting that gives the w position p of entry i, whose
- * value is lte_rate_matching_turbo_rx's (clear = 1): the int16 wrap sum of the soft inputs the
- * circular selection maps to p, 0 for NULL positions.  d1[2] is never written (the reference's
- * prefix slot), d1[3 Kpi + 2] is the d[3D + 2] entry the +5 of the last column produces. */
+ * contiguous: entry i holds lte_rate_matching_turbo_rx's value (clear = 1) of its w position
+ * ul_w_of_d, 0 for NULL positions and past Ncb.  The form for blocks of more than 32768 soft inputs. */
 __global__ void __launch_bounds__(256) k_ul_rm_deint(const ul_dev_t *__restrict__ c, const int16_t *__restrict__ e,
                                                      size_t e_stride, int16_t *__restrict__ dfull, size_t d_stride,
                                                      uint32_t j0)
 {
   const uint32_t j = j0 + blockIdx.y, tb = j / c->C, r = j - tb * c->C;
   const ul_pat_t &P = c->pat[c->pat_of[r]];
-  const uint32_t R = P.R, Kpi = R << 5, i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= 3 * Kpi + 3 || i == 2) return;
-  const uint32_t sft = i % 3, base = sft == 2 ? i - 5 : i, row = base / 96, cp = (base % 96) / 3;
-  if (row >= R) return;
-  const uint32_t k = (__builtin_bitreverse32(cp) >> 27) * R + row;
-  const uint32_t p = sft == 0 ? k : Kpi + 2 * k + (sft == 2 ? 1 : 0);
-  int16_t acc = 0;
-  if (p < P.Ncb && P.dummy[p] != OAI4G_LTE_NULL) {
-    const int16_t *soft = e + tb * e_stride + c->off[r];
-    const uint32_t ci = P.cidx[p], E = c->E[r];
-    for (uint32_t q = ci >= P.k0c ? ci - P.k0c : ci + P.Nnn - P.k0c; q < E; q += P.Nnn) acc = (int16_t)(acc + soft[q]);
-  }
-  dfull[(size_t)j * d_stride + 96 - 3 * (Kpi - P.D) + i] = acc;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  ul_w_of_d(i, P.R, [&](uint32_t p) {
+    int16_t acc = 0;
+    if (p < P.Ncb && P.dummy[p] != OAI4G_LTE_NULL)
+      acc = rm_rx_gather(e + tb * e_stride + c->off[r], P.cidx[p], c->E[r], &P.k0c, &P.Nnn, 0);
+    dfull[(size_t)j * d_stride + 96 - 3 * ((P.R << 5) - P.D) + i] = acc;
+  });
 }
 
 /* k_ul_rm_deint with the block's E soft inputs staged in LDS first (one coalesced pass; the
@@ -944,17 +969,11 @@ __global__ void __launch_bounds__(256) k_ul_rm_deint_lds(const ul_dev_t *__restr
   __syncthreads();
   int16_t *d = dfull + (size_t)j * d_stride + 96 - 3 * (Kpi - P.D);
   for (uint32_t i = threadIdx.x; i < 3 * Kpi + 3; i += blockDim.x) {
-    if (i == 2) continue;
-    const uint32_t sft = i % 3, base = sft == 2 ? i - 5 : i, row = base / 96, cp = (base % 96) / 3;
-    if (row >= R) continue;
-    const uint32_t k = (__builtin_bitreverse32(cp) >> 27) * R + row;
-    const uint32_t p = sft == 0 ? k : Kpi + 2 * k + (sft == 2 ? 1 : 0);
-    int16_t acc = 0;
-    if (p < P.Ncb && P.dummy[p] != OAI4G_LTE_NULL) {
-      const uint32_t ci = P.cidx[p];
-      for (uint32_t q = ci >= P.k0c ? ci - P.k0c : ci + P.Nnn - P.k0c; q < E; q += P.Nnn) acc = (int16_t)(acc + sb[q]);
-    }
-    d[i] = acc;
+    ul_w_of_d(i, R, [&](uint32_t p) {
+      int16_t acc = 0;
+      if (p < P.Ncb && P.dummy[p] != OAI4G_LTE_NULL) acc = rm_rx_gather(sb, P.cidx[p], E, &P.k0c, &P.Nnn, 0);
+      d[i] = acc;
+    });
   }
 }
 
@@ -964,105 +983,86 @@ hipError_t oai4g_launch_ul_rm_deint(const ul_dev_t *d_cfg, const ul_dev_t *h_cfg
   if (n_tb <= 0) return hipSuccess;
   uint32_t emax = 0;
   for (uint32_t r = 0; r < h_cfg->C; r++) emax = h_cfg->E[r] > emax ? h_cfg->E[r] : emax;
+  const uint32_t rows = (uint32_t)n_tb * h_cfg->C;
   if (2 * (size_t)emax <= 64 * 1024) {         /* the staged form while a block's inputs fit 64 KB of LDS */
-    const uint32_t rows = (uint32_t)n_tb * h_cfg->C;
     hipLaunchKernelGGL(k_ul_rm_deint_lds, dim3(rows), dim3(256), 2 * (size_t)emax, s, d_cfg, d_e, e_stride, d_dfull,
                        d_stride);
     return hipGetLastError();
   }
-  /* (tb, r) rows in chunks within the 65535 limit of gridDim.y */
-  const uint32_t rows = (uint32_t)n_tb * h_cfg->C, gx = (3 * (h_cfg->Rmax << 5) + 3 + 255) / 256;
-  for (uint32_t j0 = 0; j0 < rows; j0 += 65535u) {
-    const uint32_t n = rows - j0 < 65535u ? rows - j0 : 65535u;
+  const uint32_t gx = (3 * (h_cfg->Rmax << 5) + 3 + 255) / 256;
+  return ul_row_chunks(rows, [&](uint32_t n, uint32_t j0) {
     hipLaunchKernelGGL(k_ul_rm_deint, dim3(gx, n), dim3(256), 0, s, d_cfg, d_e, e_stride, d_dfull, d_stride, j0);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return err;
-  }
-  return hipSuccess;
+    return hipGetLastError();
+  });
 }
 
 /* lte_rate_matching_turbo_rx (lte_rate_matching.c:688-831) of every block into its HARQ soft buffer
  * w, one thread per circular-buffer position p < Ncb (rows j = (tb, r) on blockIdx.y): clear = 1
  * (round 0) starts from 0 (the reference's memset of w[0..Ncb)), clear = 0 from the stored value;
- * the soft inputs the circular selection of this round's k0 maps to p are added with int16
- * wrap-around, in the reference's order (the sum is associative mod 2^16). */
-__global__ void __launch_bounds__(256) k_ul_rm_harq(const ul_dev_t *__restrict__ c, const int16_t *__restrict__ e,
-                                                    size_t e_stride, int16_t *__restrict__ w, size_t w_stride,
-                                                    uint32_t rv, int clear, uint32_t j0)
+ * the soft inputs the circular selection of this round's k0 maps to p are added.  k_ul_rm_harq takes
+ * one redundancy version and one clear flag for the batch, k_ul_rm_harq_tb those of each transport
+ * block: rv[tb] (masked to 0..3, the four entries of k0cr) and clear[tb] != 0, so one batch holds
+ * HARQ processes at different rounds. */
+template <typename RvOf, typename ClearOf>
+__device__ __forceinline__ void ul_rm_harq_body(const ul_dev_t *__restrict__ c, const int16_t *__restrict__ e,
+                                                size_t e_stride, int16_t *__restrict__ w, size_t w_stride, uint32_t j0,
+                                                RvOf rv_of, ClearOf clear_of)
 {
   const uint32_t j = j0 + blockIdx.y, tb = j / c->C, r = j - tb * c->C;
   const ul_pat_t &P = c->pat[c->pat_of[r]];
   const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= P.Ncb) return;
   int16_t *wp = w + (size_t)j * w_stride + p;
-  int16_t acc = clear ? (int16_t)0 : *wp;
-  if (P.dummy[p] != OAI4G_LTE_NULL) {
-    const int16_t *soft = e + tb * e_stride + c->off[r];
-    const uint32_t ci = P.cidx[p], E = c->E[r], k0c = P.k0cr[rv];
-    for (uint32_t q = ci >= k0c ? ci - k0c : ci + P.Nnn - k0c; q < E; q += P.Nnn) acc = (int16_t)(acc + soft[q]);
-  }
+  int16_t acc = clear_of(tb) ? (int16_t)0 : *wp;
+  if (P.dummy[p] != OAI4G_LTE_NULL)
+    acc = rm_rx_gather(e + tb * e_stride + c->off[r], P.cidx[p], c->E[r], &P.k0cr[rv_of(tb)], &P.Nnn, acc);
   *wp = acc;
 }
-
-/* k_ul_rm_harq with the redundancy version and the clear flag of each transport block: rv[tb] (masked
- * to 0..3, the four entries of k0cr) and clear[tb] != 0, so one batch holds HARQ processes at different
- * rounds */
+__global__ void __launch_bounds__(256) k_ul_rm_harq(const ul_dev_t *__restrict__ c, const int16_t *__restrict__ e,
+                                                    size_t e_stride, int16_t *__restrict__ w, size_t w_stride,
+                                                    uint32_t rv, int clear, uint32_t j0)
+{
+  ul_rm_harq_body(c, e, e_stride, w, w_stride, j0, [=](uint32_t) { return rv; }, [=](uint32_t) { return clear; });
+}
 __global__ void __launch_bounds__(256) k_ul_rm_harq_tb(const ul_dev_t *__restrict__ c, const int16_t *__restrict__ e,
                                                        size_t e_stride, int16_t *__restrict__ w, size_t w_stride,
                                                        const uint8_t *__restrict__ rv, const uint8_t *__restrict__ clear,
                                                        uint32_t j0)
 {
-  const uint32_t j = j0 + blockIdx.y, tb = j / c->C, r = j - tb * c->C;
-  const ul_pat_t &P = c->pat[c->pat_of[r]];
-  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= P.Ncb) return;
-  int16_t *wp = w + (size_t)j * w_stride + p;
-  int16_t acc = clear[tb] ? (int16_t)0 : *wp;
-  if (P.dummy[p] != OAI4G_LTE_NULL) {
-    const int16_t *soft = e + tb * e_stride + c->off[r];
-    const uint32_t ci = P.cidx[p], E = c->E[r], k0c = P.k0cr[rv[tb] & 3u];
-    for (uint32_t q = ci >= k0c ? ci - k0c : ci + P.Nnn - k0c; q < E; q += P.Nnn) acc = (int16_t)(acc + soft[q]);
-  }
-  *wp = acc;
+  ul_rm_harq_body(c, e, e_stride, w, w_stride, j0, [=](uint32_t tb) { return rv[tb] & 3u; },
+                  [=](uint32_t tb) { return clear[tb]; });
 }
 
-/* sub_block_deinterleaving_turbo (lte_rate_matching.c:193-243) of every block's soft buffer into
- * its decoder row, one thread per d entry (the inverse map of k_ul_rm_deint); positions past Ncb
- * read 0, as a zero-initialised buffer the RX rate matcher never writes there gives */
+/* sub_block_deinterleaving_turbo of every block's soft buffer into its decoder row, one thread per d
+ * entry (ul_w_of_d); positions past Ncb read 0, as a zero-initialised buffer the RX rate matcher
+ * never writes there gives */
 __global__ void __launch_bounds__(256) k_ul_deint_w(const ul_dev_t *__restrict__ c, const int16_t *__restrict__ w,
                                                     size_t w_stride, int16_t *__restrict__ dfull, size_t d_stride,
                                                     uint32_t j0)
 {
   const uint32_t j = j0 + blockIdx.y, r = j % c->C;
   const ul_pat_t &P = c->pat[c->pat_of[r]];
-  const uint32_t R = P.R, Kpi = R << 5, i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= 3 * Kpi + 3 || i == 2) return;
-  const uint32_t sft = i % 3, base = sft == 2 ? i - 5 : i, row = base / 96, cp = (base % 96) / 3;
-  if (row >= R) return;
-  const uint32_t k = (__builtin_bitreverse32(cp) >> 27) * R + row;
-  const uint32_t p = sft == 0 ? k : Kpi + 2 * k + (sft == 2 ? 1 : 0);
-  dfull[(size_t)j * d_stride + 96 - 3 * (Kpi - P.D) + i] = p < P.Ncb ? w[(size_t)j * w_stride + p] : (int16_t)0;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  ul_w_of_d(i, P.R, [&](uint32_t p) {
+    dfull[(size_t)j * d_stride + 96 - 3 * ((P.R << 5) - P.D) + i] = p < P.Ncb ? w[(size_t)j * w_stride + p] : (int16_t)0;
+  });
 }
 
 /* the HARQ round of every row (tb, r): the rate matcher into w (launch_rm(grid, first row)), then w ->
- * the decoder rows, in chunks of rows within the 65535 limit of gridDim.y */
+ * the decoder rows */
 template <typename LaunchRm>
 static hipError_t ul_rm_harq_rows(const ul_dev_t *d_cfg, const ul_dev_t *h_cfg, int n_tb, const int16_t *d_w,
                                   size_t w_stride, int16_t *d_dfull, size_t d_stride, hipStream_t s, LaunchRm launch_rm)
 {
   if (n_tb <= 0) return hipSuccess;
-  const uint32_t rows = (uint32_t)n_tb * h_cfg->C, gw = (3 * (h_cfg->Rmax << 5) + 255) / 256,
-                 gd = (3 * (h_cfg->Rmax << 5) + 3 + 255) / 256;
-  for (uint32_t j0 = 0; j0 < rows; j0 += 65535u) {
-    const uint32_t n = rows - j0 < 65535u ? rows - j0 : 65535u;
+  const uint32_t gw = (3 * (h_cfg->Rmax << 5) + 255) / 256, gd = (3 * (h_cfg->Rmax << 5) + 3 + 255) / 256;
+  return ul_row_chunks((uint32_t)n_tb * h_cfg->C, [&](uint32_t n, uint32_t j0) {
     launch_rm(dim3(gw, n), j0);
-    hipError_t err = hipGetLastError();
+    const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return err;
     hipLaunchKernelGGL(k_ul_deint_w, dim3(gd, n), dim3(256), 0, s, d_cfg, d_w, w_stride, d_dfull, d_stride, j0);
-    err = hipGetLastError();
-    if (err != hipSuccess) return err;
-  }
-  return hipSuccess;
+    return hipGetLastError();
+  });
 }
 
 hipError_t oai4g_launch_ul_rm_harq(const ul_dev_t *d_cfg, const ul_dev_t *h_cfg, int n_tb, const int16_t *d_e,

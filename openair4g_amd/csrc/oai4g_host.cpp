@@ -26,6 +26,7 @@
 #include "../../include/oai4g_tbs.h"
 #include "oai4g_internal.h"
 #include "oai4g_dev_buf.h"
+#include "oai4g_rm_geom.h"
 
 /* ------------------------------------------------------------------------------------------
  * errors
@@ -998,6 +999,19 @@ extern "C" int oai4g_qpp_fold32(uint32_t K, uint32_t *s_out, uint16_t *tab)
   return 1;
 }
 
+/* what the reference prints where Ncb < Kw before its rate matcher returns 0 (lte_rate_matching.c:518-521) */
+static void rm_condition_exit(const rm_ncb_t &g, uint32_t Nsoft)
+{
+  printf("Exiting, RM condition (Nir %u, Nsoft %u, Kw %u\n", g.Nir, Nsoft, g.Kw);
+}
+
+/* Compacted start of the circular buffer w[0..Ncb) of a block with R rows and the NULL list of size
+ * index ki, for redundancy version rv (lte_rate_matching.c:523-524): k0 less the NULLs below it */
+static uint32_t rm_k0c_of_rv(const cw_dev_t &c, uint32_t ki, uint32_t R, uint32_t Ncb, uint32_t rv)
+{
+  return rm_compact(rm_k0(R, Ncb, rv), rm_null_list{c.nullpos[ki], c.nnull[ki]});
+}
+
 static int derive_cfg(oai4g_tx_config *cfg, const oai4g_tx_params_t *p, const uint8_t Nl[2], bool need_remap,
                       int only_sf)
 {
@@ -1091,16 +1105,14 @@ static int derive_cfg(oai4g_tx_config *cfg, const oai4g_tx_params_t *p, const ui
       /* rate matching geometry */
       uint32_t D = K + 4, R = (D + 31) >> 5, Kpi = R << 5;
       c.R[r] = R; c.Kpi[r] = Kpi; c.ND[r] = Kpi - D;
-      uint32_t Kw = 3 * Kpi;
-      uint32_t Nir = OAI4G_NSOFT / p->Kmimo / (p->Mdlharq < 8 ? p->Mdlharq : 8);
-      uint32_t Ncb = (Nir / C < Kw) ? Nir / C : Kw;
-      if (Ncb < Kw && !p->rm_limited_buffer) {
-        printf("Exiting, RM condition (Nir %u, Nsoft %u, Kw %u\n", Nir, OAI4G_NSOFT, Kw);
-        set_err("RM condition: Ncb %u < Kw %u (the reference emits E=0, lte_rate_matching.c:518-521)", Ncb, Kw);
+      const rm_ncb_t g = rm_ncb(OAI4G_NSOFT, p->Kmimo, p->Mdlharq, C, R);
+      c.Ncb[r] = g.Ncb;
+      if (g.shorter && !p->rm_limited_buffer) {
+        rm_condition_exit(g, OAI4G_NSOFT);
+        set_err("RM condition: Ncb %u < Kw %u (the reference emits E=0, lte_rate_matching.c:518-521)", g.Ncb, g.Kw);
         rm_fail = true;
-        Ncb = Kw;
+        c.Ncb[r] = g.Kw;
       }   /* else (opt-in): the circular buffer is w[0..Ncb), 36.212 5.1.4.1.2 */
-      c.Ncb[r] = Ncb;
       c.kidx[r] = (C > 1 && r < Cm) ? 0 : 1;
     }
     if (src != (c.TBS + 24) / 8) { set_err("segmentation byte accounting mismatch"); return -1; }
@@ -1180,17 +1192,9 @@ static int derive_cfg(oai4g_tx_config *cfg, const oai4g_tx_params_t *p, const ui
       c.nnull[ki] = (uint32_t)n;
     }
     for (uint32_t r = 0; r < C; r++) {
-      uint32_t R = c.R[r], Ncb = c.Ncb[r], nn = c.nnull[c.kidx[r]];
-      const uint16_t *np = c.nullpos[c.kidx[r]];
-      uint32_t ncol8 = R << 3;
-      uint32_t k0 = R * (2 + p->rvidx[cw] * ((Ncb % ncol8 ? 1 : 0) + Ncb / ncol8) * 2);
-      uint32_t before = 0, inbuf = 0;
-      for (uint32_t i = 0; i < nn; i++) {
-        if (np[i] < k0) before++;
-        if (np[i] < Ncb) inbuf++;             /* NULLs inside the (possibly limited) circular buffer */
-      }
-      c.k0c[r] = k0 - before;
-      c.Nnn[r] = Ncb - inbuf;
+      /* k0 >= Ncb (limited buffer only) keeps k0 less the NULLs below it: enable_tb_rv refuses such a start */
+      c.k0c[r] = rm_k0c_of_rv(c, c.kidx[r], c.R[r], c.Ncb[r], p->rvidx[cw]);
+      c.Nnn[r] = rm_compact(c.Ncb[r], rm_null_list{c.nullpos[c.kidx[r]], c.nnull[c.kidx[r]]});   /* the (possibly limited) buffer */
     }
     uint32_t nw = (maxK + 31) >> 5;
     c.stream_words = nw + 3;   /* + tail word + read-ahead words */
@@ -1260,15 +1264,14 @@ static int derive_cfg(oai4g_tx_config *cfg, const oai4g_tx_params_t *p, const ui
       }
       if (G <= 0 || G > OAI4G_MAX_CHANNEL_BITS) { set_err("G=%d out of range", G); return -1; }
       c.G[sf] = (uint32_t)G;
-      uint32_t Gp = (uint32_t)G / Nl[cw] / c.Qm, GpmodC = Gp % C, off = 0;
+      uint32_t off = 0;
       for (uint32_t r = 0; r < C; r++) {
-        uint32_t E = (r < C - GpmodC) ? Nl[cw] * c.Qm * (Gp / C) : Nl[cw] * c.Qm * ((GpmodC ? 1 : 0) + Gp / C);
-        c.E[sf][r] = E;
+        c.E[sf][r] = rm_E((uint32_t)G, Nl[cw], c.Qm, C, r);
         c.roff[sf][r] = off;
-        off += E;
+        off += c.E[sf][r];
       }
       c.roff[sf][C] = off;
-      c.esplit[sf] = C - GpmodC;
+      c.esplit[sf] = rm_esplit((uint32_t)G, Nl[cw], c.Qm, C);
       for (int h = 0; h < 2; h++) {
         const uint32_t E = c.E[sf][h ? C - 1 : 0], w = (E + 31) / 32;
         c.ew[sf][h] = w;
@@ -1545,18 +1548,6 @@ extern "C" int oai4g_tx_encode(const oai4g_tx_config_t *cfg, int n_sf, const uin
   return 0;
 }
 
-/* Compacted start of the circular buffer for redundancy version rv and block size index ki
- * (lte_rate_matching.c:523-524: k0 = R (2 + rv ceil(Ncb / 8R) 2), less the NULLs below it), as
- * derive_cfg computes it per block for the configuration's own rvidx */
-static uint32_t rm_k0c_of_rv(const cw_dev_t &c, uint32_t ki, uint32_t rv)
-{
-  const uint32_t R = c.Rk[ki], Ncb = c.Ncbk[ki], ncol8 = R << 3;
-  const uint32_t k0 = R * (2 + rv * ((Ncb % ncol8 ? 1 : 0) + Ncb / ncol8) * 2);
-  uint32_t before = 0;
-  for (uint32_t i = 0; i < c.nnull[ki]; i++) before += c.nullpos[ki][i] < k0 ? 1u : 0u;
-  return k0 - before;
-}
-
 extern "C" int oai4g_tx_config_enable_tb_rv(oai4g_tx_config_t *cfg)
 {
   NEED_INIT(-1);
@@ -1574,8 +1565,8 @@ extern "C" int oai4g_tx_config_enable_tb_rv(oai4g_tx_config_t *cfg)
       enc_rv_tab_t &t = tabs[rv * n_cw + cw];
       memset(&t, 0, sizeof(t));
       /* with one block size (n0 = 0) index 0 mirrors index 1, whose NULL list is the size's */
-      c->k0ck[1] = rm_k0c_of_rv(*c, 1, rv);
-      c->k0ck[0] = c->n0 ? rm_k0c_of_rv(*c, 0, rv) : c->k0ck[1];
+      c->k0ck[1] = rm_k0c_of_rv(*c, 1, c->Rk[1], c->Ncbk[1], rv);
+      c->k0ck[0] = c->n0 ? rm_k0c_of_rv(*c, 0, c->Rk[0], c->Ncbk[0], rv) : c->k0ck[1];
       for (int ki = 0; ki < 2; ki++) {
         if (c->k0ck[ki] >= c->Nnnk[ki]) {
           set_err("tx_config_enable_tb_rv: rv %u starts at %u of %u circular-buffer entries", rv, c->k0ck[ki], c->Nnnk[ki]);
@@ -2000,18 +1991,12 @@ extern "C" uint32_t oai4g_lte_rate_matching_turbo(uint32_t RTC, uint32_t G, cons
   (void)nb_rb;
   (void)m;
   NEED_INIT(0);
-  uint32_t Kw = 3 * (RTC << 5);
-  uint32_t Nir = Nsoft / Kmimo / (Mdlharq < 8 ? Mdlharq : 8);
-  uint32_t Ncb = (Nir / C < Kw) ? Nir / C : Kw;
-  if (Ncb < Kw) {
-    printf("Exiting, RM condition (Nir %u, Nsoft %u, Kw %u\n", Nir, Nsoft, Kw);
+  const rm_ncb_t g = rm_ncb(Nsoft, Kmimo, Mdlharq, C, RTC);
+  if (g.shorter) {
+    rm_condition_exit(g, Nsoft);
     return 0;
   }
-  uint32_t Gp = G / Nl / Qm, GpmodC = Gp % C, E;
-  if (r < (C - GpmodC)) E = Nl * Qm * (Gp / C);
-  else E = Nl * Qm * ((GpmodC == 0 ? 0 : 1) + (Gp / C));
-  uint32_t ncol8 = RTC << 3;
-  uint32_t k0 = RTC * (2 + rvidx * ((Ncb % ncol8 ? 1 : 0) + Ncb / ncol8) * 2);
+  const uint32_t Ncb = g.Ncb, E = rm_E(G, Nl, Qm, C, r), k0 = rm_k0(RTC, Ncb, rvidx);
   stage_t st("lte_rate_matching_turbo");
   const int r_w = st.add(Ncb), r_e = st.add(E), r_s = st.add(4, 60);   /* s: the status word */
   if (!st.open()) return 0;
@@ -2081,8 +2066,7 @@ static int dlsch_encoding_retx(const oai4g_frame_parms_t *fp, uint8_t num_pdcch_
   }
   const int Gi = oai4g_get_G(fp, h->nb_rb, h->rb_alloc, (uint8_t)Qm, (uint8_t)Nl, num_pdcch_symbols, frame, subframe);
   if (Gi <= 0 || Gi > OAI4G_MAX_CHANNEL_BITS) { set_err("dlsch_encoding: G=%d out of range", Gi); return -1; }
-  const uint32_t G = (uint32_t)Gi, Gp = G / Nl / Qm, GpmodC = Gp % C;
-  const uint32_t Nir = OAI4G_NSOFT / dlsch->Kmimo / (dlsch->Mdlharq < 8 ? dlsch->Mdlharq : 8);
+  const uint32_t G = (uint32_t)Gi;
   /* device layout: w rows | block descriptors | status words (uploaded as 0) | e: the upload ends
    * behind the status words and the download starts at them */
   rm_blk_t blk[OAI4G_MAX_SEGMENTS];
@@ -2091,18 +2075,18 @@ static int dlsch_encoding_retx(const oai4g_frame_parms_t *fp, uint8_t num_pdcch_
   size_t wtot = 0;
   uint32_t etot = 0, max_Ncb = 0;
   for (uint32_t r = 0; r < C; r++) {
-    const uint32_t RTC = h->RTC[r], Kw = 3 * (RTC << 5);
-    if (RTC == 0 || Kw > OAI4G_W_BYTES) { set_err("dlsch_encoding: RTC[%u] = %u", r, RTC); return -1; }
-    const uint32_t Ncb = (Nir / C < Kw) ? Nir / C : Kw;
-    if (Ncb < Kw) {   /* lte_rate_matching_turbo returns 0: e untouched, r_offset stays (lte_rate_matching.c:518-521) */
-      printf("Exiting, RM condition (Nir %u, Nsoft %u, Kw %u\n", Nir, OAI4G_NSOFT, Kw);
+    const uint32_t RTC = h->RTC[r];
+    const rm_ncb_t g = rm_ncb(OAI4G_NSOFT, dlsch->Kmimo, dlsch->Mdlharq, C, RTC);
+    if (RTC == 0 || g.Kw > OAI4G_W_BYTES) { set_err("dlsch_encoding: RTC[%u] = %u", r, RTC); return -1; }
+    if (g.shorter) {   /* lte_rate_matching_turbo returns 0: e untouched, r_offset stays (lte_rate_matching.c:518-521) */
+      rm_condition_exit(g, OAI4G_NSOFT);
       continue;
     }
-    const uint32_t ncol8 = RTC << 3;
+    const uint32_t Ncb = g.Ncb;
     blk[r].woff = (uint32_t)wtot;
     blk[r].Ncb = Ncb;
-    blk[r].k0 = RTC * (2 + h->rvidx * ((Ncb % ncol8 ? 1 : 0) + Ncb / ncol8) * 2);
-    blk[r].E = r < C - GpmodC ? Nl * Qm * (Gp / C) : Nl * Qm * ((GpmodC ? 1 : 0) + Gp / C);
+    blk[r].k0 = rm_k0(RTC, Ncb, h->rvidx);
+    blk[r].E = rm_E(G, Nl, Qm, C, r);
     blk[r].eoff = etot;
     etot += blk[r].E;
     wtot += up256(Ncb);
@@ -2553,6 +2537,25 @@ extern "C" uint32_t oai4g_generate_dummy_w(uint32_t D, uint8_t *w, uint8_t F)
   return R;
 }
 
+/* compact (non-NULL) index of every position of w[0..Ncb) under generate_dummy_w's mask: the kernels' cidx table */
+static std::vector<uint32_t> rm_compact_index(const uint8_t *dw, uint32_t Ncb)
+{
+  std::vector<uint32_t> cidx(Ncb);
+  for (uint32_t q = 0, nn = 0; q < Ncb; q++) {
+    cidx[q] = nn;
+    nn += dw[q] != OAI4G_LTE_NULL ? 1u : 0u;
+  }
+  return cidx;
+}
+
+/* the receive side's compacted start of redundancy version rv (lte_rate_matching.c:743-745); with k0 >= Ncb the
+ * reference's first pass is empty and the selection starts at 0 */
+static uint32_t rm_rx_k0c(const uint8_t *dw, uint32_t R, uint32_t Ncb, uint32_t rv)
+{
+  const uint32_t k0 = rm_k0(R, Ncb, rv);
+  return k0 >= Ncb ? 0 : rm_compact(k0, rm_null_mask{dw, OAI4G_LTE_NULL});
+}
+
 /* ------------------------------------------------------------------------------------------
  * Batched UL receive chain (ulsch_decoding.c:1208-1350): n_tb transport blocks of one
  * configuration, e soft bits -> RM-rx + sub-block deinterleaving (k_ul_rm_deint) -> 16-bit turbo
@@ -2593,10 +2596,10 @@ extern "C" oai4g_ul_config_t *oai4g_ul_config_create(uint32_t B, uint32_t G, uin
   ul_dev_t &h = cfg->h;
   memset(&h, 0, sizeof(h));
   h.C = cfg->C;
-  const uint32_t C = cfg->C, Nir = Nsoft / (Mdlharq < 8 ? Mdlharq : 8), Gp = G / Qm, GpmodC = Gp % C;
+  const uint32_t C = cfg->C;
   uint32_t off = 0, npat = 0, keyK[3] = {0, 0, 0}, keyF[3] = {0, 0, 0};
   for (uint32_t r = 0; r < C; r++) {
-    h.E[r] = r < C - GpmodC ? Qm * (Gp / C) : Qm * ((GpmodC == 0 ? 0 : 1) + Gp / C);   /* Nl = 1 */
+    h.E[r] = rm_E(G, 1, Qm, C, r);   /* Nl = 1 */
     h.off[r] = off;
     off += h.E[r];
     const uint32_t K = r < cfg->Cminus ? cfg->Kminus : cfg->Kplus, Fr = r == 0 ? cfg->F : 0;
@@ -2611,26 +2614,12 @@ extern "C" oai4g_ul_config_t *oai4g_ul_config_create(uint32_t B, uint32_t G, uin
       std::vector<uint8_t> dw;
       P.D = K + 4;
       P.R = dummy_w_h(P.D, Fr, dw);
-      const uint32_t Kw = 3 * (P.R << 5);
-      P.Ncb = Nir / C < Kw ? Nir / C : Kw;
-      const uint32_t Ncbmod = P.Ncb % (P.R << 3);
-      const uint32_t k0 = P.R * (2 + (rvidx * (((Ncbmod == 0) ? 0 : 1) + (P.Ncb / (P.R << 3))) * 2));
-      std::vector<uint32_t> cidx(P.Ncb);
-      uint32_t nn = 0, k0c = 0;
-      for (uint32_t q = 0; q < P.Ncb; q++) {
-        if (q == k0) k0c = nn;
-        cidx[q] = nn;
-        if (dw[q] != OAI4G_LTE_NULL) nn++;
-      }
-      if (k0 >= P.Ncb) k0c = 0;
-      P.Nnn = nn;
-      P.k0c = k0c;
-      for (uint32_t rv = 0; rv < 4; rv++) {        /* every round's k0 (lte_rate_matching.c:743-745) */
-        const uint32_t k0r = P.R * (2 + (rv * (((Ncbmod == 0) ? 0 : 1) + (P.Ncb / (P.R << 3))) * 2));
-        uint32_t c = 0;
-        for (uint32_t q = 0; q < P.Ncb && q < k0r; q++) c += dw[q] != OAI4G_LTE_NULL;
-        P.k0cr[rv] = k0r >= P.Ncb ? 0 : c;
-      }
+      P.Ncb = rm_ncb(Nsoft, 1, Mdlharq, C, P.R).Ncb;   /* Kmimo = 1 */
+      const std::vector<uint32_t> cidx = rm_compact_index(dw.data(), P.Ncb);
+      P.Nnn = rm_compact(P.Ncb, rm_null_mask{dw.data(), OAI4G_LTE_NULL});
+      for (uint32_t rv = 0; rv < 4; rv++)          /* every round's k0 (lte_rate_matching.c:743-745) */
+        P.k0cr[rv] = rm_rx_k0c(dw.data(), P.R, P.Ncb, rv);
+      P.k0c = P.k0cr[rvidx];
       if (P.R > h.Rmax) h.Rmax = P.R;
       if (dd.upload(dw) != hipSuccess || dc.upload(cidx) != hipSuccess) {
         set_err("ul_config: device allocation failed");
@@ -2707,16 +2696,33 @@ static int ul_decode_rows(oai4g_ul_config_t *cfg, int n_tb, uint8_t *d_c, size_t
   return 0;
 }
 
+/* what the three batch entry points share: the stride checks (the caller words the error), and after the caller's own
+ * checks the work buffers, its rate-matching launch into cfg->d_dfull (0 or -1 with the error set) and the decoders */
+static bool ul_strides_ok(const oai4g_ul_config_t *cfg, size_t c_stride, size_t e_stride)
+{
+  return c_stride >= cfg->Kplus / 8 && e_stride >= cfg->G;
+}
+
+template <typename LaunchRm>
+static int ul_batch(oai4g_ul_config_t *cfg, int n_tb, uint8_t *d_c, size_t c_stride, uint8_t *d_iters, void *stream,
+                    LaunchRm launch_rm)
+{
+  if (ul_reserve(cfg, n_tb) != 0) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  if (launch_rm(s) != 0) return -1;
+  return ul_decode_rows(cfg, n_tb, d_c, c_stride, d_iters, s);
+}
+
 extern "C" int oai4g_ul_decode_batch(oai4g_ul_config_t *cfg, int n_tb, const int16_t *d_e, size_t e_stride,
                                      uint8_t *d_c, size_t c_stride, uint8_t *d_iters, void *stream)
 {
   NEED_INIT(-1);
   if (n_tb <= 0) return 0;
-  if (c_stride < cfg->Kplus / 8 || e_stride < cfg->G) { set_err("ul_decode_batch: strides too small"); return -1; }
-  if (ul_reserve(cfg, n_tb) != 0) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  HCK(oai4g_launch_ul_rm_deint(cfg->d.get(), &cfg->h, n_tb, d_e, e_stride, cfg->d_dfull.get(), cfg->d_stride, s), -1);
-  return ul_decode_rows(cfg, n_tb, d_c, c_stride, d_iters, s);
+  if (!ul_strides_ok(cfg, c_stride, e_stride)) { set_err("ul_decode_batch: strides too small"); return -1; }
+  return ul_batch(cfg, n_tb, d_c, c_stride, d_iters, stream, [&](hipStream_t s) {
+    HCK(oai4g_launch_ul_rm_deint(cfg->d.get(), &cfg->h, n_tb, d_e, e_stride, cfg->d_dfull.get(), cfg->d_stride, s), -1);
+    return 0;
+  });
 }
 
 extern "C" size_t oai4g_ul_config_w_entries(const oai4g_ul_config_t *cfg) { return 3 * ((size_t)cfg->h.Rmax << 5); }
@@ -2730,15 +2736,15 @@ extern "C" int oai4g_ul_decode_batch_harq(oai4g_ul_config_t *cfg, int n_tb, cons
   NEED_INIT(-1);
   if (n_tb <= 0) return 0;
   if (rvidx > 3 || clear > 1) { set_err("ul_decode_batch_harq: rvidx 0..3, clear 0 / 1"); return -1; }
-  if (c_stride < cfg->Kplus / 8 || e_stride < cfg->G || w_stride < oai4g_ul_config_w_entries(cfg)) {
+  if (!ul_strides_ok(cfg, c_stride, e_stride) || w_stride < oai4g_ul_config_w_entries(cfg)) {
     set_err("ul_decode_batch_harq: strides too small");
     return -1;
   }
-  if (ul_reserve(cfg, n_tb) != 0) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  HCK(oai4g_launch_ul_rm_harq(cfg->d.get(), &cfg->h, n_tb, d_e, e_stride, d_w, w_stride, rvidx, clear, cfg->d_dfull.get(),
-                              cfg->d_stride, s), -1);
-  return ul_decode_rows(cfg, n_tb, d_c, c_stride, d_iters, s);
+  return ul_batch(cfg, n_tb, d_c, c_stride, d_iters, stream, [&](hipStream_t s) {
+    HCK(oai4g_launch_ul_rm_harq(cfg->d.get(), &cfg->h, n_tb, d_e, e_stride, d_w, w_stride, rvidx, clear,
+                                cfg->d_dfull.get(), cfg->d_stride, s), -1);
+    return 0;
+  });
 }
 
 /* the same round with rv and clear per transport block (device arrays [n_tb]) */
@@ -2749,15 +2755,15 @@ extern "C" int oai4g_ul_decode_batch_harq_tb(oai4g_ul_config_t *cfg, int n_tb, c
   NEED_INIT(-1);
   if (n_tb <= 0) return 0;
   if (!cfg || !d_rv || !d_clear) { set_err("ul_decode_batch_harq_tb: null configuration, rv or clear array"); return -1; }
-  if (c_stride < cfg->Kplus / 8 || e_stride < cfg->G || w_stride < oai4g_ul_config_w_entries(cfg)) {
+  if (!ul_strides_ok(cfg, c_stride, e_stride) || w_stride < oai4g_ul_config_w_entries(cfg)) {
     set_err("ul_decode_batch_harq_tb: strides too small");
     return -1;
   }
-  if (ul_reserve(cfg, n_tb) != 0) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  HCK(oai4g_launch_ul_rm_harq_tb(cfg->d.get(), &cfg->h, n_tb, d_e, e_stride, d_w, w_stride, d_rv, d_clear, cfg->d_dfull.get(),
-                                 cfg->d_stride, s), -1);
-  return ul_decode_rows(cfg, n_tb, d_c, c_stride, d_iters, s);
+  return ul_batch(cfg, n_tb, d_c, c_stride, d_iters, stream, [&](hipStream_t s) {
+    HCK(oai4g_launch_ul_rm_harq_tb(cfg->d.get(), &cfg->h, n_tb, d_e, e_stride, d_w, w_stride, d_rv, d_clear,
+                                   cfg->d_dfull.get(), cfg->d_stride, s), -1);
+    return 0;
+  });
 }
 
 extern "C" uint8_t oai4g_phy_threegpplte_turbo_decoder16(const int16_t *y, uint8_t *decoded_bytes, uint16_t n,
@@ -2792,20 +2798,9 @@ extern "C" int oai4g_lte_rate_matching_turbo_rx(uint32_t RTC, uint32_t G, int16_
 {
   NEED_INIT(-1);
   if (Kmimo == 0 || Mdlharq == 0 || C == 0 || Qm == 0 || Nl == 0) return -1;
-  const uint32_t Nir = Nsoft / Kmimo / (Mdlharq < 8 ? Mdlharq : 8), Kw = 3 * (RTC << 5);
-  const uint32_t Ncb = Nir / C < Kw ? Nir / C : Kw, Gp = G / Nl / Qm, GpmodC = Gp % C;
-  const uint32_t E = r < C - GpmodC ? Nl * Qm * (Gp / C) : Nl * Qm * ((GpmodC == 0 ? 0 : 1) + Gp / C);
-  const uint32_t Ncbmod = Ncb % (RTC << 3);
-  const uint32_t k0 = RTC * (2 + (rvidx * (((Ncbmod == 0) ? 0 : 1) + (Ncb / (RTC << 3))) * 2));
-  /* compact (non-NULL) index of every w position, and of k0 */
-  std::vector<uint32_t> cidx(Ncb);
-  uint32_t nn = 0, k0c = 0;
-  for (uint32_t p = 0; p < Ncb; p++) {
-    if (p == k0) k0c = nn;
-    cidx[p] = nn;
-    if (dummy_w[p] != OAI4G_LTE_NULL) nn++;
-  }
-  if (k0 >= Ncb) k0c = 0;   /* the reference's first pass is empty; selection starts at 0 */
+  const uint32_t Ncb = rm_ncb(Nsoft, Kmimo, Mdlharq, C, RTC).Ncb, E = rm_E(G, Nl, Qm, C, r);
+  const std::vector<uint32_t> cidx = rm_compact_index(dummy_w, Ncb);
+  const uint32_t nn = rm_compact(Ncb, rm_null_mask{dummy_w, OAI4G_LTE_NULL}), k0c = rm_rx_k0c(dummy_w, RTC, Ncb, rvidx);
   if (nn == 0 && E > 0) { set_err("rate_matching_rx: no non-NULL entries"); return -1; }
   const size_t b_soft = (size_t)E * 2, b_w = (size_t)Ncb * 2, b_c = (size_t)Ncb * 4;
   stage_t st("rate_matching_rx");

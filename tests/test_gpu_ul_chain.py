@@ -61,8 +61,10 @@ def test_gpu_ul_chain_c5_batch(gpu):
 
 
 def test_gpu_ul_chain_rows_beyond_grid_y_limit(gpu):
-    """n_tb x C above gridDim.y's 65 535: k_ul_rm_deint runs in row chunks; the TBs on both sides
-    of every chunk boundary decode as the oracle does."""
+    """n_tb x C above 65 535 rows through k_ul_rm_deint_lds (E = 288 soft inputs per block take the
+    LDS-staged form, whose rows lie on gridDim.x, so nothing is chunked here); the TBs on both sides
+    of the 65 535 boundary decode as the oracle does.  The row chunks of the gridDim.y kernels are
+    test_gpu_ul_chain_harq_row_chunks's."""
     tbs, G, Qm, n_tb = 16, 288, 2, 70000
     e = _batch(tbs, G, Qm, n_tb, 9, 50, 20, n_unique=4)
     ub = gpu.UlDecodeBatch(tbs + 24, G, Qm, n_tb, max_iterations=4)
@@ -106,4 +108,56 @@ def test_gpu_ul_chain_harq_rounds_match_oracle(gpu, tbs, G, Qm):
                 assert np.array_equal(wg[t, r, :Ncb], w_o[t][r][:Ncb]), (rnd, t, r)
                 assert its[t, r] == it, (rnd, t, r, its[t, r], it)
                 assert np.array_equal(c[t, r, :len(d)], d), (rnd, t, r)
+    ub.close()
+
+
+@pytest.mark.parametrize("G", [32768, 32770])
+def test_gpu_ul_chain_lds_limit_and_global_form(gpu, G):
+    """One K = 40 block with E = G soft inputs on both sides of the 64 KB LDS limit: E = 32768 is the
+    last size k_ul_rm_deint_lds takes (all 64 KB of dynamic LDS), E = 32770 the first that goes to
+    k_ul_rm_deint, the global form, which no other case reaches.  Every circular-buffer position sums
+    about 250 soft inputs.  The global form at more than 65 535 rows (its row chunks, j0 > 0) would
+    need a 4.3 GB input and stays unrun: the chunk helper it shares with the HARQ kernels is what
+    test_gpu_ul_chain_harq_row_chunks covers."""
+    tbs, Qm, n_tb = 16, 2, 3
+    e = _batch(tbs, G, Qm, n_tb, G, 4, 60)
+    ub = gpu.UlDecodeBatch(tbs + 24, G, Qm, n_tb, max_iterations=4)
+    assert ub.C == 1 and ub.E(0) == G
+    ub.upload(e)
+    ub.launch()
+    its, c = ub.results()
+    for t in range(n_tb):
+        ref = O.ulsch_decode(e[t], tbs + 24, G, Qm, max_it=4)
+        for r, (it, d) in enumerate(ref):
+            assert its[t, r] == it, (t, r, its[t, r], it)
+            assert np.array_equal(c[t, r, :len(d)], d), (t, r)
+    ub.close()
+
+
+def test_gpu_ul_chain_harq_row_chunks(gpu):
+    """n_tb x C = 70 000 rows through the HARQ round (k_ul_rm_harq, then k_ul_deint_w), whose rows
+    lie on gridDim.y and run in chunks of 65 535: the second chunk starts at j0 = 65535.  Two rounds
+    (rv 0 with clear = 1, rv 2 with clear = 0); the soft buffers, iteration counts and decoded blocks
+    of the TBs on both sides of the chunk boundary match the oracle's."""
+    tbs, G, Qm, n_tb = 16, 288, 2, 70000
+    rng = np.random.default_rng(11)
+    pays = [rng.integers(0, 256, tbs // 8 + 8, dtype=np.uint8) for _ in range(4)]
+    check = (0, 1, 65534, 65535, 65536, n_tb - 1)
+    w_o = {t: [np.zeros(3 * 64 + 64, np.int16)] for t in check}          # K = 40: Kw = 3 * 64
+    ub = gpu.UlDecodeBatch(tbs + 24, G, Qm, n_tb, max_iterations=4)
+    assert ub.C == 1
+    for rnd, rv in enumerate((0, 2)):
+        codes = [(2 * np.array(ul_e(p, tbs, G, Qm, rv=rv), np.float64) - 1) * 20 for p in pays]
+        e = np.clip(np.round(np.stack(codes)[np.arange(n_tb) % 4] + rng.normal(0, 30, (n_tb, G))), -32768, 32767) \
+            .astype(np.int16)
+        ub.upload(e)
+        ub.launch_harq(rv, 1 if rnd == 0 else 0)
+        its, c = ub.results()
+        wg = ub.soft_buffers()                                           # 70 000 x 192 int16: 27 MB
+        for t in check:
+            ref = O.ulsch_decode_harq(e[t], tbs + 24, G, Qm, rv, 1 if rnd == 0 else 0, w_o[t], max_it=4)
+            (it, d), = ref
+            assert np.array_equal(wg[t, 0, :192], w_o[t][0][:192]), (rnd, t)
+            assert its[t, 0] == it, (rnd, t, its[t, 0], it)
+            assert np.array_equal(c[t, 0, :len(d)], d), (rnd, t)
     ub.close()

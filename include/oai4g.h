@@ -486,6 +486,102 @@ typedef struct {
 int oai4g_pbch_detect_batch(oai4g_pbch_front_config_t *cfg, int n, const int8_t *d_llr, oai4g_pbch_detect_t *d_out,
                             void *stream);
 
+/* ---------------- UE initial cell search: PSS timing ---------------- */
+/* FDD with the normal prefix, the hypothesis initial_sync tries first (PHY/LTE_TRANSPORT/initial_sync.c:274-372)
+ * and the only one the PBCH front accepts.  Refused (-1 / null, oai4g_last_error says which): TDD, the extended
+ * prefix, more than 2 receive antennas, N_RB_DL 15 (lte_sync_time_init's switch, lte_sync_time.c:157-186, has no
+ * 256-point case and leaves all-zero replicas), N_RB_DL 75 (idft1536) and every size the switch does not name.
+ *
+ * lte_sync_time_init's time-domain replicas (PHY/LTE_ESTIMATION/lte_sync_time.c:143-292): for Nid2 = 0, 1, 2 the 72
+ * entries of primary_synch<Nid2> (PHY/LTE_REFSIG/primary_synch.h), each component >> 2, from bin N - 36 on, DC
+ * skipped at the wrap (:151-154), inverse DFT of N = ofdm_symbol_size points with scale 1.  out [3][N] packed int16
+ * pairs.  Host only: no device is needed. */
+int oai4g_lte_sync_time_replicas(const oai4g_frame_parms_t *frame_parms, int32_t *out);
+/* lte_sync_time (lte_sync_time.c:357-517), bit-exact.  length = 5 samples_per_tti; for n = 0, 4, ... < length, every
+ * sequence s and antenna: dot_product(replica_s, rxdata + n, N, 15) (PHY/TOOLS/cdot_prod.c:40-118: per tap
+ * (xr yr + xi yi) >> 15 and (xr yi + xi (int16)(-yr)) >> 15 into two wrapping 32-bit sums, saturated to int16 at
+ * the end) and the same at n + length, the antennas added in int16 with wrap (:428-435); n >= length - N adds
+ * nothing (:420).  abs32 = re^2 + im^2 in int (:348-351), metric (abs32 >> 1) + (abs32 of the second half >> 1)
+ * compared as unsigned with peak_val from 0, strictly greater, n ascending then s (:477-489): all-zero input
+ * gives position 0, source 0.
+ *
+ * The batched form: d_rx [n][nb_antennas_rx][10 samples_per_tti] frames, d_peak [n] {peak_pos, peak_val, Nid2},
+ * d_corr null or [n][3][2 length], where only every fourth entry is written: sync_corr_ue0..2 after their abs32
+ * (:470-475).  Asynchronous on `stream`, no host visit.  Returns 0 or -1. */
+typedef struct oai4g_sync_config oai4g_sync_config_t;
+oai4g_sync_config_t *oai4g_sync_config_create(const oai4g_frame_parms_t *frame_parms, uint8_t nb_antennas_rx);
+void oai4g_sync_config_destroy(oai4g_sync_config_t *cfg);
+int oai4g_sync_time_batch(oai4g_sync_config_t *cfg, int n, const int32_t *d_rx, int32_t *d_peak, int32_t *d_corr,
+                          void *stream);
+/* The drop-in on one frame in host memory: rxdata[aa] holds 10 samples_per_tti words; returns peak_pos (or -1), the
+ * sequence in *eNB_id, the winning metric in *peak_val; sync_corr, when not null, receives [3][10 samples_per_tti]. */
+int oai4g_lte_sync_time(int32_t *const *rxdata, const oai4g_frame_parms_t *frame_parms, uint8_t nb_antennas_rx, int *eNB_id,
+                        uint32_t *peak_val, int32_t *sync_corr);
+
+/* ---------------- UE initial cell search: FEP at an offset, SSS cell id ---------------- */
+/* slot_fep (PHY/MODULATION/slot_fep.c:40-156) of `nsym` symbols from symbol 0 of slot `first_slot` on, with
+ * sample_offset = d_offset[f * offset_stride] of frame f, a device value: the windows are those of
+ * oai4g_slot_fep_offset, its - rx_offset % 4 alignment included (:118), taken modulo the frame length; a window that
+ * runs past the frame's end reads on from its start, where the reference's wrap extension holds that copy
+ * (:123-126).  d_rx [n][nb_antennas_rx][10 samples_per_tti]; symbol k of the run lands in row k of
+ * d_rxF + f * frame_stride + antenna * symbols_per_tti * N, the layout oai4g_fep_batch writes when frame_stride is
+ * 0 (= nb_antennas_rx * symbols_per_tti * N words).  1 <= nsym <= symbols_per_tti: the PBCH stage's fifteenth symbol
+ * (symbol 0 of slot 2, initial_sync.c:87-92) is a second call, into the row the estimation reads it from.
+ * Scope and refusals as above.  Asynchronous on `stream`.  Returns 0 or -1. */
+int oai4g_fep_offset_batch(const oai4g_frame_parms_t *frame_parms, int n, int nb_antennas_rx, const int32_t *d_rx,
+                           const int32_t *d_offset, uint32_t offset_stride, uint8_t first_slot, int nsym, int32_t *d_rxF,
+                           size_t frame_stride, void *stream);
+/* What the search knows of a frame's cell.  status 0: found; 1: "SSS error condition" (initial_sync.c:373-376), the
+ * frame has no cell (Nid_cell -1). */
+typedef struct {
+  int32_t Nid_cell, rx_offset, metric, flip, phase, status;
+} oai4g_cell_t;
+/* initial_sync's offset arithmetic and rx_sss per frame, from d_peak on the device (initial_sync.c:310-362, FDD,
+ * normal prefix): sync_pos2 = peak_pos - nb_prefix_samples (plus the frame length when negative), sync_pos_slot =
+ * samples_per_tti / 2 - N - nb_prefix_samples, rx_offset = sync_pos2 - sync_pos_slot (plus the frame length when
+ * negative); rx_sss runs only when 0 <= sync_pos2 - sync_pos_slot < frame - samples_per_tti / 2 (:353-354).
+ * rx_sss (PHY/LTE_TRANSPORT/sss.c:222-391): slot_fep of symbols 5 and 6 of slot 0, then of slot 10, at rx_offset;
+ * pss_sss_extract (:157-215: 72 words per symbol, rxF[N - 36 ..] for three RBs, then rxF[1 ..]); pss_ch_est
+ * (:93-154) over the 62 words from word 5 against &primary_synch<Nid2>[10], every >> 15 and (int16_t) cast where
+ * the reference has them (:132-137), antenna 0 in place and antenna 1 added in int16; the search (:356-388) over
+ * flip 0..1, phase 0..6 (phase_re / phase_im, :218-219) and Nid1 0..167 of the sum of the 62 terms
+ * (int16_t)(d0[i] A0 + d5[i] A5), A = ((phase_re re) >> 19) - ((phase_im im) >> 19), flip 1 swapping the tables; the
+ * first strictly greater metric from -99999999 wins.  With flip = 1 the reported rx_offset has the half frame added
+ * (initial_sync.c:361-362).  d_cell [n].  Asynchronous on `stream`, no host visit.  Returns 0 or -1. */
+int oai4g_sss_batch(oai4g_sync_config_t *cfg, int n, const int32_t *d_rx, const int32_t *d_peak, oai4g_cell_t *d_cell,
+                    void *stream);
+/* The same without the slot_fep calls, on the caller's rows d_rows [n][nb_antennas_rx][4][N]: symbols 5 and 6 of slot
+ * 0, then of slot 10.  The forward DFT's last level scales by 1/sqrt(2) or 1/2, which keeps slot_fep's output at or
+ * below 23170 per component, so the wraps of pss_ch_est's (int16_t) casts can only be reached with rows given
+ * directly. */
+int oai4g_sss_rows_batch(oai4g_sync_config_t *cfg, int n, const int32_t *d_rows, const int32_t *d_peak, oai4g_cell_t *d_cell,
+                         void *stream);
+/* The drop-in for rx_sss on one frame in host memory, rxdata[aa] of 10 samples_per_tti words: Nid2 is
+ * lte_ue_common_vars.eNb_id, rx_offset is phy_vars_ue->rx_offset.  Returns the Nid_cell rx_sss leaves in the frame
+ * parameters (or -1), and *tot_metric, *flip_max, *phase_max. */
+int oai4g_rx_sss(int32_t *const *rxdata, const oai4g_frame_parms_t *frame_parms, uint8_t nb_antennas_rx, uint8_t Nid2,
+                 int rx_offset, int32_t *tot_metric, uint8_t *flip_max, uint8_t *phase_max);
+/* initial_sync's first hypothesis (PHY/LTE_TRANSPORT/initial_sync.c:290-372: FDD, normal prefix) on one frame in host
+ * memory: oai4g_lte_sync_time (:305), the offset arithmetic (:310-354), oai4g_rx_sss (:358), the frame parameters
+ * of the found cell (:359-365), pbch_detection (:57-161): slot_fep of slots 0 and 1 and of symbol 0 of slot 2 at
+ * rx_offset (:69-92), the channel estimation of nb_ports (1 or 2) ports, oai4g_rx_pbch_front and the
+ * eight-hypothesis search.  frame_parms gives N_RB_DL; phy_adjust_gain and the rx_power / lte_ue_measurements
+ * bookkeeping (:320-341, :94-109) are not part of it.  Returns 0 with *out filled, or -1: no PBCH found
+ * (oai4g_last_error() empty; Nid_cell and rx_offset are still reported), the SSS error condition (Nid_cell -1), or a
+ * refused call.
+ * A batch of frames of unknown cells ends on the device at oai4g_sss_batch's d_cell: the estimation and PBCH
+ * configurations are per cell, so the caller reads those few bytes, groups the frames by cell, and runs
+ * oai4g_fep_offset_batch -> oai4g_chest_batch -> oai4g_pbch_front_batch / oai4g_pbch_detect_batch per group. */
+typedef struct {
+  int32_t Nid_cell, rx_offset;
+  uint8_t tx_ant;            /* 1 / 2, or 0xFF: no PBCH found */
+  uint8_t frame_mod4, mimo_mode;
+  uint8_t mib[3];
+  uint8_t pad[2];
+} oai4g_initial_sync_t;
+int oai4g_initial_sync(int32_t *const *rxdata, const oai4g_frame_parms_t *frame_parms, uint8_t nb_antennas_rx, uint8_t nb_ports,
+                       uint32_t high_speed_flag, oai4g_initial_sync_t *out);
+
 /* ---------------- UE PHICH reception ---------------- */
 /* rx_phich's numeric core (PHY/LTE_TRANSPORT/phich.c:1112-1346, normal prefix, normal duration): the 12
  * scrambling signs of c_init = ((subframe + 1)(Nid_cell + 1) << 9) + Nid_cell, the 24 signs d of nseq_PHICH

@@ -429,6 +429,26 @@ _SIGS = {
                                               ctypes.c_void_p]),
     "oai4g_pbch_detect_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_void_p]),
+    "oai4g_lte_sync_time_replicas": (ctypes.c_int, [ctypes.POINTER(FrameParms), ctypes.c_void_p]),
+    "oai4g_sync_config_create": (ctypes.c_void_p, [ctypes.POINTER(FrameParms), ctypes.c_uint8]),
+    "oai4g_sync_config_destroy": (None, [ctypes.c_void_p]),
+    "oai4g_sync_time_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_void_p]),
+    "oai4g_lte_sync_time": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(FrameParms), ctypes.c_uint8,
+                                           ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint32),
+                                           ctypes.c_void_p]),
+    "oai4g_fep_offset_batch": (ctypes.c_int, [ctypes.POINTER(FrameParms), ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint8, ctypes.c_int,
+                                              ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "oai4g_sss_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_void_p]),
+    "oai4g_sss_rows_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p]),
+    "oai4g_rx_sss": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(FrameParms), ctypes.c_uint8,
+                                    ctypes.c_uint8, ctypes.c_int, ctypes.POINTER(ctypes.c_int32),
+                                    ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8)]),
+    "oai4g_initial_sync": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(FrameParms), ctypes.c_uint8,
+                                          ctypes.c_uint8, ctypes.c_uint32, ctypes.c_void_p]),
     "oai4g_rx_phich": (ctypes.c_int, [ctypes.POINTER(FrameParms), ctypes.c_uint8, ctypes.c_void_p, ctypes.c_uint8,
                                       ctypes.c_uint8, ctypes.POINTER(ctypes.c_int16)]),
     "oai4g_phich_rx_config_create": (ctypes.c_void_p, [ctypes.POINTER(FrameParms), ctypes.c_uint8, ctypes.c_uint8]),
@@ -1503,6 +1523,133 @@ class PbchFrontBatch(_EstPlanes):
 
     def detected(self):
         return self._get(self.d_out, self.n, PbchDetect)
+
+
+def lte_sync_time_replicas(fp):
+    """oai4g_lte_sync_time_replicas: lte_sync_time_init's three time-domain PSS replicas, int16 [3][N][2].  Host only."""
+    out = np.zeros((3, fp.ofdm_symbol_size, 2), dtype=np.int16)
+    _check(lib().oai4g_lte_sync_time_replicas(ctypes.byref(fp), _ptr(out)) == 0)
+    return out
+
+
+def lte_sync_time(rxdata, fp, want_corr=False):
+    """oai4g_lte_sync_time on one frame: rxdata[a] int32 [10 samples_per_tti] -> (peak_pos, Nid2, peak_val), and
+    with want_corr the three correlation buffers int32 [3][10 samples_per_tti] (every fourth entry is defined)."""
+    init()
+    fl = 10 * fp.samples_per_tti
+    keep = [np.ascontiguousarray(a, dtype=np.int32).ravel() for a in rxdata]
+    assert all(a.size == fl for a in keep)
+    rx = (ctypes.c_void_p * len(keep))(*[a.ctypes.data for a in keep])
+    corr = np.zeros((3, fl), dtype=np.int32) if want_corr else None
+    src, val = ctypes.c_int(-1), ctypes.c_uint32(0)
+    pos = lib().oai4g_lte_sync_time(rx, ctypes.byref(fp), len(keep), ctypes.byref(src), ctypes.byref(val),
+                                    _ptr(corr) if want_corr else None)
+    _check(pos >= 0)
+    return (pos, src.value, val.value) + ((corr,) if want_corr else ())
+
+
+def rx_sss(rxdata, fp, Nid2, rx_offset):
+    """oai4g_rx_sss on one frame: rxdata[a] int32 [10 samples_per_tti] -> (Nid_cell, tot_metric, flip_max, phase_max)"""
+    init()
+    keep = [np.ascontiguousarray(a, dtype=np.int32).ravel() for a in rxdata]
+    assert all(a.size == 10 * fp.samples_per_tti for a in keep)
+    rx = (ctypes.c_void_p * len(keep))(*[a.ctypes.data for a in keep])
+    metric, flip, phase = ctypes.c_int32(0), ctypes.c_uint8(0), ctypes.c_uint8(0)
+    nid = lib().oai4g_rx_sss(rx, ctypes.byref(fp), len(keep), Nid2, rx_offset, ctypes.byref(metric), ctypes.byref(flip),
+                             ctypes.byref(phase))
+    _check(nid >= 0)
+    return nid, metric.value, flip.value, phase.value
+
+
+class InitialSync(ctypes.Structure):
+    """oai4g_initial_sync_t"""
+    _fields_ = [("Nid_cell", ctypes.c_int32), ("rx_offset", ctypes.c_int32), ("tx_ant", ctypes.c_uint8),
+                ("frame_mod4", ctypes.c_uint8), ("mimo_mode", ctypes.c_uint8), ("mib", ctypes.c_uint8 * 3),
+                ("pad", ctypes.c_uint8 * 2)]
+
+
+def initial_sync(rxdata, fp, nb_ports=2, high_speed_flag=1):
+    """oai4g_initial_sync on one frame: (0 or -1 when no PBCH was found, the InitialSync record); a refused call
+    raises."""
+    init()
+    keep = [np.ascontiguousarray(a, dtype=np.int32).ravel() for a in rxdata]
+    assert all(a.size == 10 * fp.samples_per_tti for a in keep)
+    rx = (ctypes.c_void_p * len(keep))(*[a.ctypes.data for a in keep])
+    out = InitialSync()
+    r = lib().oai4g_initial_sync(rx, ctypes.byref(fp), len(keep), nb_ports, high_speed_flag, ctypes.byref(out))
+    err = lib().oai4g_last_error()
+    _check(r == 0 or not err or b"SSS error condition" in err)
+    return r, out
+
+
+class Cell(ctypes.Structure):
+    """oai4g_cell_t"""
+    _fields_ = [(k, ctypes.c_int32) for k in ("Nid_cell", "rx_offset", "metric", "flip", "phase", "status")]
+
+
+class _SyncBatch(_DeviceOwner):
+    """Device-resident cell search of n frames: d_rx [n][nb_rx][10 samples_per_tti] -> d_peak [n] {peak_pos,
+    peak_val, Nid2} (oai4g_sync_time_batch) -> d_cell [n] Cell (oai4g_sss_batch); d_corr [n][3][10 samples_per_tti]
+    exists once a launch asked for it.  fep() is oai4g_fep_offset_batch of these frames at the offsets in d_cell.
+    Handed out by sync_batch()."""
+
+    def __init__(self, fp, n, nb_rx):
+        self.L, self.fp, self.n, self.nb_rx = init(), fp, n, nb_rx
+        self.frame = 10 * fp.samples_per_tti
+        self.cfg = self._own(self.L.oai4g_sync_config_create(ctypes.byref(fp), nb_rx), self.L.oai4g_sync_config_destroy)
+        self.d_rx = self._dev(n * nb_rx * self.frame * 4)
+        self.d_peak = self._dev(n * 12)
+        self.d_cell = self._dev(n * ctypes.sizeof(Cell))
+        self.d_corr = None
+
+    def upload_peaks(self, peaks):
+        """int32 [n][3] in place of the PSS stage's result"""
+        peaks = np.ascontiguousarray(peaks, dtype=np.int32)
+        assert peaks.size == 3 * self.n
+        self._put(self.d_peak, peaks)
+
+    def launch_sss(self, stream=None):
+        _check(self.L.oai4g_sss_batch(self.cfg, self.n, self.d_rx, self.d_peak, self.d_cell, stream) == 0)
+
+    def launch_sss_rows(self, d_rows, stream=None):
+        """the SSS stage on given rows [n][nb_rx][4][N] in place of its own FEP (oai4g_sss_rows_batch)"""
+        _check(self.L.oai4g_sss_rows_batch(self.cfg, self.n, d_rows, self.d_peak, self.d_cell, stream) == 0)
+
+    def cells(self):
+        return self._get(self.d_cell, self.n, Cell)
+
+    def fep(self, d_rxF, first_slot, nsym, frames=None, frame_stride=0, stream=None):
+        """the frames (all, or the listed ones in that order) at their rx_offset: rows of d_rxF + i * frame_stride"""
+        runs = [(0, self.n)] if frames is None else [(f, 1) for f in frames]
+        step = (frame_stride or self.nb_rx * self.fp.symbols_per_tti * self.fp.ofdm_symbol_size) * 4
+        for i, (f, k) in enumerate(runs):
+            _check(self.L.oai4g_fep_offset_batch(ctypes.byref(self.fp), k, self.nb_rx, self.d_rx + f * self.nb_rx * self.frame * 4,
+                                                 self.d_cell + f * ctypes.sizeof(Cell) + 4, 6, first_slot, nsym,
+                                                 d_rxF + i * step, frame_stride, stream) == 0)
+
+    def upload(self, rx):
+        """int32 [n][nb_rx][10 samples_per_tti]"""
+        rx = np.ascontiguousarray(rx, dtype=np.int32)
+        assert rx.size == self.n * self.nb_rx * self.frame
+        self._put(self.d_rx, rx)
+
+    def launch(self, want_corr=False, stream=None):
+        if want_corr and self.d_corr is None:
+            self.d_corr = self._dev(self.n * 3 * self.frame * 4)
+        _check(self.L.oai4g_sync_time_batch(self.cfg, self.n, self.d_rx, self.d_peak,
+                                            self.d_corr if want_corr else None, stream) == 0)
+
+    def peaks(self):
+        """int32 [n][3]: peak_pos, peak_val (the unsigned metric's bits), Nid2"""
+        return self._get(self.d_peak, (self.n, 3), np.int32)
+
+    def corr(self):
+        return self._get(self.d_corr, (self.n, 3, self.frame), np.int32)
+
+
+def sync_batch(fp, n, nb_rx):
+    """the device-resident cell search of n frames of nb_rx antennas"""
+    return _SyncBatch(fp, n, nb_rx)
 
 
 def rx_phich(fp, subframe, comp, ngroup, nseq):

@@ -411,6 +411,66 @@ __global__ void __launch_bounds__(128) k_fep(const int32_t *__restrict__ in, int
   }
 }
 
+/* ======================================================================================
+ * k_fep_offset: slot_fep at a sample offset that is a device value per frame (initial cell search: the offset
+ * comes out of the PSS / SSS stage).  Unit s = (frame * n_ant + antenna) * nsym + sym; the window of symbol sym
+ * starts where slot_fep.c:105-150 puts it, in unsigned arithmetic: (offset + pre[sym]) rounded down to a
+ * multiple of 4, plus post[sym], modulo the frame; a window that runs past the frame's end reads on from its
+ * start (the reference's wrap extension holds that copy).
+ * ==================================================================================== */
+template <int LOG2N>
+__global__ void __launch_bounds__(128) k_fep_offset(const int32_t *__restrict__ in, int32_t *__restrict__ out,
+                                                    fep_offset_args_t a, const uint32_t *__restrict__ twf)
+{
+  constexpr int N = 1 << LOG2N, T = N >> 4, UNITS = 128 / T, LDSW = dft_sel<LOG2N>::XW;
+  __shared__ uint32_t lds_all[UNITS * LDSW];
+  const int unit = threadIdx.x / T, t = threadIdx.x % T;
+  typename dft_sel<LOG2N>::tw_t twr;
+  twr.load(twf, t);
+  uint32_t *la = lds_all + unit * LDSW;
+  for (int s0 = blockIdx.x * UNITS; s0 < a.n_units; s0 += gridDim.x * UNITS) {
+    const int s = s0 + unit;
+    const bool active = s < a.n_units;
+    const int item = active ? s / a.nsym : 0, sym = active ? s - item * a.nsym : 0;
+    const int frame = item / (int)a.n_ant, ant = item - frame * (int)a.n_ant;
+    gu32_t *src = (gu32_t *)in + (size_t)item * a.frame_len;
+    uint32_t *dst = (uint32_t *)out + (size_t)frame * a.out_frame_stride + (size_t)ant * a.out_ant_stride + (size_t)sym * N;
+    uint32_t off = (uint32_t)a.offset[(size_t)frame * a.offset_stride] + a.pre[sym];
+    off = (off - (off & 3u) + a.post[sym]) % a.frame_len;
+    const uint32_t len = a.frame_len;
+    auto prod = [&](s16x2 *x) {
+#pragma unroll
+      for (int n = 0; n < 16; n++) {
+        uint32_t i = off + (uint32_t)(t + T * n);
+        i = (i >= len) ? i - len : i;
+        x[n] = u2c(src[i]);
+      }
+    };
+    auto cons = [&](int f, s16x2 y) { dst[f] = c2u(y); };
+    if constexpr (LOG2N == 11) dft2048_unit(la, t, active, twr, prod, cons, a.scale);
+    else dft_unit<LOG2N>(la, t, active, twr, prod, cons, a.scale);
+    __syncthreads();   /* the next round's leaf stores reuse la */
+  }
+}
+
+hipError_t oai4g_launch_fep_offset(const int32_t *d_in, int32_t *d_out, int log2n, const fep_offset_args_t &a,
+                                   const uint32_t *d_twf, int n_cu, hipStream_t s)
+{
+  if (a.n_units <= 0) return hipSuccess;
+  if (a.nsym <= 0 || a.nsym > OAI4G_FEP_OFFSET_MAX_SYM || a.n_ant == 0 || a.frame_len < (1u << log2n)) return hipErrorInvalidValue;
+  const int units = 128 / ((1 << log2n) >> 4);
+  const int need = (a.n_units + units - 1) / units, cap = n_cu * OAI4G_FEP_WG_PER_CU;
+  const dim3 grid(need < cap ? need : cap), blk(128);
+  switch (log2n) {
+  case 7: hipLaunchKernelGGL(k_fep_offset<7>, grid, blk, 0, s, d_in, d_out, a, d_twf); break;
+  case 9: hipLaunchKernelGGL(k_fep_offset<9>, grid, blk, 0, s, d_in, d_out, a, d_twf); break;
+  case 10: hipLaunchKernelGGL(k_fep_offset<10>, grid, blk, 0, s, d_in, d_out, a, d_twf); break;
+  case 11: hipLaunchKernelGGL(k_fep_offset<11>, grid, blk, 0, s, d_in, d_out, a, d_twf); break;
+  default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
 hipError_t oai4g_launch_fep(const int32_t *d_in, int32_t *d_out, int log2n, const fep_args_t &a,
                             const uint32_t *d_twf, int n_cu, hipStream_t s)
 {

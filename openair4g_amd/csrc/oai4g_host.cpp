@@ -5919,3 +5919,474 @@ extern "C" int oai4g_phich_rx_batch(const oai4g_phich_rx_config_t *cfg, const in
   HCK(oai4g_launch_phich_rx(a, (hipStream_t)stream), -1);
   return 0;
 }
+
+/* ------------------------------------------------------------------------------------------
+ * UE initial cell search: lte_sync_time (PHY/LTE_ESTIMATION/lte_sync_time.c), k_sync_time.
+ * ---------------------------------------------------------------------------------------- */
+/* The fixed-point inverse DFT of lte_dfts.c on the host, for the three replicas only (they are derived
+ * once per configuration and pinned without a device): the arithmetic of oai4g_dft_prims.h word for word. */
+namespace {
+struct hc16 {
+  int16_t r, i;
+};
+inline int16_t h_sat16(int32_t v) { return (int16_t)(v > 32767 ? 32767 : (v < -32768 ? -32768 : v)); }
+inline int16_t h_wrap16(int32_t v) { return (int16_t)(uint16_t)(uint32_t)v; }
+inline hc16 h_adds(hc16 a, hc16 b) { return {h_sat16(a.r + b.r), h_sat16(a.i + b.i)}; }
+inline hc16 h_subs(hc16 a, hc16 b) { return {h_sat16(a.r - b.r), h_sat16(a.i - b.i)}; }
+inline hc16 h_addw(hc16 a, hc16 b) { return {h_wrap16(a.r + b.r), h_wrap16(a.i + b.i)}; }
+inline hc16 h_flip(hc16 a) { return {a.i, h_wrap16(-(int32_t)a.r)}; }
+inline hc16 h_pack(uint32_t re, uint32_t im) { return {h_sat16((int32_t)re >> 15), h_sat16((int32_t)im >> 15)}; }
+inline hc16 h_tw(int N, int m)
+{
+  hc16 t;
+  twiddle_host(N, m, &t.r, &t.i);
+  return t;
+}
+/* x conj(t) in 32 bits, as unsigned so that the sums behind it wrap */
+inline void h_mulc(hc16 x, hc16 t, uint32_t &re, uint32_t &im)
+{
+  re = (uint32_t)((int32_t)x.r * t.r + (int32_t)x.i * t.i);
+  im = (uint32_t)((int32_t)x.r * (int32_t)h_wrap16(-(int32_t)t.i) + (int32_t)x.i * t.r);
+}
+inline hc16 h_mulc16(hc16 x, hc16 t)
+{
+  uint32_t re, im;
+  h_mulc(x, t, re, im);
+  return h_pack(re, im);
+}
+inline void h_r4inv(hc16 p0, hc16 p1, hc16 p2, hc16 p3, hc16 &o0, hc16 &o1, hc16 &o2, hc16 &o3)
+{
+  const hc16 s02 = h_adds(p0, p2), s13 = h_adds(p1, p3), d02 = h_subs(p0, p2), d13 = h_subs(h_flip(p1), h_flip(p3));
+  o0 = h_adds(s02, s13);
+  o2 = h_subs(s02, s13);
+  o3 = h_adds(d02, d13);
+  o1 = h_subs(d02, d13);
+}
+/* y = IDFT(x) of 2^l2 points with the size's own scaling (idft64 >> 3, radix-4 levels >> 1, radix-2 levels x 23170 >> 15) */
+void h_idft(int l2, const hc16 *x, hc16 *y)
+{
+  const int N = 1 << l2;
+  if (l2 == 4) {
+    hc16 S[4][4], B[4][4];
+    for (int j = 0; j < 4; j++) h_r4inv(x[j], x[4 + j], x[8 + j], x[12 + j], S[0][j], S[1][j], S[2][j], S[3][j]);
+    for (int j = 0; j < 4; j++)
+      for (int k = 0; k < 4; k++) B[j][k] = j == 0 ? S[k][j] : h_mulc16(S[k][j], h_tw(16, j * k));
+    for (int k = 0; k < 4; k++) h_r4inv(B[0][k], B[1][k], B[2][k], B[3][k], y[k], y[4 + k], y[8 + k], y[12 + k]);
+    return;
+  }
+  const int R = (l2 & 1) ? 2 : 4, M = N / R;
+  std::vector<hc16> blk(N), Y(N);
+  for (int r = 0; r < R; r++) {
+    for (int n = 0; n < M; n++) blk[r * M + n] = x[R * n + r];
+    h_idft(l2 - (R == 2 ? 1 : 2), &blk[r * M], &Y[r * M]);
+  }
+  for (int k = 0; k < M; k++) {
+    if (l2 == 6) {
+      h_r4inv(Y[k], h_mulc16(Y[M + k], h_tw(64, k)), h_mulc16(Y[2 * M + k], h_tw(64, 2 * k)), h_mulc16(Y[3 * M + k], h_tw(64, 3 * k)),
+              y[k], y[M + k], y[2 * M + k], y[3 * M + k]);
+    } else if (R == 4) {
+      uint32_t a1r, a1i, a2r, a2i, a3r, a3i;
+      h_mulc(Y[M + k], h_tw(N, k), a1r, a1i);
+      h_mulc(Y[2 * M + k], h_tw(N, 2 * k), a2r, a2i);
+      h_mulc(Y[3 * M + k], h_tw(N, 3 * k), a3r, a3i);
+      y[k] = h_addw(Y[k], h_pack(a1r + a2r + a3r, a1i + a2i + a3i));
+      y[3 * M + k] = h_addw(Y[k], h_pack(a1i - (a2r + a3i), a3r - a2i - a1r));
+      y[2 * M + k] = h_addw(Y[k], h_pack(a2r - a3r - a1r, a2i - a3i - a1i));
+      y[M + k] = h_addw(Y[k], h_pack(a3i - a2r - a1i, a1r - (a2i + a3r)));
+    } else {
+      uint32_t a0r, a0i, a1r, a1i;
+      h_mulc(Y[k], hc16{32767, 0}, a0r, a0i);
+      h_mulc(Y[M + k], h_tw(N, k), a1r, a1i);
+      y[k] = h_pack(a0r + a1r, a0i + a1i);
+      y[M + k] = h_pack(a0r - a1r, a0i - a1i);
+    }
+  }
+  for (int k = 0; k < N; k++) {
+    if (l2 == 6) y[k] = {(int16_t)(y[k].r >> 3), (int16_t)(y[k].i >> 3)};
+    else if (R == 4) y[k] = {(int16_t)(y[k].r >> 1), (int16_t)(y[k].i >> 1)};
+    else y[k] = {h_wrap16((((int32_t)y[k].r * 23170) >> 16) << 1), h_wrap16((((int32_t)y[k].i * 23170) >> 16) << 1)};
+  }
+}
+}  // namespace
+
+/* what the cell search is defined for: FDD, the normal prefix, 1 or 2 receive antennas, and the sizes for which
+ * lte_sync_time_init's switch (:157-186) builds replicas with an inverse DFT this library has */
+static bool sync_ok(const char *who, const oai4g_frame_parms_t *fp, uint32_t nb_rx)
+{
+  if (!fp) { set_err("%s: null frame parameters", who); return false; }
+  if (fp->frame_type != 0) { set_err("%s: TDD is not supported", who); return false; }
+  if (fp->Ncp != 0) { set_err("%s: the extended prefix is not supported", who); return false; }
+  if (nb_rx < 1 || nb_rx > 2) { set_err("%s: %u receive antennas (1 or 2 are supported)", who, nb_rx); return false; }
+  if (fp->N_RB_DL == 15) { set_err("%s: N_RB_DL 15 has no 256-point case in lte_sync_time_init: its replicas are all zero", who); return false; }
+  if (fp->N_RB_DL == 75) { set_err("%s: N_RB_DL 75 (idft1536) is not supported", who); return false; }
+  const uint32_t N = fp->N_RB_DL == 6 ? 128u : fp->N_RB_DL == 25 ? 512u : fp->N_RB_DL == 50 ? 1024u : fp->N_RB_DL == 100 ? 2048u : 0u;
+  if (N == 0 || fp->ofdm_symbol_size != N || fp->samples_per_tti != 15u * N) {
+    set_err("%s: N_RB_DL %u with ofdm_symbol_size %u is not supported", who, fp->N_RB_DL, fp->ofdm_symbol_size);
+    return false;
+  }
+  return true;
+}
+
+/* lte_sync_time_init (:143-292): primary_synch<Nid2>[0..71] >> 2 from bin N - 36 on, DC skipped at the wrap, inverse
+ * DFT with scale 1.  Entries 5..66 of the reference's 72 are the Zadoff-Chu values, the rest are 0. */
+extern "C" int oai4g_lte_sync_time_replicas(const oai4g_frame_parms_t *fp, int32_t *out)
+{
+  if (!sync_ok("lte_sync_time_replicas", fp, 1) || !out) { if (fp && !out) set_err("lte_sync_time_replicas: null output"); return -1; }
+  const uint32_t N = fp->ofdm_symbol_size;
+  std::vector<hc16> F(N), T(N);
+  for (uint32_t s = 0; s < 3; s++) {
+    int16_t v[62][2];
+    pss_table(s, v);
+    std::fill(F.begin(), F.end(), hc16{0, 0});
+    uint32_t k = N - 36;
+    for (uint32_t i = 0; i < 72; i++) {
+      if (i >= 5 && i < 67) F[k] = {(int16_t)(v[i - 5][0] >> 2), (int16_t)(v[i - 5][1] >> 2)};
+      if (++k >= N) k = k + 1 - N;
+    }
+    h_idft(fp->log2_symbol_size, F.data(), T.data());
+    memcpy(out + (size_t)s * N, T.data(), (size_t)N * 4);
+  }
+  return 0;
+}
+
+struct oai4g_sync_config {
+  oai4g_frame_parms_t fp;
+  uint32_t nb_rx;
+  dev_buf<uint32_t> rep;                  /* [3][N] */
+  dev_buf<unsigned long long> keys;       /* [n] of the last batch */
+  dev_buf<uint32_t> pss;                  /* [3][62], with dbits: the SSS stage's tables, built when it first runs */
+  dev_buf<unsigned long long> dbits;      /* [504][2] */
+  dev_buf<int32_t> sssF;                  /* [n][nb_rx][4][N]: the SSS stage's FEP rows of the last batch */
+};
+
+extern "C" oai4g_sync_config_t *oai4g_sync_config_create(const oai4g_frame_parms_t *fp, uint8_t nb_antennas_rx)
+{
+  if (!sync_ok("sync_config_create", fp, nb_antennas_rx)) return nullptr;
+  std::vector<uint32_t> rep(3 * (size_t)fp->ofdm_symbol_size);
+  if (oai4g_lte_sync_time_replicas(fp, (int32_t *)rep.data()) != 0) return nullptr;
+  NEED_INIT(nullptr);
+  std::unique_ptr<oai4g_sync_config_t> cfg(new oai4g_sync_config_t);
+  cfg->fp = *fp;
+  cfg->nb_rx = nb_antennas_rx;
+  HCK(cfg->rep.upload(rep), nullptr);
+  return cfg.release();
+}
+
+extern "C" void oai4g_sync_config_destroy(oai4g_sync_config_t *cfg) { delete cfg; }
+
+extern "C" int oai4g_sync_time_batch(oai4g_sync_config_t *cfg, int n, const int32_t *d_rx, int32_t *d_peak, int32_t *d_corr,
+                                     void *stream)
+{
+  if (!cfg || n < 0 || (n > 0 && (!d_rx || !d_peak))) { set_err("sync_time_batch: bad arguments"); return -1; }
+  NEED_INIT(-1);
+  if (n == 0) return 0;
+  if (cfg->keys.count() < (size_t)n) {
+    HCK(hipDeviceSynchronize(), -1);                                   /* an earlier batch may still use the old slots */
+    HCK(cfg->keys.reserve((size_t)n), -1);
+  }
+  sync_time_args_t a;
+  memset(&a, 0, sizeof(a));
+  a.rx = (const uint32_t *)d_rx;
+  a.rep = cfg->rep.get();
+  a.N = cfg->fp.ofdm_symbol_size;
+  a.length = 5u * cfg->fp.samples_per_tti;
+  a.nb_rx = cfg->nb_rx;
+  a.n = (uint32_t)n;
+  a.keys = cfg->keys.get();
+  a.peak = d_peak;
+  a.corr = d_corr;
+  HCK(oai4g_launch_sync_time(a, (hipStream_t)stream), -1);
+  return 0;
+}
+
+/* lte_sync_time (:357) of one frame on the host's buffers: rxdata[aa] holds 10 samples_per_tti words.  sync_corr,
+ * when not null, receives the three buffers [3][10 samples_per_tti], every fourth entry defined. */
+extern "C" int oai4g_lte_sync_time(int32_t *const *rxdata, const oai4g_frame_parms_t *fp, uint8_t nb_antennas_rx, int *eNB_id,
+                                   uint32_t *peak_val, int32_t *sync_corr)
+{
+  if (!sync_ok("lte_sync_time", fp, nb_antennas_rx)) return -1;
+  if (!rxdata || !rxdata[0] || (nb_antennas_rx > 1 && !rxdata[1])) { set_err("lte_sync_time: null rxdata"); return -1; }
+  NEED_INIT(-1);
+  const size_t fl = (size_t)10 * fp->samples_per_tti, fb = fl * 4;
+  std::unique_ptr<oai4g_sync_config_t, void (*)(oai4g_sync_config_t *)> cfg(oai4g_sync_config_create(fp, nb_antennas_rx),
+                                                                            oai4g_sync_config_destroy);
+  if (!cfg) return -1;
+  stage_t st("lte_sync_time");
+  const int r_rx = st.add(fb * nb_antennas_rx), r_peak = st.add(12), r_corr = st.add(sync_corr ? 3 * fb : 0);
+  if (!st.open()) return -1;
+  for (uint32_t aa = 0; aa < nb_antennas_rx; aa++) HCK(st.up(r_rx, rxdata[aa], fb, aa * fb), -1);
+  if (oai4g_sync_time_batch(cfg.get(), 1, st.ptr<int32_t>(r_rx), st.ptr<int32_t>(r_peak), sync_corr ? st.ptr<int32_t>(r_corr) : nullptr,
+                            g_scr.s) != 0)
+    return -1;
+  int32_t peak[3] = {0, 0, 0};
+  HCK(st.down(peak, r_peak, 12), -1);
+  if (sync_corr) HCK(st.down(sync_corr, r_corr, 3 * fb), -1);
+  HCK(st.sync(), -1);                                                  /* the configuration goes after the kernels have run */
+  if (eNB_id) *eNB_id = peak[2];
+  if (peak_val) *peak_val = (uint32_t)peak[1];
+  return peak[0];
+}
+
+/* slot_fep's window of symbol l of slot Ns without the sample offset (slot_fep.c:105-150): what is added in front of
+ * the alignment and what behind it */
+static void fep_offset_sym(const oai4g_frame_parms_t *fp, uint32_t Ns, uint32_t l, uint32_t &pre, uint32_t &post)
+{
+  pre = fp->samples_per_tti * (Ns >> 1) + (fp->samples_per_tti >> 1) * (Ns & 1u) + fp->nb_prefix_samples0;
+  post = (fp->ofdm_symbol_size + fp->nb_prefix_samples) * l;
+}
+
+extern "C" int oai4g_fep_offset_batch(const oai4g_frame_parms_t *fp, int n, int nb_antennas_rx, const int32_t *d_rx,
+                                      const int32_t *d_offset, uint32_t offset_stride, uint8_t first_slot, int nsym,
+                                      int32_t *d_rxF, size_t frame_stride, void *stream)
+{
+  if (!sync_ok("fep_offset_batch", fp, nb_antennas_rx > 0 ? (uint32_t)nb_antennas_rx : 0u)) return -1;
+  const uint32_t nslot = fp->symbols_per_tti / 2u, N = fp->ofdm_symbol_size;
+  if (n < 0 || nsym < 1 || nsym > (int)fp->symbols_per_tti || first_slot + (nsym + nslot - 1) / nslot > 20 ||
+      (n > 0 && (!d_rx || !d_offset || !d_rxF))) {
+    set_err("fep_offset_batch: bad arguments (1 to %u symbols from slot %u, inside the frame)", fp->symbols_per_tti, first_slot);
+    return -1;
+  }
+  static_assert(OAI4G_FEP_MAX_SYM <= OAI4G_FEP_OFFSET_MAX_SYM, "a subframe's rows fit the argument block");
+  const size_t ant_stride = (size_t)fp->symbols_per_tti * N;
+  if (frame_stride == 0) frame_stride = ant_stride * nb_antennas_rx;
+  if (frame_stride < ant_stride * nb_antennas_rx || frame_stride * (size_t)n > 0xFFFFFFFFull) {
+    set_err("fep_offset_batch: frame stride %zu", frame_stride);
+    return -1;
+  }
+  NEED_INIT(-1);
+  if (n == 0) return 0;
+  fep_offset_args_t a;
+  memset(&a, 0, sizeof(a));
+  a.nsym = nsym;
+  a.n_units = n * nb_antennas_rx * nsym;
+  a.n_ant = (uint32_t)nb_antennas_rx;
+  a.frame_len = 10u * fp->samples_per_tti;
+  a.out_frame_stride = (uint32_t)frame_stride;
+  a.out_ant_stride = (uint32_t)ant_stride;
+  a.offset = d_offset;
+  a.offset_stride = offset_stride;
+  a.scale = 1;
+  for (int k = 0; k < nsym; k++) fep_offset_sym(fp, first_slot + (uint32_t)k / nslot, (uint32_t)k % nslot, a.pre[k], a.post[k]);
+  HCK(oai4g_launch_fep_offset(d_rx, d_rxF, fp->log2_symbol_size, a, g_twf, g_n_cu, (hipStream_t)stream), -1);
+  return 0;
+}
+
+/* the tables of the SSS stage, built when it first runs: primary_synch<Nid2>[10..133] as words, and d0_sss / d5_sss as
+ * sign bits */
+static int sync_sss_tables(oai4g_sync_config_t *cfg)
+{
+  if (cfg->pss) return 0;
+  std::vector<uint32_t> pss(3 * 62);
+  for (uint32_t s = 0; s < 3; s++) {
+    int16_t v[62][2];
+    pss_table(s, v);
+    for (int i = 0; i < 62; i++) pss[s * 62 + i] = (uint32_t)(uint16_t)v[i][0] | ((uint32_t)(uint16_t)v[i][1] << 16);
+  }
+  std::vector<unsigned long long> bits(504 * 2, 0ull);
+  for (uint32_t nid = 0; nid < 504; nid++)
+    for (int sf5 = 0; sf5 < 2; sf5++) {
+      int16_t d[62];
+      sss_table(nid, sf5 != 0, d);
+      for (int i = 0; i < 62; i++)
+        if (d[i] < 0) bits[2 * nid + sf5] |= 1ull << i;
+    }
+  HCK(cfg->dbits.upload(bits), -1);
+  HCK(cfg->pss.upload(pss), -1);
+  return 0;
+}
+
+static void sss_fill(const oai4g_sync_config_t *cfg, sss_args_t &a, uint32_t n)
+{
+  memset(&a, 0, sizeof(a));
+  a.pss = cfg->pss.get();
+  a.d = cfg->dbits.get();
+  a.n = n;
+  a.nb_rx = cfg->nb_rx;
+  a.N = cfg->fp.ofdm_symbol_size;
+  a.cp = cfg->fp.nb_prefix_samples;
+  a.spt = cfg->fp.samples_per_tti;
+  /* the seven phase hypotheses between PSS and SSS, -60 .. 60 degrees in Q15 (the values of sss.c:218-219, which no
+   * single rounding rule reproduces) */
+  static const int16_t phase_re[7] = {16383, 25101, 30791, 32767, 30791, 25101, 16383};
+  static const int16_t phase_im[7] = {-28378, -21063, -11208, 0, 11207, 21062, 28377};
+  memcpy(a.phase_re, phase_re, sizeof(phase_re));
+  memcpy(a.phase_im, phase_im, sizeof(phase_im));
+}
+
+/* the four slot_fep calls of rx_sss (sss.c:247-259, :306-316) at the records' rx_offset, then the detection */
+static int sss_run(oai4g_sync_config_t *cfg, sss_args_t &a, const int32_t *d_rx, hipStream_t s)
+{
+  const uint32_t N = a.N;
+  if (cfg->sssF.count() < (size_t)a.n * a.nb_rx * 4 * N) {
+    HCK(hipDeviceSynchronize(), -1);                                   /* an earlier batch may still use the old rows */
+    HCK(cfg->sssF.reserve((size_t)a.n * a.nb_rx * 4 * N), -1);
+  }
+  fep_offset_args_t f;
+  memset(&f, 0, sizeof(f));
+  f.nsym = 4;
+  f.n_units = (int)(a.n * a.nb_rx * 4u);
+  f.n_ant = a.nb_rx;
+  f.frame_len = 10u * a.spt;
+  f.out_ant_stride = 4u * N;
+  f.out_frame_stride = a.nb_rx * 4u * N;
+  f.offset = a.cell + 1;
+  f.offset_stride = OAI4G_CELL_WORDS;
+  f.scale = 1;
+  for (uint32_t k = 0; k < 4; k++) fep_offset_sym(&cfg->fp, k < 2 ? 0u : 10u, 5u + (k & 1u), f.pre[k], f.post[k]);
+  HCK(oai4g_launch_fep_offset(d_rx, cfg->sssF.get(), cfg->fp.log2_symbol_size, f, g_twf, g_n_cu, s), -1);
+  a.rxF = cfg->sssF.get();
+  HCK(oai4g_launch_sss(a, s), -1);
+  return 0;
+}
+
+static_assert(sizeof(oai4g_cell_t) == 4 * OAI4G_CELL_WORDS, "the kernels address a cell record as six words");
+
+extern "C" int oai4g_sss_batch(oai4g_sync_config_t *cfg, int n, const int32_t *d_rx, const int32_t *d_peak, oai4g_cell_t *d_cell,
+                               void *stream)
+{
+  if (!cfg || n < 0 || (n > 0 && (!d_rx || !d_peak || !d_cell))) { set_err("sss_batch: bad arguments"); return -1; }
+  NEED_INIT(-1);
+  if (n == 0) return 0;
+  if (sync_sss_tables(cfg) != 0) return -1;
+  sss_args_t a;
+  sss_fill(cfg, a, (uint32_t)n);
+  a.peak = d_peak;
+  a.cell = (int32_t *)d_cell;
+  a.add_half = 1;
+  HCK(oai4g_launch_sss_offsets(a, (hipStream_t)stream), -1);
+  return sss_run(cfg, a, d_rx, (hipStream_t)stream);
+}
+
+/* the same behind the four slot_fep calls, on the caller's rows [n][nb_rx][4][N] (symbols 5 and 6 of slot 0, then of
+ * slot 10): values the forward DFT's own scaling never produces, such as full-scale symbols, can be put through the
+ * compensation and the search */
+extern "C" int oai4g_sss_rows_batch(oai4g_sync_config_t *cfg, int n, const int32_t *d_rows, const int32_t *d_peak,
+                                    oai4g_cell_t *d_cell, void *stream)
+{
+  if (!cfg || n < 0 || (n > 0 && (!d_rows || !d_peak || !d_cell))) { set_err("sss_rows_batch: bad arguments"); return -1; }
+  NEED_INIT(-1);
+  if (n == 0) return 0;
+  if (sync_sss_tables(cfg) != 0) return -1;
+  sss_args_t a;
+  sss_fill(cfg, a, (uint32_t)n);
+  a.peak = d_peak;
+  a.cell = (int32_t *)d_cell;
+  a.add_half = 1;
+  a.rxF = d_rows;
+  HCK(oai4g_launch_sss_offsets(a, (hipStream_t)stream), -1);
+  HCK(oai4g_launch_sss(a, (hipStream_t)stream), -1);
+  return 0;
+}
+
+/* rx_sss (sss.c:222) on one frame in host memory: the sequence the PSS stage found and phy_vars_ue->rx_offset come
+ * from the caller; returns the Nid_cell it leaves in the frame parameters */
+extern "C" int oai4g_rx_sss(int32_t *const *rxdata, const oai4g_frame_parms_t *fp, uint8_t nb_antennas_rx, uint8_t Nid2,
+                            int rx_offset, int32_t *tot_metric, uint8_t *flip_max, uint8_t *phase_max)
+{
+  if (!sync_ok("rx_sss", fp, nb_antennas_rx)) return -1;
+  if (!rxdata || !rxdata[0] || (nb_antennas_rx > 1 && !rxdata[1]) || Nid2 > 2 || rx_offset < 0) {
+    set_err("rx_sss: null rxdata, Nid2 %u or a negative rx_offset", Nid2);
+    return -1;
+  }
+  NEED_INIT(-1);
+  const size_t fb = (size_t)10 * fp->samples_per_tti * 4;
+  std::unique_ptr<oai4g_sync_config_t, void (*)(oai4g_sync_config_t *)> cfg(oai4g_sync_config_create(fp, nb_antennas_rx),
+                                                                            oai4g_sync_config_destroy);
+  if (!cfg || sync_sss_tables(cfg.get()) != 0) return -1;
+  stage_t st("rx_sss");
+  const int r_rx = st.add(fb * nb_antennas_rx), r_peak = st.add(12), r_cell = st.add(4 * OAI4G_CELL_WORDS);
+  if (!st.open()) return -1;
+  const int32_t peak[3] = {0, 0, Nid2};
+  int32_t cell[OAI4G_CELL_WORDS] = {-1, rx_offset, 0, 0, 0, 0};
+  for (uint32_t aa = 0; aa < nb_antennas_rx; aa++) HCK(st.up(r_rx, rxdata[aa], fb, aa * fb), -1);
+  HCK(st.up(r_peak, peak, sizeof(peak)), -1);
+  HCK(st.up(r_cell, cell, sizeof(cell)), -1);
+  sss_args_t a;
+  sss_fill(cfg.get(), a, 1);
+  a.peak = st.ptr<int32_t>(r_peak);
+  a.cell = st.ptr<int32_t>(r_cell);
+  if (sss_run(cfg.get(), a, st.ptr<int32_t>(r_rx), g_scr.s) != 0) return -1;
+  HCK(st.down(cell, r_cell, sizeof(cell)), -1);
+  HCK(st.sync(), -1);
+  if (tot_metric) *tot_metric = cell[2];
+  if (flip_max) *flip_max = (uint8_t)cell[3];
+  if (phase_max) *phase_max = (uint8_t)cell[4];
+  return cell[0];
+}
+
+/* initial_sync's first hypothesis (initial_sync.c:290-372, FDD with the normal prefix) on one frame in host memory:
+ * lte_sync_time, the offset arithmetic and rx_sss, the frame parameters of the found cell, pbch_detection's slot_fep
+ * calls (:69-92: slots 0 and 1 and symbol 0 of slot 2 at rx_offset), the channel estimation of nb_ports ports, the
+ * PBCH front end and the eight-hypothesis search.  The cell is read back once in the middle: the estimation and PBCH
+ * configurations are per cell. */
+extern "C" int oai4g_initial_sync(int32_t *const *rxdata, const oai4g_frame_parms_t *fp, uint8_t nb_antennas_rx, uint8_t nb_ports,
+                                  uint32_t high_speed_flag, oai4g_initial_sync_t *out)
+{
+  if (!sync_ok("initial_sync", fp, nb_antennas_rx)) return -1;
+  if (!rxdata || !rxdata[0] || (nb_antennas_rx > 1 && !rxdata[1]) || !out || nb_ports < 1 || nb_ports > 2) {
+    set_err("initial_sync: null argument or %u estimated ports (1 or 2)", nb_ports);
+    return -1;
+  }
+  NEED_INIT(-1);
+  memset(out, 0, sizeof(*out));
+  out->Nid_cell = -1;
+  out->tx_ant = 0xFF;
+  using sync_ptr = std::unique_ptr<oai4g_sync_config_t, void (*)(oai4g_sync_config_t *)>;
+  using chest_ptr = std::unique_ptr<oai4g_chest_config_t, void (*)(oai4g_chest_config_t *)>;
+  using pbch_ptr = std::unique_ptr<oai4g_pbch_front_config_t, void (*)(oai4g_pbch_front_config_t *)>;
+  sync_ptr cfg(oai4g_sync_config_create(fp, nb_antennas_rx), oai4g_sync_config_destroy);
+  if (!cfg) return -1;
+  const uint32_t N = fp->ofdm_symbol_size, nb_rx = nb_antennas_rx;
+  const size_t fb = (size_t)10 * fp->samples_per_tti * 4, grid = (size_t)fp->symbols_per_tti * N;
+  stage_t st("initial_sync");
+  const int r_rx = st.add(fb * nb_rx), r_peak = st.add(12), r_cell = st.add(sizeof(oai4g_cell_t));
+  const int r_rxF = st.add(2 * nb_rx * grid * 4), r_est = st.add(4 * grid * 4), r_llr = st.add(2 * OAI4G_PBCH_SOFT);
+  const int r_l2 = st.add(4), r_det = st.add(sizeof(oai4g_pbch_detect_t));
+  if (!st.open()) return -1;
+  for (uint32_t aa = 0; aa < nb_rx; aa++) HCK(st.up(r_rx, rxdata[aa], fb, aa * fb), -1);
+  const int32_t *d_rx = st.ptr<int32_t>(r_rx);
+  oai4g_cell_t *d_cell = st.ptr<oai4g_cell_t>(r_cell);
+  if (oai4g_sync_time_batch(cfg.get(), 1, d_rx, st.ptr<int32_t>(r_peak), nullptr, g_scr.s) != 0 ||
+      oai4g_sss_batch(cfg.get(), 1, d_rx, st.ptr<int32_t>(r_peak), d_cell, g_scr.s) != 0)
+    return -1;
+  oai4g_cell_t cell;
+  HCK(st.down(&cell, r_cell, sizeof(cell)), -1);
+  HCK(st.sync(), -1);
+  out->rx_offset = cell.rx_offset;
+  if (cell.status != 0) { set_err("initial_sync: SSS error condition (rx_offset %d)", cell.rx_offset); return -1; }
+  out->Nid_cell = cell.Nid_cell;
+  oai4g_frame_parms_t fc;
+  if (oai4g_init_frame_parms(&fc, fp->N_RB_DL, (uint16_t)cell.Nid_cell, 0, nb_ports, nb_ports == 1, 0) != 0) return -1;
+  /* rows: element 0 holds slots 0 and 1 per antenna, element 1's row 0 the symbol that closes rows 12 / 13 */
+  int32_t *d_rxF = st.ptr<int32_t>(r_rxF);
+  const int32_t *d_off = &d_cell->rx_offset;
+  if (oai4g_fep_offset_batch(&fc, 1, nb_rx, d_rx, d_off, 0, 0, fc.symbols_per_tti, d_rxF, 0, g_scr.s) != 0 ||
+      oai4g_fep_offset_batch(&fc, 1, nb_rx, d_rx, d_off, 0, 2, 1, d_rxF + nb_rx * grid, 0, g_scr.s) != 0)
+    return -1;
+  HCK(st.zero(r_est, 4 * grid * 4, r_est), -1);
+  const int32_t *ep[4] = {nullptr, nullptr, nullptr, nullptr};
+  for (uint32_t p = 0; p < nb_ports; p++) {
+    chest_ptr ce(oai4g_chest_config_create(&fc, (uint8_t)p, 0, 0), oai4g_chest_config_destroy);
+    if (!ce || oai4g_chest_config_set_stride(ce.get(), nb_rx, nb_rx) != 0) return -1;
+    for (uint32_t aa = 0; aa < nb_rx; aa++) {
+      int32_t *e = st.ptr<int32_t>(r_est, ((p << 1) + aa) * grid * 4);
+      if (oai4g_chest_batch(ce.get(), 1, d_rxF + aa * grid, e, g_scr.s) != 0) return -1;
+      ep[(p << 1) + aa] = e;
+    }
+    HCK(st.sync(), -1);                                                /* the configuration goes with this scope */
+  }
+  pbch_ptr pb(oai4g_pbch_front_config_create(&fc, nb_antennas_rx, nb_ports, high_speed_flag), oai4g_pbch_front_config_destroy);
+  if (!pb) return -1;
+  oai4g_pbch_detect_t det;
+  if (oai4g_pbch_front_batch(pb.get(), 1, d_rxF, ep, st.ptr<int8_t>(r_llr), st.ptr(r_l2), g_scr.s) != 0 ||
+      oai4g_pbch_detect_batch(pb.get(), 1, st.ptr<int8_t>(r_llr), st.ptr<oai4g_pbch_detect_t>(r_det), g_scr.s) != 0)
+    return -1;
+  HCK(st.down(&det, r_det, sizeof(det)), -1);
+  HCK(st.sync(), -1);
+  if (det.tx_ant != 1 && det.tx_ant != 2) { set_err(""); return -1; }   /* no PBCH found: not an error of the call */
+  out->tx_ant = det.tx_ant;
+  out->frame_mod4 = det.frame_mod4;
+  out->mimo_mode = det.mimo_mode;
+  memcpy(out->mib, det.mib, 3);
+  return 0;
+}

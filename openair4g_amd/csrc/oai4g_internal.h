@@ -685,6 +685,50 @@ struct phich_rx_args_t {
   oai4g_phich_rx_out_t *out;   /* [n_items] */
 };
 hipError_t oai4g_launch_phich_rx(const phich_rx_args_t &a, hipStream_t s);
+
+/* The PSS time-domain correlation of initial cell search (oai4g_sync_rx.hip: k_sync_time, k_sync_peak) */
+struct sync_time_args_t {
+  const uint32_t *rx;          /* [n][nb_rx][2 length] received frames, packed int16 pairs */
+  const uint32_t *rep;         /* [3][N] the time-domain replicas of lte_sync_time_init, 16-byte aligned */
+  uint32_t N, length, nb_rx, n;   /* ofdm_symbol_size, 5 samples_per_tti, receive antennas (1 or 2), frames */
+  unsigned long long *keys;    /* [n] scratch: metric << 32 | ~(n + s), the largest wins */
+  int32_t *peak;               /* [n] {peak_pos, peak_val, Nid2} */
+  int32_t *corr;               /* null, or [n][3][2 length]: sync_corr_ue0..2 after abs32, every fourth entry */
+};
+hipError_t oai4g_launch_sync_time(const sync_time_args_t &a, hipStream_t s);
+/* slot_fep at a per-frame device offset (oai4g_fep.hip: k_fep_offset): items are (frame, antenna) pairs of
+ * frame_len input words; symbol sym of the run starts at ((offset + pre[sym]) & ~3) + post[sym] modulo frame_len
+ * (slot_fep.c:105-150) and lands at out + frame * out_frame_stride + antenna * out_ant_stride + sym * N */
+#define OAI4G_FEP_OFFSET_MAX_SYM 16
+struct fep_offset_args_t {
+  int n_units;                 /* frames x antennas x nsym */
+  int nsym;
+  uint32_t n_ant, frame_len;
+  uint32_t out_frame_stride, out_ant_stride;   /* words */
+  const int32_t *offset;       /* frame f's sample offset at offset[f * offset_stride] */
+  uint32_t offset_stride;
+  uint32_t pre[OAI4G_FEP_OFFSET_MAX_SYM];    /* slot_offset + nb_prefix_samples0 + subframe_offset of the symbol's slot */
+  uint32_t post[OAI4G_FEP_OFFSET_MAX_SYM];   /* (N + nb_prefix_samples) l */
+  int scale;
+};
+hipError_t oai4g_launch_fep_offset(const int32_t *d_in, int32_t *d_out, int log2n, const fep_offset_args_t &a,
+                                   const uint32_t *d_twf, int n_cu, hipStream_t s);
+/* SSS detection behind the PSS stage (oai4g_sync_rx.hip: k_sss_offsets, k_sss).  A cell record is six int32:
+ * {Nid_cell, rx_offset, metric, flip, phase, status} */
+#define OAI4G_CELL_WORDS 6u
+#define OAI4G_SSS_ERROR 1      /* status: "SSS error condition" (initial_sync.c:373-376), the frame has no cell */
+struct sss_args_t {
+  const int32_t *peak;         /* [n] {peak_pos, peak_val, Nid2} */
+  int32_t *cell;               /* [n] records */
+  const int32_t *rxF;          /* [n][nb_rx][4][N]: symbols 5 and 6 of slot 0, then of slot 10, at the record's rx_offset */
+  const uint32_t *pss;         /* [3][62] primary_synch<Nid2>[10..133] as packed int16 pairs */
+  const unsigned long long *d;   /* [504][2] bit i: d0_sss / d5_sss [Nid_cell][i] is -1 */
+  uint32_t n, nb_rx, N, cp, spt;
+  uint32_t add_half;           /* 1: flip = 1 adds the half frame to the reported rx_offset (initial_sync.c:361-362) */
+  int16_t phase_re[8], phase_im[8];   /* sss.c:218-219: floor(32767 cos / sin) of -60, -40, ... 60 degrees */
+};
+hipError_t oai4g_launch_sss_offsets(const sss_args_t &a, hipStream_t s);
+hipError_t oai4g_launch_sss(const sss_args_t &a, hipStream_t s);
 void oai4g_set_error(const char *fmt, ...);
 /* binds the calling thread to the device the library was initialised on (hipSetDevice is per thread) */
 int oai4g_bind_thread(void);

@@ -894,6 +894,69 @@ int oai4g_awgn_batch(const int32_t *d_tx, size_t tx_stride, uint32_t tx_len, con
                      int32_t *d_rx, size_t rx_stride, int n, const int32_t *d_tx_lev, double offset_db, uint64_t seed,
                      uint32_t first_vector, void *stream);
 
+/* ---------------- fading channels (SIMULATION/TOOLS/random_channel.c, multipath_channel.c) ---------------- */
+/* new_channel_desc_scm / fill_channel_desc (random_channel.c:195-860, :42-147) for n_vectors trials, each with its
+ * own descriptor state on the device: a [n_vectors][nb_taps][nb_tx nb_rx], ch [n_vectors][nb_tx nb_rx]
+ * [channel_length] as complex doubles (pair index aarx + aatx nb_rx) and a first_run flag.  `model` takes the
+ * numeric values of SCM_t (SIMULATION/TOOLS/defs.h:158-178; dlsim's -g letters): EPA 5, EVA 6, ETU 7, Rayleigh8 9,
+ * Rayleigh1 10, Rayleigh1_800 11, Rayleigh1_corr 12, Rayleigh1_anticorr 13, Rice8 14, Rice1 15, Rice1_corr 16,
+ * Rice1_anticorr 17, AWGN 18.  BW is the caller's number (dlsim passes 1.25 / 5 / 10 / 20 for 6 / 25 / 50 / 100
+ * PRB, not the sampling rate).  Refused with oai4g_last_error naming it: SCM_A .. SCM_D, custom, MBSFN, nb_tx or
+ * nb_rx outside 1..2, and a channel_length beyond 255 (the reference's field is a uint8_t).  EPA / EVA / ETU at
+ * 1x2 and 2x1 use identity correlation (the reference leaves that matrix's off-diagonals uninitialised). */
+#define OAI4G_CHANNEL_MAX_TAPS 9
+typedef struct {
+  uint32_t nb_taps, channel_length, random_aoa;
+  uint32_t n_matrices;                    /* correlation matrices held: tap i uses matrix i / 3 */
+  double ricean_factor, aoa;
+  double amps[OAI4G_CHANNEL_MAX_TAPS], delays[OAI4G_CHANNEL_MAX_TAPS];
+} oai4g_channel_info_t;
+typedef struct oai4g_channel_config oai4g_channel_config_t;
+oai4g_channel_config_t *oai4g_channel_config_create(uint8_t nb_tx, uint8_t nb_rx, int model, double BW,
+                                                    double forgetting_factor, int32_t channel_offset, double path_loss_dB,
+                                                    int n_vectors);
+void oai4g_channel_config_destroy(oai4g_channel_config_t *cfg);
+/* the descriptor's tables; r_sqrt, when not null, receives [n_matrices][nb_tx nb_rx][nb_tx nb_rx][re, im] (at most
+ * 6 x 4 x 4 x 2 doubles).  _model_describe is the constructor's host side alone and needs no device. */
+int oai4g_channel_config_query(const oai4g_channel_config_t *cfg, oai4g_channel_info_t *info, double *r_sqrt);
+int oai4g_channel_model_describe(int model, uint8_t nb_tx, uint8_t nb_rx, double BW, oai4g_channel_info_t *info,
+                                 double *r_sqrt);
+/* random_channel (:866-1015) of vectors [0, n): new state a (a copy on a vector's first run, else sqrt(ff) a +
+ * sqrt(1 - ff) acorr) and interpolated taps ch.  The normals and uniforms are Philox-4x32 / Box-Muller keyed by
+ * (seed, first_vector + vector, step, tap, pair), or, with d_draws not null, read from d_draws [n][per vector] in
+ * the reference's draw order: tap, aarx, aatx: x, y, and on tap 0 of a model that draws its angle of arrival the
+ * uniform behind them.  In the reference all trials share one descriptor, so a forgetting factor correlates trial t
+ * with trial t - 1; in the batch the correlation runs along the successive calls of one vector.  Asynchronous on
+ * `stream`; n > n_vectors is refused. */
+int oai4g_channel_random_batch(oai4g_channel_config_t *cfg, int n, uint64_t seed, uint32_t first_vector, uint32_t step,
+                               const double *d_draws, void *stream);
+/* host <-> device state of vectors [first_vector, first_vector + n): ch [n][nb_tx nb_rx][channel_length][re, im] and
+ * a [n][nb_taps][nb_tx nb_rx][re, im]; a null array is skipped.  Setting `a` ends the vectors' first run.  Both
+ * synchronise. */
+int oai4g_channel_set_taps(oai4g_channel_config_t *cfg, int first_vector, int n, const double *ch, const double *a);
+int oai4g_channel_get_taps(oai4g_channel_config_t *cfg, int first_vector, int n, double *ch, double *a);
+/* multipath_channel (multipath_channel.c:152-219, the non-SSE form) with keep_channel = 1 on the vectors' ch, and
+ * dlsim's noise (dlsim.c:2852-2864), n <= n_vectors and <= 65535.  Input of vector v and transmit antenna j: the
+ * tx_len int16 IQ samples at d_tx + v tx_stride + j tx_ant_stride followed by the tail_len samples at d_tail + j
+ * tail_len; length = tx_len + tail_len.  Per output sample and receive antenna the reference's loop (j outer, l
+ * inner, separate double multiplies and adds, zero input in front of sample 0), times 10^(path_loss_dB / 20),
+ * delayed by |channel_offset| samples; samples [0, |channel_offset|), which the reference leaves unwritten, are 0
+ * here.  Then (short)(r + sqrt(sigma2 / 2) g) per component with sigma2 in dB = 10 log10(sum_j d_tx_lev[v nb_tx +
+ * j]) + offset_db; g is oai4g_awgn_batch's stream for receive antenna 0 (so model AWGN 1x1 equals oai4g_awgn_batch
+ * bit for bit) and a stream of its own per further antenna.  Sample i of receive antenna a goes to d_rx + v
+ * rx_stride + (i / seg_len) seg_stride + a rx_ant_stride + i % seg_len.  Strides in samples.  Asynchronous. */
+int oai4g_multipath_batch(oai4g_channel_config_t *cfg, int n, const int32_t *d_tx, size_t tx_stride, size_t tx_ant_stride,
+                          uint32_t tx_len, const int32_t *d_tail, uint32_t tail_len, int32_t *d_rx, size_t rx_stride,
+                          size_t rx_ant_stride, uint32_t seg_len, size_t seg_stride, const int32_t *d_tx_lev,
+                          double offset_db, uint64_t seed, uint32_t first_vector, void *stream);
+/* The drop-ins, the reference's signatures with the configuration in place of channel_desc_t *, on vector 0.
+ * random_channel draws from the Philox stream of the configuration's seed 0, one step per call.  multipath_channel
+ * works on host doubles, draws a new channel first unless keep_channel, and leaves rx[.][0 .. |channel_offset|)
+ * untouched as the reference does. */
+int oai4g_random_channel(oai4g_channel_config_t *cfg);
+int oai4g_multipath_channel(oai4g_channel_config_t *cfg, double **tx_sig_re, double **tx_sig_im, double **rx_sig_re,
+                            double **rx_sig_im, uint32_t length, uint8_t keep_channel);
+
 /* ---------------- uplink turbo decoding ---------------- */
 enum { OAI4G_CRC24_A = 0, OAI4G_CRC24_B = 1 };
 /* phy_threegpplte_turbo_decoder16 (PHY/CODING/3gpplte_turbo_decoder_sse_16bit.c:945, decl

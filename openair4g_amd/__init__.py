@@ -455,6 +455,24 @@ _SIGS = {
     "oai4g_phich_rx_config_destroy": (None, [ctypes.c_void_p]),
     "oai4g_phich_rx_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
                                             ctypes.c_void_p, ctypes.c_void_p]),
+    "oai4g_channel_config_create": (ctypes.c_void_p, [ctypes.c_uint8, ctypes.c_uint8, ctypes.c_int, ctypes.c_double,
+                                                      ctypes.c_double, ctypes.c_int32, ctypes.c_double, ctypes.c_int]),
+    "oai4g_channel_config_destroy": (None, [ctypes.c_void_p]),
+    "oai4g_channel_config_query": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "oai4g_channel_model_describe": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_double,
+                                                    ctypes.c_void_p, ctypes.c_void_p]),
+    "oai4g_channel_random_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32,
+                                                  ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
+    "oai4g_channel_set_taps": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    "oai4g_channel_get_taps": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    "oai4g_multipath_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t,
+                                             ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                             ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_size_t,
+                                             ctypes.c_void_p, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32,
+                                             ctypes.c_void_p]),
+    "oai4g_random_channel": (ctypes.c_int, [ctypes.c_void_p]),
+    "oai4g_multipath_channel": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_void_p)] * 4
+                                + [ctypes.c_uint32, ctypes.c_uint8]),
 }
 
 
@@ -1580,6 +1598,117 @@ def initial_sync(rxdata, fp, nb_ports=2, high_speed_flag=1):
     err = lib().oai4g_last_error()
     _check(r == 0 or not err or b"SSS error condition" in err)
     return r, out
+
+
+# ------------------------------------------------------------------------------------------
+# fading channels (SIMULATION/TOOLS/random_channel.c, multipath_channel.c)
+# ------------------------------------------------------------------------------------------
+CHANNEL_MAX_TAPS = 9
+# SCM_t (SIMULATION/TOOLS/defs.h:158-178), the supported ones; dlsim's -g letters map to these
+(EPA, EVA, ETU, Rayleigh8, Rayleigh1, Rayleigh1_800, Rayleigh1_corr, Rayleigh1_anticorr, Rice8, Rice1, Rice1_corr,
+ Rice1_anticorr, AWGN) = 5, 6, 7, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18
+
+
+class ChannelInfo(ctypes.Structure):
+    """oai4g_channel_info_t"""
+    _fields_ = [("nb_taps", ctypes.c_uint32), ("channel_length", ctypes.c_uint32), ("random_aoa", ctypes.c_uint32),
+                ("n_matrices", ctypes.c_uint32), ("ricean_factor", ctypes.c_double), ("aoa", ctypes.c_double),
+                ("amps", ctypes.c_double * CHANNEL_MAX_TAPS), ("delays", ctypes.c_double * CHANNEL_MAX_TAPS)]
+
+
+def _r_sqrt(raw, info, n):
+    return (raw[:info.n_matrices * n * n * 2].reshape(info.n_matrices, n, n, 2) @ np.array([1, 1j])).copy()
+
+
+def channel_model_describe(model, nb_tx, nb_rx, BW):
+    """oai4g_channel_model_describe: (ChannelInfo, R_sqrt complex [n_matrices][npair][npair]) of a model.  Host only."""
+    info, raw = ChannelInfo(), np.zeros(6 * 16 * 2)
+    _check(lib().oai4g_channel_model_describe(model, nb_tx, nb_rx, BW, ctypes.byref(info), _ptr(raw)) == 0)
+    return info, _r_sqrt(raw, info, nb_tx * nb_rx)
+
+
+class _ChannelBatch(_DeviceOwner):
+    """Fading channel of n_vectors trials on the device (oai4g_channel_config_create): every vector has its own
+    descriptor state.  Public as ChannelBatch.  draw() is random_channel of the vectors, run() multipath_channel on their taps plus dlsim's
+    noise; taps() / set_taps() move a and ch between host and device as complex arrays a [n][nb_taps][npair] and
+    ch [n][npair][channel_length], pair index aarx + aatx nb_rx."""
+
+    def __init__(self, nb_tx, nb_rx, model, BW, n_vectors, forgetting_factor=0.0, channel_offset=0, path_loss_dB=0.0):
+        self.L = init()
+        self.nb_tx, self.nb_rx, self.n, self.npair = nb_tx, nb_rx, n_vectors, nb_tx * nb_rx
+        self.cfg = self._own(self.L.oai4g_channel_config_create(nb_tx, nb_rx, model, BW, forgetting_factor, channel_offset,
+                                                                path_loss_dB, n_vectors),
+                             self.L.oai4g_channel_config_destroy)
+        self.info, raw = ChannelInfo(), np.zeros(6 * 16 * 2)
+        _check(self.L.oai4g_channel_config_query(self.cfg, ctypes.byref(self.info), _ptr(raw)) == 0)
+        self.R_sqrt = _r_sqrt(raw, self.info, self.npair)
+        self.nb_taps, self.channel_length = self.info.nb_taps, self.info.channel_length
+        angles = self.info.ricean_factor != 1.0 and self.info.random_aoa == 1
+        self.draws_per_vector = self.nb_taps * self.npair * 2 + (self.npair if angles else 0)
+        self.d_draws = None
+
+    def draw(self, seed=0, first_vector=0, step=0, n=None, draws=None, stream=None):
+        """a new channel for vectors [0, n): Philox draws keyed by (seed, first_vector + vector, step), or the given
+        float64 [n][draws_per_vector] in the reference's draw order"""
+        n = self.n if n is None else n
+        d = None
+        if draws is not None:
+            draws = np.ascontiguousarray(draws, dtype=np.float64)
+            assert draws.size == n * self.draws_per_vector
+            if self.d_draws is None:
+                self.d_draws = self._dev(self.n * self.draws_per_vector * 8)
+            self._put(self.d_draws, draws)
+            d = self.d_draws
+        _check(self.L.oai4g_channel_random_batch(self.cfg, n, seed, first_vector, step, d, stream) == 0)
+
+    def run(self, d_tx, tx_stride, tx_ant_stride, tx_len, d_tail, tail_len, d_rx, rx_stride, rx_ant_stride, seg_len,
+            seg_stride, d_tx_lev, offset_db, seed, first_vector=0, n=None, stream=None):
+        """oai4g_multipath_batch on the vectors' current taps"""
+        _check(self.L.oai4g_multipath_batch(self.cfg, self.n if n is None else n, d_tx, tx_stride, tx_ant_stride, tx_len,
+                                            d_tail, tail_len, d_rx, rx_stride, rx_ant_stride, seg_len, seg_stride, d_tx_lev,
+                                            offset_db, seed, first_vector, stream) == 0)
+
+    def taps(self, first_vector=0, n=None):
+        """(a, ch) of vectors [first_vector, +n) (synchronises)"""
+        n = self.n - first_vector if n is None else n
+        a = np.zeros((n, self.nb_taps, self.npair, 2))
+        ch = np.zeros((n, self.npair, self.channel_length, 2))
+        _check(self.L.oai4g_channel_get_taps(self.cfg, first_vector, n, _ptr(ch), _ptr(a)) == 0)
+        return a[..., 0] + 1j * a[..., 1], ch[..., 0] + 1j * ch[..., 1]
+
+    def set_taps(self, ch=None, a=None, first_vector=0):
+        """complex ch [n][npair][channel_length] and / or a [n][nb_taps][npair] into vectors [first_vector, +n)"""
+        def pairs(v, shape):
+            v = np.asarray(v, dtype=np.complex128).reshape((-1,) + shape)
+            return np.ascontiguousarray(np.stack([v.real, v.imag], axis=-1))
+        hc = None if ch is None else pairs(ch, (self.npair, self.channel_length))
+        ha = None if a is None else pairs(a, (self.nb_taps, self.npair))
+        n = len(hc if hc is not None else ha)
+        assert ha is None or hc is None or len(ha) == len(hc)
+        _check(self.L.oai4g_channel_set_taps(self.cfg, first_vector, n, None if hc is None else _ptr(hc),
+                                             None if ha is None else _ptr(ha)) == 0)
+
+
+ChannelBatch = _ChannelBatch
+
+
+def random_channel(chan):
+    """oai4g_random_channel: the drop-in on vector 0 of a ChannelBatch"""
+    _check(chan.L.oai4g_random_channel(chan.cfg) == 0)
+
+
+def multipath_channel(chan, tx_re, tx_im, length=None, keep_channel=1, rx_re=None, rx_im=None):
+    """oai4g_multipath_channel on vector 0 of a ChannelBatch: tx_re / tx_im float64 [nb_tx][length] -> (rx_re, rx_im)
+    float64 [nb_rx][length]; samples [0, |channel_offset|) keep what rx_re / rx_im held (NaN when not given)"""
+    tx = [np.ascontiguousarray(v, dtype=np.float64) for v in list(tx_re) + list(tx_im)]
+    length = tx[0].size if length is None else length
+    assert len(tx) == 2 * chan.nb_tx and all(v.size >= length for v in tx)
+    rx = [np.full(length, np.nan) if v is None else v for v in
+          ([None] * (2 * chan.nb_rx) if rx_re is None else list(rx_re) + list(rx_im))]
+    pp = [(ctypes.c_void_p * len(v))(*[a.ctypes.data for a in v])
+          for v in (tx[:chan.nb_tx], tx[chan.nb_tx:], rx[:chan.nb_rx], rx[chan.nb_rx:])]
+    _check(chan.L.oai4g_multipath_channel(chan.cfg, *pp, length, keep_channel) == 0)
+    return np.stack(rx[:chan.nb_rx]), np.stack(rx[chan.nb_rx:])
 
 
 class Cell(ctypes.Structure):

@@ -6390,3 +6390,367 @@ extern "C" int oai4g_initial_sync(int32_t *const *rxdata, const oai4g_frame_parm
   memcpy(out->mib, det.mib, 3);
   return 0;
 }
+
+/* ------------------------------------------------------------------------------------------
+ * fading channels: new_channel_desc_scm / fill_channel_desc (SIMULATION/TOOLS/random_channel.c:195-860, :42-147),
+ * random_channel and multipath_channel batched over trials (oai4g_channel.hip)
+ * ---------------------------------------------------------------------------------------- */
+namespace {
+enum { CH_EPA = 5, CH_EVA = 6, CH_ETU = 7, CH_RAYLEIGH8 = 9, CH_RAYLEIGH1 = 10, CH_RAYLEIGH1_800 = 11, CH_RAYLEIGH1_CORR = 12,
+       CH_RAYLEIGH1_ANTICORR = 13, CH_RICE8 = 14, CH_RICE1 = 15, CH_RICE1_CORR = 16, CH_RICE1_ANTICORR = 17, CH_AWGN = 18 };
+
+/* tap delays in us and powers in dB (3GPP TS 36.101 B.2.1, as random_channel.c:156-163 states them), and the 8-tap
+ * models' linear powers (:165) */
+const double epa_delays[] = {0, .03, .07, .09, .11, .19, .41};
+const double epa_amps_dB[] = {0.0, -1.0, -2.0, -3.0, -8.0, -17.2, -20.8};
+const double eva_delays[] = {0, .03, .15, .31, .37, .71, 1.09, 1.73, 2.51};
+const double eva_amps_dB[] = {0.0, -1.5, -1.4, -3.6, -0.6, -9.1, -7.0, -12.0, -16.9};
+const double etu_delays[] = {0, .05, .12, .2, .23, .5, 1.6, 2.3, 5.0};
+const double etu_amps_dB[] = {-1.0, -1.0, -1.0, 0.0, 0.0, 0.0, -3.0, -5.0, -7.0};
+const double amps8_lin[] = {0.3868472, 0.3094778, 0.1547389, 0.0773694, 0.0386847, 0.0193424, 0.0096712, 0.0038685};
+
+/* scm_corrmat.h R22_sqrt: six 4x4 complex matrices, [re, im] row by row; pinned entry by entry by
+ * tests/golden/channel_ref.json */
+const double r22_sqrt[6][32] = {
+  {0.921700, -0.000000, 0.010380, -0.027448, -0.250153, 0.294754, 0.005961, 0.010769, 0.010380, 0.027448, 0.921700, 0.000000, -0.011595, -0.004130, -0.250153, 0.294754, -0.250153, -0.294754, -0.011595, 0.004130, 0.921700, 0.000000, 0.010380, -0.027448, 0.005961, -0.010769, -0.250153, -0.294754, 0.010380, 0.027448, 0.921700, 0.000000},
+  {0.923810, 0.000000, 0.004069, 0.027832, 0.151730, 0.350180, -0.009882, 0.006114, 0.004069, -0.027832, 0.923810, 0.000000, 0.011218, -0.003029, 0.151730, 0.350180, 0.151730, -0.350180, 0.011218, 0.003029, 0.923810, -0.000000, 0.004069, 0.027832, -0.009882, -0.006114, 0.151730, -0.350180, 0.004069, -0.027832, 0.923810, 0.000000},
+  {0.927613, 0.000000, 0.014253, 0.025767, -0.061171, -0.367133, 0.009258, -0.007340, 0.014253, -0.025767, 0.927613, -0.000000, -0.011138, -0.003942, -0.061171, -0.367133, -0.061171, 0.367133, -0.011138, 0.003942, 0.927613, 0.000000, 0.014253, 0.025767, 0.009258, 0.007340, -0.061171, 0.367133, 0.014253, -0.025767, 0.927613, 0.000000},
+  {0.869794, -0.000000, -0.010613, -0.001218, 0.399115, 0.289852, -0.004464, -0.004096, -0.010613, 0.001218, 0.869794, -0.000000, -0.005276, -0.002978, 0.399115, 0.289852, 0.399115, -0.289852, -0.005276, 0.002978, 0.869794, -0.000000, -0.010613, -0.001218, -0.004464, 0.004096, 0.399115, -0.289852, -0.010613, 0.001218, 0.869794, 0.000000},
+  {0.919726, -0.000000, 0.038700, -0.111146, 0.217804, 0.300925, 0.045531, -0.013659, 0.038700, 0.111146, 0.919726, 0.000000, -0.027201, 0.038983, 0.217804, 0.300925, 0.217804, -0.300925, -0.027201, -0.038983, 0.919726, 0.000000, 0.038700, -0.111146, 0.045531, 0.013659, 0.217804, -0.300925, 0.038700, 0.111146, 0.919726, 0.000000},
+  {0.867608, -0.000000, 0.194097, -0.112414, -0.418811, 0.095938, -0.081264, 0.075727, 0.194097, 0.112414, 0.867608, -0.000000, -0.106125, -0.032801, -0.418811, 0.095938, -0.418811, -0.095938, -0.106125, 0.032801, 0.867608, 0.000000, 0.194097, -0.112414, -0.081264, -0.075727, -0.418811, -0.095938, 0.194097, 0.112414, 0.867608, 0.000000},
+};
+
+struct chan_model_t {
+  oai4g_channel_info_t info;
+  std::vector<double> R;                 /* [n_matrices][npair][npair][re, im] */
+};
+
+/* the descriptor of a model, or false with the error set */
+bool chan_describe(int model, uint32_t nb_tx, uint32_t nb_rx, double BW, chan_model_t &m)
+{
+  if (nb_tx < 1 || nb_tx > 2 || nb_rx < 1 || nb_rx > 2) {
+    set_err("channel: nb_tx %u, nb_rx %u: 1 or 2 antennas a side (the reference's NB_ANTENNAS_TX / _RX)", nb_tx, nb_rx);
+    return false;
+  }
+  if (!(BW > 0.0)) { set_err("channel: BW %g", BW); return false; }
+  oai4g_channel_info_t &d = m.info;
+  memset(&d, 0, sizeof(d));
+  const uint32_t n = nb_tx * nb_rx;
+  double corr = 0.0;                     /* the cross terms' sign of a fully (anti-)correlated transmit pair */
+  const double *delays = nullptr, *dB = nullptr;
+  double Td = 0.0, len = 1.0;
+  d.ricean_factor = 1.0;
+  d.aoa = .03;
+  switch (model) {
+  case CH_EPA: d.nb_taps = 7; Td = .410; delays = epa_delays; dB = epa_amps_dB; break;
+  case CH_EVA: d.nb_taps = 9; Td = 2.51; delays = eva_delays; dB = eva_amps_dB; break;
+  case CH_ETU: d.nb_taps = 9; Td = 5.0; delays = etu_delays; dB = etu_amps_dB; break;
+  case CH_RICE8: d.ricean_factor = 0.1; d.random_aoa = 1; /* fall through */
+  case CH_RAYLEIGH8: d.nb_taps = 8; Td = 0.8; break;
+  case CH_RICE1_CORR: case CH_RICE1_ANTICORR: d.random_aoa = 1; /* fall through */
+  case CH_RICE1: d.ricean_factor = 0.1; /* fall through */
+  case CH_RAYLEIGH1: case CH_RAYLEIGH1_800: case CH_RAYLEIGH1_CORR: case CH_RAYLEIGH1_ANTICORR: d.nb_taps = 1; break;
+  case CH_AWGN: d.nb_taps = 1; d.ricean_factor = 0.0; d.aoa = 0.0; break;
+  case 1: case 2: set_err("channel: model %d (SCM_A / SCM_B): the reference has no such descriptor", model); return false;
+  case 3: case 4: set_err("channel: model %d (SCM_C / SCM_D) is not built", model); return false;
+  default: set_err("channel: model %d is not supported", model); return false;
+  }
+  if (model == CH_RAYLEIGH1_CORR || model == CH_RICE1_CORR) corr = 1.0;
+  if (model == CH_RAYLEIGH1_ANTICORR || model == CH_RICE1_ANTICORR) corr = -1.0;
+  if (dB) {
+    /* amps = 10^(dB / 10) / sum_amps; channel_length from the delay spread (:352) */
+    double sum_amps = 0;
+    for (uint32_t i = 0; i < d.nb_taps; i++) {
+      d.amps[i] = pow(10, .1 * dB[i]);
+      sum_amps += d.amps[i];
+    }
+    for (uint32_t i = 0; i < d.nb_taps; i++) {
+      d.amps[i] /= sum_amps;
+      d.delays[i] = delays[i];
+    }
+    d.aoa = 0;
+    len = 2 * BW * Td + 1 + 2 / (M_PI * M_PI) * log(4 * M_PI * BW * Td);
+  } else if (d.nb_taps == 8) {
+    const double delta_tau = Td / d.nb_taps;
+    for (uint32_t i = 0; i < 8; i++) {
+      d.amps[i] = amps8_lin[i];
+      d.delays[i] = ((double)i) * delta_tau;
+    }
+    len = 11 + 2 * BW * Td;
+  } else {
+    d.amps[0] = 1;
+  }
+  if (!(len < OAI4G_CHAN_MAX_LENGTH + 1.0)) {
+    set_err("channel: channel_length %.0f at BW %g is beyond %d (the reference's field is a uint8_t)", len, BW, OAI4G_CHAN_MAX_LENGTH);
+    return false;
+  }
+  d.channel_length = (uint32_t)(int)len;
+  /* correlation: R22_sqrt[i / 3] for the tapped models at 2x2; the 0.70711 matrices of the _corr / _anticorr models
+   * at 2x1 and 2x2 (:169-190); identity everywhere else, also for the tapped models at 1x2 and 2x1, where the
+   * reference sets only the diagonal of uninitialised memory */
+  d.n_matrices = dB ? 6 : (d.nb_taps - 1) / 3 + 1;
+  m.R.assign((size_t)d.n_matrices * n * n * 2, 0.0);
+  for (uint32_t k = 0; k < d.n_matrices; k++) {
+    double *R = &m.R[(size_t)k * n * n * 2];
+    if (dB && n == 4) {
+      memcpy(R, r22_sqrt[k], sizeof(r22_sqrt[k]));
+      continue;
+    }
+    for (uint32_t r = 0; r < n; r++) R[(r * n + r) * 2] = 1.0;
+    if (corr != 0.0 && nb_tx == 2)
+      for (uint32_t r = 0; r < n; r++) {
+        R[(r * n + r) * 2] = 0.70711;
+        R[(r * n + (r + nb_rx) % n) * 2] = corr * 0.70711;   /* the same receive antenna's other transmit antenna */
+      }
+  }
+  return true;
+}
+
+void chan_r_out(const chan_model_t &m, double *r_sqrt)
+{
+  if (r_sqrt) memcpy(r_sqrt, m.R.data(), m.R.size() * sizeof(double));
+}
+}  // namespace
+
+struct oai4g_channel_config {
+  chan_model_t m;
+  uint32_t nb_tx, nb_rx, n_vectors, dd, calls;
+  double BW, ff, path_loss;
+  dev_buf<double> R, a, ch;
+  dev_buf<uint8_t> first_run;
+};
+
+extern "C" int oai4g_channel_model_describe(int model, uint8_t nb_tx, uint8_t nb_rx, double BW, oai4g_channel_info_t *info,
+                                            double *r_sqrt)
+{
+  chan_model_t m;
+  if (!info) { set_err("channel_model_describe: null info"); return -1; }
+  if (!chan_describe(model, nb_tx, nb_rx, BW, m)) return -1;
+  *info = m.info;
+  chan_r_out(m, r_sqrt);
+  return 0;
+}
+
+extern "C" oai4g_channel_config_t *oai4g_channel_config_create(uint8_t nb_tx, uint8_t nb_rx, int model, double BW,
+                                                               double forgetting_factor, int32_t channel_offset,
+                                                               double path_loss_dB, int n_vectors)
+{
+  std::unique_ptr<oai4g_channel_config_t> cfg(new oai4g_channel_config_t);
+  if (!chan_describe(model, nb_tx, nb_rx, BW, cfg->m)) return nullptr;
+  if (n_vectors < 1 || !(forgetting_factor >= 0.0 && forgetting_factor <= 1.0) || channel_offset == INT32_MIN) {
+    set_err("channel_config_create: n_vectors %d (>= 1), forgetting_factor %g (0..1)", n_vectors, forgetting_factor);
+    return nullptr;
+  }
+  NEED_INIT(nullptr);
+  cfg->nb_tx = nb_tx;
+  cfg->nb_rx = nb_rx;
+  cfg->n_vectors = (uint32_t)n_vectors;
+  cfg->dd = (uint32_t)abs(channel_offset);
+  cfg->calls = 0;
+  cfg->BW = BW;
+  cfg->ff = forgetting_factor;
+  cfg->path_loss = pow(10, path_loss_dB / 20);
+  const size_t n = (size_t)nb_tx * nb_rx;
+  HCK(cfg->R.upload(cfg->m.R), nullptr);
+  HCK(cfg->a.reserve((size_t)n_vectors * cfg->m.info.nb_taps * n * 2), nullptr);
+  HCK(cfg->ch.reserve((size_t)n_vectors * n * cfg->m.info.channel_length * 2), nullptr);
+  HCK(cfg->first_run.upload(std::vector<uint8_t>((size_t)n_vectors, 1)), nullptr);
+  HCK(hipMemset(cfg->a.get(), 0, cfg->a.count() * sizeof(double)), nullptr);
+  HCK(hipMemset(cfg->ch.get(), 0, cfg->ch.count() * sizeof(double)), nullptr);
+  return cfg.release();
+}
+
+extern "C" void oai4g_channel_config_destroy(oai4g_channel_config_t *cfg) { delete cfg; }
+
+extern "C" int oai4g_channel_config_query(const oai4g_channel_config_t *cfg, oai4g_channel_info_t *info, double *r_sqrt)
+{
+  if (!cfg || !info) { set_err("channel_config_query: null argument"); return -1; }
+  *info = cfg->m.info;
+  chan_r_out(cfg->m, r_sqrt);
+  return 0;
+}
+
+extern "C" int oai4g_channel_random_batch(oai4g_channel_config_t *cfg, int n, uint64_t seed, uint32_t first_vector, uint32_t step,
+                                          const double *d_draws, void *stream)
+{
+  if (!cfg || n < 0 || (uint32_t)n > cfg->n_vectors) {
+    set_err("channel_random_batch: %d vectors of a configuration for %u", n, cfg ? cfg->n_vectors : 0u);
+    return -1;
+  }
+  NEED_INIT(-1);
+  const oai4g_channel_info_t &d = cfg->m.info;
+  chan_dev_t c;
+  memset(&c, 0, sizeof(c));
+  c.nb_tx = cfg->nb_tx;
+  c.nb_rx = cfg->nb_rx;
+  c.nb_taps = d.nb_taps;
+  c.channel_length = d.channel_length;
+  c.random_aoa = d.random_aoa;
+  c.ricean_factor = d.ricean_factor;
+  c.aoa = d.aoa;
+  c.BW = cfg->BW;
+  c.sqrt_ff = sqrt(cfg->ff);
+  c.sqrt_1mff = sqrt(1 - cfg->ff);
+  static_assert(OAI4G_CHAN_TAPS == OAI4G_CHANNEL_MAX_TAPS, "the kernel's tap tables hold the header's count");
+  memcpy(c.amps, d.amps, sizeof(c.amps));
+  memcpy(c.delays, d.delays, sizeof(c.delays));
+  c.R = cfg->R.get();
+  c.a = cfg->a.get();
+  c.ch = cfg->ch.get();
+  c.first_run = cfg->first_run.get();
+  HCK(oai4g_launch_channel_taps(c, n, seed, first_vector, step, d_draws, (hipStream_t)stream), -1);
+  return 0;
+}
+
+static bool chan_span(const oai4g_channel_config_t *cfg, const char *who, int first_vector, int n)
+{
+  if (cfg && first_vector >= 0 && n >= 0 && (uint32_t)first_vector <= cfg->n_vectors && (uint32_t)n <= cfg->n_vectors - first_vector)
+    return true;
+  set_err("%s: vectors [%d, +%d) of a configuration for %u", who, first_vector, n, cfg ? cfg->n_vectors : 0u);
+  return false;
+}
+
+extern "C" int oai4g_channel_set_taps(oai4g_channel_config_t *cfg, int first_vector, int n, const double *ch, const double *a)
+{
+  if (!chan_span(cfg, "channel_set_taps", first_vector, n)) return -1;
+  NEED_INIT(-1);
+  const size_t np = (size_t)cfg->nb_tx * cfg->nb_rx, cw = np * cfg->m.info.channel_length * 2, aw = np * cfg->m.info.nb_taps * 2;
+  HCK(hipDeviceSynchronize(), -1);
+  if (ch) HCK(hipMemcpy(cfg->ch.get() + first_vector * cw, ch, (size_t)n * cw * sizeof(double), hipMemcpyHostToDevice), -1);
+  if (a) {
+    HCK(hipMemcpy(cfg->a.get() + first_vector * aw, a, (size_t)n * aw * sizeof(double), hipMemcpyHostToDevice), -1);
+    HCK(hipMemset(cfg->first_run.get() + first_vector, 0, (size_t)n), -1);
+  }
+  return 0;
+}
+
+extern "C" int oai4g_channel_get_taps(oai4g_channel_config_t *cfg, int first_vector, int n, double *ch, double *a)
+{
+  if (!chan_span(cfg, "channel_get_taps", first_vector, n)) return -1;
+  NEED_INIT(-1);
+  const size_t np = (size_t)cfg->nb_tx * cfg->nb_rx, cw = np * cfg->m.info.channel_length * 2, aw = np * cfg->m.info.nb_taps * 2;
+  HCK(hipDeviceSynchronize(), -1);
+  if (ch) HCK(hipMemcpy(ch, cfg->ch.get() + first_vector * cw, (size_t)n * cw * sizeof(double), hipMemcpyDeviceToHost), -1);
+  if (a) HCK(hipMemcpy(a, cfg->a.get() + first_vector * aw, (size_t)n * aw * sizeof(double), hipMemcpyDeviceToHost), -1);
+  return 0;
+}
+
+/* the layout checks both forms share: every sample a segment holds must lie inside it */
+static bool mp_layout_ok(const char *who, const oai4g_channel_config_t *cfg, uint32_t length, uint32_t seg_len, size_t seg_stride)
+{
+  if (length == 0 || seg_len == 0 || (length > seg_len && seg_stride == 0)) {
+    set_err("%s: %u samples in segments of %u, %zu apart", who, length, seg_len, seg_stride);
+    return false;
+  }
+  (void)cfg;
+  return true;
+}
+
+extern "C" int oai4g_multipath_batch(oai4g_channel_config_t *cfg, int n, const int32_t *d_tx, size_t tx_stride, size_t tx_ant_stride,
+                                     uint32_t tx_len, const int32_t *d_tail, uint32_t tail_len, int32_t *d_rx, size_t rx_stride,
+                                     size_t rx_ant_stride, uint32_t seg_len, size_t seg_stride, const int32_t *d_tx_lev,
+                                     double offset_db, uint64_t seed, uint32_t first_vector, void *stream)
+{
+  if (!cfg || n < 0 || (uint32_t)n > cfg->n_vectors || n > 65535) {
+    set_err("multipath_batch: %d vectors of a configuration for %u (at most 65535 a call)", n, cfg ? cfg->n_vectors : 0u);
+    return -1;
+  }
+  if (n > 0 && (!d_tx || !d_rx || !d_tx_lev || (tail_len && !d_tail) || (uint64_t)tx_len + tail_len > 0x7FFFFFFFull)) {
+    set_err("multipath_batch: null array, or more than 2^31 - 1 samples");
+    return -1;
+  }
+  if (!mp_layout_ok("multipath_batch", cfg, tx_len + tail_len, seg_len, seg_stride)) return -1;
+  NEED_INIT(-1);
+  multipath_args_t a;
+  memset(&a, 0, sizeof(a));
+  a.nb_tx = cfg->nb_tx;
+  a.nb_rx = cfg->nb_rx;
+  a.channel_length = cfg->m.info.channel_length;
+  a.dd = cfg->dd;
+  a.tx_len = tx_len;
+  a.tail_len = tail_len;
+  a.seg_len = seg_len;
+  a.tx_stride = tx_stride;
+  a.tx_ant_stride = tx_ant_stride;
+  a.rx_stride = rx_stride;
+  a.rx_ant_stride = rx_ant_stride;
+  a.seg_stride = seg_stride;
+  /* four samples in one 16-byte store where no group of four can straddle a segment or leave the alignment */
+  a.vec4 = ((tx_len + tail_len) % 4 == 0 && seg_len % 4 == 0 && rx_stride % 4 == 0 && rx_ant_stride % 4 == 0 && seg_stride % 4 == 0 &&
+            (uintptr_t)d_rx % 16 == 0) ? 1u : 0u;
+  a.tx = d_tx;
+  a.tail = d_tail;
+  a.rx = d_rx;
+  a.ch = cfg->ch.get();
+  a.path_loss = cfg->path_loss;
+  a.offset_db = offset_db;
+  a.tx_lev = d_tx_lev;
+  a.seed_lo = (uint32_t)seed;
+  a.seed_hi = (uint32_t)(seed >> 32);
+  a.vec0 = first_vector;
+  HCK(oai4g_launch_multipath(a, n, false, (hipStream_t)stream), -1);
+  return 0;
+}
+
+extern "C" int oai4g_random_channel(oai4g_channel_config_t *cfg)
+{
+  if (!cfg) { set_err("random_channel: null configuration"); return -1; }
+  NEED_INIT(-1);
+  if (oai4g_channel_random_batch(cfg, 1, 0, 0, cfg->calls, nullptr, g_scr.s) != 0) return -1;
+  cfg->calls++;
+  HCK(hipStreamSynchronize(g_scr.s), -1);
+  return 0;
+}
+
+extern "C" int oai4g_multipath_channel(oai4g_channel_config_t *cfg, double **tx_sig_re, double **tx_sig_im, double **rx_sig_re,
+                                       double **rx_sig_im, uint32_t length, uint8_t keep_channel)
+{
+  if (!cfg || !tx_sig_re || !tx_sig_im || !rx_sig_re || !rx_sig_im || length == 0 || length > 0x7FFFFFFFu) {
+    set_err("multipath_channel: null argument or length %u", length);
+    return -1;
+  }
+  for (uint32_t j = 0; j < cfg->nb_tx; j++)
+    if (!tx_sig_re[j] || !tx_sig_im[j]) { set_err("multipath_channel: null tx_sig[%u]", j); return -1; }
+  for (uint32_t i = 0; i < cfg->nb_rx; i++)
+    if (!rx_sig_re[i] || !rx_sig_im[i]) { set_err("multipath_channel: null rx_sig[%u]", i); return -1; }
+  NEED_INIT(-1);
+  if (!keep_channel && oai4g_random_channel(cfg) != 0) return -1;
+  if (length <= cfg->dd) return 0;                          /* the reference's loop does not run */
+  /* [antenna][length][re, im] on both sides */
+  const size_t plane = (size_t)length * 2;
+  std::vector<double> h((size_t)std::max(cfg->nb_tx, cfg->nb_rx) * plane);
+  for (uint32_t j = 0; j < cfg->nb_tx; j++)
+    for (size_t i = 0; i < length; i++) {
+      h[j * plane + 2 * i] = tx_sig_re[j][i];
+      h[j * plane + 2 * i + 1] = tx_sig_im[j][i];
+    }
+  stage_t st("multipath_channel");
+  const int r_tx = st.add(cfg->nb_tx * plane * sizeof(double)), r_rx = st.add(cfg->nb_rx * plane * sizeof(double));
+  if (!st.open()) return -1;
+  HCK(st.up(r_tx, h.data(), cfg->nb_tx * plane * sizeof(double)), -1);
+  multipath_args_t a;
+  memset(&a, 0, sizeof(a));
+  a.nb_tx = cfg->nb_tx;
+  a.nb_rx = cfg->nb_rx;
+  a.channel_length = cfg->m.info.channel_length;
+  a.dd = cfg->dd;
+  a.tx_len = length;
+  a.seg_len = length;
+  a.tx_ant_stride = length;
+  a.rx_ant_stride = length;
+  a.tx = st.ptr(r_tx);
+  a.rx = st.ptr(r_rx);
+  a.ch = cfg->ch.get();
+  a.path_loss = cfg->path_loss;
+  HCK(oai4g_launch_multipath(a, 1, true, g_scr.s), -1);
+  const size_t skip = (size_t)cfg->dd * 2 * sizeof(double);
+  for (uint32_t i = 0; i < cfg->nb_rx; i++)
+    HCK(st.down(&h[i * plane + 2 * cfg->dd], r_rx, plane * sizeof(double) - skip, i * plane * sizeof(double) + skip), -1);
+  HCK(st.sync(), -1);
+  for (uint32_t i = 0; i < cfg->nb_rx; i++)
+    for (size_t k = cfg->dd; k < length; k++) {
+      rx_sig_re[i][k] = h[i * plane + 2 * k];
+      rx_sig_im[i][k] = h[i * plane + 2 * k + 1];
+    }
+  return 0;
+}

@@ -737,6 +737,32 @@ hipError_t oai4g_launch_signal_energy(const int32_t *d_x, int n, size_t stride, 
 hipError_t oai4g_launch_awgn(const int32_t *d_tx, size_t tx_stride, uint32_t tx_len, const int32_t *d_tail,
                              uint32_t tail_len, int32_t *d_rx, size_t rx_stride, int n, const int32_t *d_tx_lev,
                              double offset_db, uint64_t seed, uint32_t vec0, hipStream_t s);
+/* a fading-channel configuration as k_channel_taps reads it (oai4g_channel.hip); by value */
+#define OAI4G_CHAN_TAPS 9               /* OAI4G_CHANNEL_MAX_TAPS */
+#define OAI4G_CHAN_MAX_LENGTH 255       /* the reference's channel_length is a uint8_t */
+struct chan_dev_t {
+  uint32_t nb_tx, nb_rx, nb_taps, channel_length, random_aoa;
+  double ricean_factor, aoa, BW, sqrt_ff, sqrt_1mff;
+  double amps[OAI4G_CHAN_TAPS], delays[OAI4G_CHAN_TAPS];
+  const double *R;       /* [ceil(nb_taps / 3)][npair][npair][re, im], npair = nb_tx nb_rx */
+  double *a;             /* [n_vectors][nb_taps][npair][re, im] */
+  double *ch;            /* [n_vectors][npair][channel_length][re, im] */
+  uint8_t *first_run;    /* [n_vectors] */
+};
+hipError_t oai4g_launch_channel_taps(const chan_dev_t &c, int n, uint64_t seed, uint32_t vec0, uint32_t step,
+                                     const double *d_draws, hipStream_t s);
+/* k_multipath's arguments: element strides (int32 IQ words, or [re, im] double pairs in the double form) */
+struct multipath_args_t {
+  uint32_t nb_tx, nb_rx, channel_length, dd, tx_len, tail_len, seg_len, vec4;
+  size_t tx_stride, tx_ant_stride, rx_stride, rx_ant_stride, seg_stride;
+  const void *tx, *tail;
+  void *rx;
+  const double *ch;      /* vector 0's taps: [npair][channel_length][re, im], a vector apart npair channel_length */
+  double path_loss, offset_db;
+  const int32_t *tx_lev; /* [n][nb_tx] */
+  uint32_t seed_lo, seed_hi, vec0;
+};
+hipError_t oai4g_launch_multipath(const multipath_args_t &a, int n, bool double_form, hipStream_t s);
 /* device arrays of oai4g_harq_advance (oai4g_channel.hip: k_harq_advance) */
 struct harq_state_t {
   uint8_t *round;        /* [n_slots] 0 .. num_rounds - 1 */

@@ -28,18 +28,24 @@ k_fep over [trial][2 subframes] -> k_rx_chest (estimation + demodulation + unscr
 subframes apart) -> k_ul_rm_deint + k_td16.  The round loop: k_encode_rv (a redundancy version per
 slot) ... k_ul_rm_harq_tb (rv and clear per slot) + k_td16 -> k_harq_advance, which keeps the rounds,
 dlsim's round_trials / errs counters and the payload refills on the device: a step needs no host
-synchronisation.  Nothing here runs on the CPU but bookkeeping."""
+synchronisation.  Nothing here runs on the CPU but bookkeeping.
+
+With channel_model (a value of SCM_t: dlsim's -g option, dlsim.c:465-525) the link is a fading channel in place of
+the unit tap: ChannelBatch.draw (random_channel, a new channel every round as dlsim's hold_channel = 0 at :2150-2156
+has it, unless hold_channel is asked for) and oai4g_multipath_batch (multipath_channel + the same noise) on the same
+buffers, 1x1, with BW from dlsim's table (:684-703).  The default, None, runs oai4g_awgn_batch as before."""
 import ctypes
 import math
 
 import numpy as np
 
-from . import (FULL_ALLOC_25, ChestBatch, FepBatch, OAI4GError, RxBatch, TxPipeline, _check, _DeviceOwner, frame_parms,
+from . import (FULL_ALLOC_25, ChannelBatch, ChestBatch, FepBatch, OAI4GError, RxBatch, TxPipeline, _check, _DeviceOwner, frame_parms,
                init, lib, make_params, normal_prefix_mod, generate_pilots, UlDecodeBatch)
 
 DCI1_LEN = {6: 23, 15: 25, 25: 27, 50: 27, 100: 39}      # sizeof_DCI1_xMHz_FDD_t (PHY/LTE_TRANSPORT/dci.h)
 FULL_ALLOC = {6: (0x3F, 0, 0, 0), 15: (0x7FFF, 0, 0, 0), 25: FULL_ALLOC_25, 50: (0xFFFFFFFF, 0x3FFFF, 0, 0),
               100: (0xFFFFFFFF, 0xFFFFFFFF, 0xFFFFFFFF, 0xF)}
+CHANNEL_BW = {6: 1.25, 25: 5.0, 50: 10.0, 100: 20.0}      # dlsim.c:684-703: the BW new_channel_desc_scm is given
 
 
 def qm_of(mcs):
@@ -51,7 +57,8 @@ class DlsimBler(_DeviceOwner):
     """Batched BLER trials of one (N_RB_DL, MCS) configuration; see the module docstring."""
 
     def __init__(self, mcs, N_RB_DL=25, batch=4096, subframe=7, num_pdcch_symbols=1, Nid_cell=0, rnti=0x1234,
-                 max_iterations=4, with_dci=True, llr8=False, num_rounds=1):
+                 max_iterations=4, with_dci=True, llr8=False, num_rounds=1, channel_model=None, hold_channel=False,
+                 forgetting_factor=0.0):
         self.L = init()
         self.mcs, self.N_RB, self.B, self.sf = mcs, N_RB_DL, batch, subframe
         self.max_it = max_iterations
@@ -93,6 +100,12 @@ class DlsimBler(_DeviceOwner):
             _check(self.L.oai4g_ul_config_set_decoder(self.dec.cfg, 8) == 0)
         self.C = self.dec.C
         self.offset_fac = 10 * math.log10(self.N / (12.0 * N_RB_DL))
+        self.chan, self.hold_channel, self._drawn = None, hold_channel, False
+        if channel_model is not None:
+            if N_RB_DL not in CHANNEL_BW:
+                raise ValueError("dlsim gives no channel bandwidth for N_RB_DL = %d" % N_RB_DL)
+            self.chan = self._own(ChannelBatch(1, 1, channel_model, CHANNEL_BW[N_RB_DL], batch,
+                                               forgetting_factor=forgetting_factor))
         if not 1 <= num_rounds <= 4:
             raise ValueError("num_rounds must be 1..4 (dlsim's round loop)")
         self.num_rounds = num_rounds
@@ -112,24 +125,43 @@ class DlsimBler(_DeviceOwner):
     def sigma_offset(self, snr_db, pa_db=0.0):
         return self.offset_fac - snr_db - pa_db
 
-    def run_batch(self, snr_db, seed, first_trial=0, want_bits=False):
-        """One batch of trials; returns the per-trial error flags (and decoded / sent bytes)."""
+    def _channel(self, snr_db, seed, first_vector, step):
+        """the link of one subframe of every trial: tx_lev, then the unit tap or the fading channel, plus noise"""
+        L, B, d_iq = self.L, self.B, self.tx.d_iq
+        _check(L.oai4g_signal_energy_batch(d_iq, B, self.spt, self.spt, self.d_lev, None) == 0)
+        if self.chan is None:
+            _check(L.oai4g_awgn_batch(d_iq, self.spt, self.spt, self.d_tail, self.spt, self.fep.d_rx, 2 * self.spt, B,
+                                      self.d_lev, self.sigma_offset(snr_db), seed, first_vector, None) == 0)
+            return
+        if not (self.hold_channel and self._drawn):       # dlsim.c:2150-2156: a new channel every round
+            self.chan.draw(seed, first_vector, step)
+            self._drawn = True
+        self.chan.run(d_iq, self.spt, 0, self.spt, self.d_tail, self.spt, self.fep.d_rx, 2 * self.spt, 0, 2 * self.spt, 0,
+                      self.d_lev, self.sigma_offset(snr_db), seed, first_vector)
+
+    def channel_gain(self):
+        """each trial's sum_k |ch[k]|^2 of the channel it last went through"""
+        if self.chan is None:
+            return np.ones(self.B)
+        return (np.abs(self.chan.taps()[1]) ** 2).sum(axis=(1, 2))
+
+    def run_batch(self, snr_db, seed, first_trial=0, want_bits=False, want_gain=False):
+        """One batch of trials; returns the per-trial error flags (and decoded / sent bytes; with want_gain each
+        trial's channel gain behind them)."""
         L, B = self.L, self.B
         self.tx.fill_payload(seed)
         self.tx.run()
-        d_iq = self.tx.d_iq
-        _check(L.oai4g_signal_energy_batch(d_iq, B, self.spt, self.spt, self.d_lev, None) == 0)
-        _check(L.oai4g_awgn_batch(d_iq, self.spt, self.spt, self.d_tail, self.spt, self.fep.d_rx, 2 * self.spt, B,
-                                  self.d_lev, self.sigma_offset(snr_db), seed, first_trial, None) == 0)
+        self._channel(snr_db, seed, first_trial, 0)
         self.fep.run()
         self.rx.launch_estimated(self.ce, self.fep.d_rxF, 1)
         _check(L.oai4g_ul_decode_batch(self.dec.cfg, B, self.rx.d_llr, self.rx.stride, self.dec.d_c,
                                        self.dec.c_stride, self.dec.d_it, None) == 0)
         it, c = self.dec.results()
         err = np.any(it > self.max_it, axis=1)
-        if not want_bits:
-            return err
-        return err, c, self.tx.download_payload()
+        out = (err, c, self.tx.download_payload()) if want_bits else (err,)
+        if want_gain:
+            out += (self.channel_gain(),)
+        return out if len(out) > 1 else err
 
     def reset_rounds(self, seed):
         """Every slot at round 0 of its transport block 0: payloads oai4g_fill_payload(seed), counters 0."""
@@ -140,7 +172,7 @@ class DlsimBler(_DeviceOwner):
         st[2 * B:3 * B] = 1                                   # clear
         self._put(self.d_state, st)
         self.tx.fill_payload(seed)
-        self._seed, self._step = seed, 0
+        self._seed, self._step, self._drawn = seed, 0, False
 
     def step(self, snr_db):
         """One subframe of every slot, enqueued without a host synchronisation: transmit with the slot's
@@ -148,10 +180,7 @@ class DlsimBler(_DeviceOwner):
         L, B = self.L, self.B
         _check(L.oai4g_tx_batch_rv(self.tx.cfg, B, self.tx.d_payload, self.d_rv, self.tx.d_work, self.tx.d_iq,
                                    None) == 0)
-        d_iq = self.tx.d_iq
-        _check(L.oai4g_signal_energy_batch(d_iq, B, self.spt, self.spt, self.d_lev, None) == 0)
-        _check(L.oai4g_awgn_batch(d_iq, self.spt, self.spt, self.d_tail, self.spt, self.fep.d_rx, 2 * self.spt, B,
-                                  self.d_lev, self.sigma_offset(snr_db), self._seed, self._step * B, None) == 0)
+        self._channel(snr_db, self._seed, self._step * B, self._step)
         self.fep.run()
         self.rx.launch_estimated(self.ce, self.fep.d_rxF, 1)
         _check(L.oai4g_ul_decode_batch_harq_tb(self.dec.cfg, B, self.rx.d_llr, self.rx.stride, self.dec.d_w,
@@ -222,4 +251,4 @@ def wilson(k, n, z=1.96):
     return max(0.0, c - h), min(1.0, c + h)
 
 
-__all__ = ["DlsimBler", "qm_of", "wilson", "OAI4GError", "lib"]
+__all__ = ["DlsimBler", "CHANNEL_BW", "qm_of", "wilson", "OAI4GError", "lib"]

@@ -1227,6 +1227,95 @@ int oai4g_harq_advance(int n_slots, int C, uint8_t max_iterations, int num_round
                        uint8_t *d_round, uint32_t *d_trial, uint8_t *d_rv, uint8_t *d_clear, uint8_t *d_done,
                        uint32_t *d_counters, uint8_t *d_payload, size_t row_bytes, uint64_t seed, void *stream);
 
+/* ---------------- SC-FDMA: the PUSCH DFT sizes, ulsch_modulation and lte_idft ---------------- */
+/* The 33 mixed-radix "PUSCH DFTs" of PHY/TOOLS/lte_dfts.c (:3510-16087), bit-exact: 12, 24, 36, 48, 60, 72, 96, 108,
+ * 120, 144, 180, 192, 216, 240, 288, 300, 324, 360, 384, 432, 480, 540, 576, 600, 648, 720, 864, 900, 960, 972, 1080,
+ * 1152, 1200.  Every other size is refused, 768 (64 PRB) included: the reference has no dft768 (its lte_idft logs
+ * "Unsupported" and returns with the input conjugated; its dft_lte copies out an unwritten buffer).
+ *
+ * The plan of one size as the engine runs it, outermost level first: dft<size> splits off radix[0] and runs radix[0]
+ * sub-transforms of sub_size[0], and so on down to the twelve-point leaf.  norm[l] is the constant of the
+ * mulhi_int16 that follows level l when the size is called with scale_flag 1 (0: that level is not scaled; dft96,
+ * dft108 and dft120 call their sub-transforms with scale_flag 0); leaf_norm is 9459 for size 12 (applied by dft_lte
+ * and lte_idft behind dft12) and 0 otherwise.  Level l's twiddles are entries tw_offset[l] .. of the table: for q = 1
+ * .. radix - 1 and k = 1 .. sub_size - 1, entry (q - 1)(sub_size - 1) + k - 1 = 32767 (cos, -sin)(2 pi q k / (radix
+ * sub_size)), truncated toward zero where radix sub_size <= 300 and floor() above, as the reference's tables are. */
+#define OAI4G_PUSCH_MAX_LEVELS 4
+typedef struct {
+  uint16_t size, n_levels;
+  uint8_t radix[OAI4G_PUSCH_MAX_LEVELS];
+  uint16_t sub_size[OAI4G_PUSCH_MAX_LEVELS];
+  int16_t norm[OAI4G_PUSCH_MAX_LEVELS];
+  int16_t leaf_norm;
+  uint16_t pad;
+  uint32_t tw_offset[OAI4G_PUSCH_MAX_LEVELS];
+  uint32_t n_twiddles;
+} oai4g_pusch_plan_t;
+/* Host only, no device: the plan of Msc, and its twiddles into `twiddles` ([capacity][2] int16, null to skip).
+ * -1 (oai4g_last_error says why) for 768, every other size not listed, or capacity < n_twiddles. */
+int oai4g_pusch_dft_plan(int32_t Msc, oai4g_pusch_plan_t *plan, int16_t *twiddles, uint32_t capacity);
+
+/* One PUSCH allocation of one UE over a run of subframes: first_rb / nb_rb (Msc = 12 nb_rb), Qm 2 / 4 / 6, srs_active
+ * 0 / 1 (the last symbol is left out of the mapping), the scrambling identity (rnti, frame_parms->Nid_cell) and the
+ * subframe number of batch element i, (first_subframe + i subframe_step) % 10.  The plan and twiddles of Msc and the
+ * Gold words of the ten subframe numbers are built here and uploaded once.  Refused (null, oai4g_last_error set):
+ * what ulsch_modulation refuses (nb_rb 0, first_rb > 25), a size with no dft<Msc>, an allocation that leaves the
+ * band (first_rb + nb_rb > N_RB_DL), and first_carrier_offset + 12 first_rb == ofdm_symbol_size (N_RB_DL 6 with
+ * first_rb 3, N_RB_DL 50 with first_rb 25), where the reference's wrap test ('>') lets it write REs N .. N + Msc - 1
+ * of every symbol, past the symbol and in the last one past the subframe. */
+typedef struct oai4g_pusch_config oai4g_pusch_config_t;
+oai4g_pusch_config_t *oai4g_pusch_config_create(const oai4g_frame_parms_t *frame_parms, uint16_t first_rb, uint16_t nb_rb,
+                                                uint8_t Qm, uint8_t srs_active, uint16_t rnti, uint8_t first_subframe,
+                                                uint8_t subframe_step);
+void oai4g_pusch_config_destroy(oai4g_pusch_config_t *cfg);
+/* ulsch_modulation (PHY/LTE_TRANSPORT/ulsch_modulation.c:376-783, cooperation_flag != 2) of n_sf subframes in one
+ * launch: d_h [n_sf] rows of h_stride >= G bytes (ulsch->h: 0 / 1, PUSCH_x = 2, PUSCH_y = 3; G = 12 nb_rb Qm
+ * Nsymb_pusch), d_txdataF [n_sf][symbols_per_tti][ofdm_symbol_size] (one subframe of txdataF[0] per element).  Only
+ * the REs the reference writes are written: subcarriers (first_carrier_offset + 12 first_rb + i) mod
+ * ofdm_symbol_size, i < Msc, of the symbols other than 3 / 10 (normal prefix) or 2 / 8 (extended), the last symbol
+ * left out when srs_active.  Asynchronous on `stream`.  Returns 0 or -1. */
+int oai4g_pusch_mod_batch(oai4g_pusch_config_t *cfg, int n_sf, const uint8_t *d_h, size_t h_stride, int16_t amp,
+                          int32_t *d_txdataF, void *stream);
+/* dft_lte's contract (ulsch_modulation.c:53-373) on d_d / d_z [n_sf][Nsymb_pusch][Msc] (they may be the same array):
+ * each column through dft<Msc> with scale_flag 1 (12: dft12, then 9459).  Asynchronous on `stream`.  0 or -1. */
+int oai4g_pusch_dft_batch(oai4g_pusch_config_t *cfg, int n_sf, const int32_t *d_d, int32_t *d_z, void *stream);
+/* lte_idft (PHY/LTE_TRANSPORT/ulsch_demodulation.c:58-465) in place on d_comp [n_sf][symbols_per_tti][12 N_RB_DL]
+ * (rxdataF_comp[0]): subcarriers < Msc of symbols 0, 1, 2, 4 .. 9, 11, 12, 13 (normal prefix) or 0, 1, 3 .. 7, 9, 10,
+ * 11 (extended), whatever srs_active is: conjugate (an imaginary part of -32768 stays), forward transform,
+ * conjugate.  The pilot symbols and the subcarriers >= Msc are not touched.  Asynchronous on `stream`.  0 or -1. */
+int oai4g_pusch_idft_batch(oai4g_pusch_config_t *cfg, int n_sf, int32_t *d_comp, void *stream);
+/* Drop-ins on host buffers behind the reference's call shapes.
+ * oai4g_dft_lte: the reference always transforms 12 columns of d (stride Msc), whatever Nsymb is; the columns past
+ * Nsymb hold stale data there and their outputs are never mapped.  This one transforms Nsymb (<= 12) columns and
+ * leaves z beyond them untouched.
+ * oai4g_pusch_dft: one transform in the reference's dft<Msc>(x, y, scale_flag) contract, on plain samples (one
+ * transform, not the reference's four interleaved ones); dft12 has no flag and never scales.
+ * oai4g_lte_idft: z is one subframe of rxdataF_comp[0], symbols_per_tti rows of 12 N_RB_DL words. */
+int oai4g_dft_lte(int32_t *z, const int32_t *d, int32_t Msc_PUSCH, uint8_t Nsymb);
+int oai4g_pusch_dft(int32_t Msc, const int16_t *x, int16_t *y, uint8_t scale_flag);
+int oai4g_lte_idft(const oai4g_frame_parms_t *frame_parms, int32_t *z, uint16_t Msc_PUSCH);
+/* The fields of LTE_UE_ULSCH_t (PHY/LTE_TRANSPORT/defs.h:258-348) and LTE_UL_UE_HARQ_t that ulsch_modulation reads;
+ * harq_pid stands for subframe2harq_pid(frame_parms, frame, subframe), which the caller evaluates. */
+typedef struct {
+  uint16_t first_rb, nb_rb;
+  uint8_t mcs;
+  uint8_t pad[3];
+} oai4g_ul_harq_t;
+typedef struct {
+  const oai4g_ul_harq_t *harq_processes[8];
+  const uint8_t *h;
+  uint16_t rnti;
+  uint8_t harq_pid, Nsymb_pusch, srs_active, cooperation_flag;
+  uint8_t pad[2];
+} oai4g_ue_ulsch_t;
+/* ulsch_modulation: writes the allocation into txdataF[0] at symbol_offset = ofdm_symbol_size (l + subframe
+ * symbols_per_tti), a frame of ten subframes.  0: done.  1: the reference's own refusal (harq_pid > 7, nb_rb 0,
+ * first_rb > 25), nothing written, as there.  -1: refused here, nothing written: cooperation_flag 2 (distributed
+ * Alamouti), Nsymb_pusch other than the symbols the mapping takes, and what oai4g_pusch_config_create refuses.
+ * oai4g_last_error says which in both cases. */
+int oai4g_ulsch_modulation(int32_t *const *txdataF, int16_t amp, uint32_t frame, uint32_t subframe,
+                           const oai4g_frame_parms_t *frame_parms, const oai4g_ue_ulsch_t *ulsch);
+
 #ifdef __cplusplus
 }
 #endif

@@ -473,6 +473,19 @@ _SIGS = {
     "oai4g_random_channel": (ctypes.c_int, [ctypes.c_void_p]),
     "oai4g_multipath_channel": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_void_p)] * 4
                                 + [ctypes.c_uint32, ctypes.c_uint8]),
+    "oai4g_pusch_dft_plan": (ctypes.c_int, [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]),
+    "oai4g_pusch_config_create": (ctypes.c_void_p, [ctypes.POINTER(FrameParms), ctypes.c_uint16, ctypes.c_uint16, ctypes.c_uint8,
+                                                    ctypes.c_uint8, ctypes.c_uint16, ctypes.c_uint8, ctypes.c_uint8]),
+    "oai4g_pusch_config_destroy": (None, [ctypes.c_void_p]),
+    "oai4g_pusch_mod_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int16,
+                                             ctypes.c_void_p, ctypes.c_void_p]),
+    "oai4g_pusch_dft_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "oai4g_pusch_idft_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    "oai4g_dft_lte": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint8]),
+    "oai4g_pusch_dft": (ctypes.c_int, [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint8]),
+    "oai4g_lte_idft": (ctypes.c_int, [ctypes.POINTER(FrameParms), ctypes.c_void_p, ctypes.c_uint16]),
+    "oai4g_ulsch_modulation": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int16, ctypes.c_uint32, ctypes.c_uint32,
+                                              ctypes.POINTER(FrameParms), ctypes.c_void_p]),
 }
 
 
@@ -2235,3 +2248,143 @@ def unpack_bits(words, nbits):
     """Packed LSB-first uint32 words -> uint8 bit array."""
     b = np.unpackbits(np.ascontiguousarray(words, dtype="<u4").view(np.uint8), bitorder="little")
     return b[:nbits]
+
+
+# ------------------------------------------------------------------------------------------
+# SC-FDMA: the PUSCH DFT sizes, ulsch_modulation, lte_idft
+# ------------------------------------------------------------------------------------------
+class PuschPlan(ctypes.Structure):
+    """oai4g_pusch_plan_t"""
+    _fields_ = [("size", ctypes.c_uint16), ("n_levels", ctypes.c_uint16), ("radix", ctypes.c_uint8 * 4),
+                ("sub_size", ctypes.c_uint16 * 4), ("norm", ctypes.c_int16 * 4), ("leaf_norm", ctypes.c_int16),
+                ("pad", ctypes.c_uint16), ("tw_offset", ctypes.c_uint32 * 4), ("n_twiddles", ctypes.c_uint32)]
+
+
+class UlHarq(ctypes.Structure):
+    """oai4g_ul_harq_t"""
+    _fields_ = [("first_rb", ctypes.c_uint16), ("nb_rb", ctypes.c_uint16), ("mcs", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 3)]
+
+
+class UeUlsch(ctypes.Structure):
+    """oai4g_ue_ulsch_t"""
+    _fields_ = [("harq_processes", ctypes.POINTER(UlHarq) * 8), ("h", ctypes.c_void_p), ("rnti", ctypes.c_uint16),
+                ("harq_pid", ctypes.c_uint8), ("Nsymb_pusch", ctypes.c_uint8), ("srs_active", ctypes.c_uint8),
+                ("cooperation_flag", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 2)]
+
+
+def pusch_dft_plan(Msc):
+    """oai4g_pusch_dft_plan: (PuschPlan, twiddles int16 [n_twiddles][2]).  Host only; raises for a size the reference
+    has no transform for."""
+    plan = PuschPlan()
+    tw = np.zeros((2048, 2), dtype=np.int16)
+    _check(lib().oai4g_pusch_dft_plan(Msc, ctypes.byref(plan), _ptr(tw), len(tw)) == 0)
+    return plan, tw[:plan.n_twiddles].copy()
+
+
+def pusch_dft(Msc, x, scale_flag=1):
+    """oai4g_pusch_dft: dft<Msc>(x, y, scale_flag) of one transform on plain samples, int16 [Msc][2] -> the same"""
+    x = np.ascontiguousarray(x, dtype=np.int16)
+    assert x.size == 2 * Msc
+    y = np.zeros((Msc, 2), dtype=np.int16)
+    _check(lib().oai4g_pusch_dft(Msc, _ptr(x), _ptr(y), scale_flag) == 0)
+    return y
+
+
+def dft_lte(d, Msc, Nsymb, z=None):
+    """oai4g_dft_lte: d int16 [>= Nsymb Msc][2] -> z (the given array, whose words past Nsymb Msc stay as they are)"""
+    d = np.ascontiguousarray(d, dtype=np.int16).reshape(-1, 2)
+    assert len(d) >= Nsymb * Msc
+    z = np.zeros((Nsymb * Msc, 2), dtype=np.int16) if z is None else z
+    assert z.flags.c_contiguous and z.dtype == np.int16 and z.size >= 2 * Nsymb * Msc
+    _check(lib().oai4g_dft_lte(_ptr(z), _ptr(d), Msc, Nsymb) == 0)
+    return z
+
+
+def lte_idft(fp, comp, Msc):
+    """oai4g_lte_idft in place on comp int16 [symbols_per_tti][12 N_RB_DL][2]"""
+    assert comp.flags.c_contiguous and comp.dtype == np.int16 and comp.size == 2 * fp.symbols_per_tti * 12 * fp.N_RB_DL
+    _check(lib().oai4g_lte_idft(ctypes.byref(fp), _ptr(comp), Msc) == 0)
+    return comp
+
+
+def ulsch_modulation(txdataF0, amp, subframe, fp, first_rb, nb_rb, mcs, h, rnti, srs_active=0, harq_pid=0, cooperation_flag=0,
+                     Nsymb_pusch=None):
+    """oai4g_ulsch_modulation into txdataF0 int16 [10 symbols_per_tti][ofdm_symbol_size][2], one frame of antenna 0.
+    Returns 0, or 1 for the reference's own refusals (nothing written); a refusal of the library raises."""
+    assert txdataF0.flags.c_contiguous and txdataF0.dtype == np.int16
+    assert txdataF0.size == 2 * 10 * fp.symbols_per_tti * fp.ofdm_symbol_size
+    h = np.ascontiguousarray(h, dtype=np.uint8)
+    harq = UlHarq(first_rb, nb_rb, mcs)
+    u = UeUlsch()
+    for i in range(8):
+        u.harq_processes[i] = ctypes.pointer(harq)
+    u.h, u.rnti, u.harq_pid, u.srs_active, u.cooperation_flag = h.ctypes.data, rnti, harq_pid, srs_active, cooperation_flag
+    u.Nsymb_pusch = fp.symbols_per_tti - 2 - srs_active if Nsymb_pusch is None else Nsymb_pusch
+    tx = (ctypes.c_void_p * 1)(txdataF0.ctypes.data)
+    r = lib().oai4g_ulsch_modulation(tx, amp, 0, subframe, ctypes.byref(fp), ctypes.byref(u))
+    _check(r >= 0)
+    return r
+
+
+class _PuschBatch(_DeviceOwner):
+    """Device-resident PUSCH transmit / transform precoding of n_sf subframes of one allocation:
+    d_h [n_sf][G] -> d_txdataF [n_sf][symbols_per_tti][ofdm_symbol_size] (launch_mod, oai4g_pusch_mod_batch);
+    d_d -> d_z [n_sf][Nsymb_pusch][Msc] (launch_dft, oai4g_pusch_dft_batch);
+    d_comp [n_sf][symbols_per_tti][12 N_RB_DL] in place (launch_idft, oai4g_pusch_idft_batch).
+    Each buffer exists once its upload asked for it.  Public as PuschBatch."""
+
+    def __init__(self, fp, n_sf, first_rb, nb_rb, Qm, srs_active=0, rnti=0x1234, first_subframe=0, subframe_step=1):
+        self.L, self.fp, self.n_sf = init(), fp, n_sf
+        self.Msc, self.Qm = 12 * nb_rb, Qm
+        self.nsymb, self.N = fp.symbols_per_tti, fp.ofdm_symbol_size
+        self.Nsymb_pusch = self.nsymb - 2 - srs_active
+        self.G = self.Msc * Qm * self.Nsymb_pusch
+        self.cfg = self._own(self.L.oai4g_pusch_config_create(ctypes.byref(fp), first_rb, nb_rb, Qm, srs_active, rnti,
+                                                              first_subframe, subframe_step), self.L.oai4g_pusch_config_destroy)
+        self.d_h = self.d_txdataF = self.d_d = self.d_z = self.d_comp = None
+
+    def _up(self, name, a, dtype, size):
+        a = np.ascontiguousarray(a, dtype=dtype)
+        assert a.size == size, (name, a.size, size)
+        if getattr(self, name) is None:
+            setattr(self, name, self._dev(a.nbytes))
+        self._put(getattr(self, name), a)
+
+    def upload_h(self, h):
+        """uint8 [n_sf][G]"""
+        self._up("d_h", h, np.uint8, self.n_sf * self.G)
+
+    def upload_grid(self, grid):
+        """int16 [n_sf][symbols_per_tti][ofdm_symbol_size][2]: what the REs the modulator does not write keep"""
+        self._up("d_txdataF", grid, np.int16, 2 * self.n_sf * self.nsymb * self.N)
+
+    def launch_mod(self, amp, stream=None):
+        _check(self.L.oai4g_pusch_mod_batch(self.cfg, self.n_sf, self.d_h, self.G, amp, self.d_txdataF, stream) == 0)
+
+    def grid(self):
+        return self._get(self.d_txdataF, (self.n_sf, self.nsymb, self.N, 2), np.int16)
+
+    def upload_d(self, d):
+        """int16 [n_sf][Nsymb_pusch][Msc][2]"""
+        self._up("d_d", d, np.int16, 2 * self.n_sf * self.Nsymb_pusch * self.Msc)
+        if self.d_z is None:
+            self.d_z = self._dev(4 * self.n_sf * self.Nsymb_pusch * self.Msc)
+
+    def launch_dft(self, stream=None):
+        _check(self.L.oai4g_pusch_dft_batch(self.cfg, self.n_sf, self.d_d, self.d_z, stream) == 0)
+
+    def z(self):
+        return self._get(self.d_z, (self.n_sf, self.Nsymb_pusch, self.Msc, 2), np.int16)
+
+    def upload_comp(self, comp):
+        """int16 [n_sf][symbols_per_tti][12 N_RB_DL][2]"""
+        self._up("d_comp", comp, np.int16, 2 * self.n_sf * self.nsymb * 12 * self.fp.N_RB_DL)
+
+    def launch_idft(self, stream=None):
+        _check(self.L.oai4g_pusch_idft_batch(self.cfg, self.n_sf, self.d_comp, stream) == 0)
+
+    def comp(self):
+        return self._get(self.d_comp, (self.n_sf, self.nsymb, 12 * self.fp.N_RB_DL, 2), np.int16)
+
+
+PuschBatch = _PuschBatch    # private by name like _SyncBatch: its lifetime cases are in tests/test_pusch_cpu.py

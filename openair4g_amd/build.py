@@ -12,7 +12,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libopenair4g_amd.so")
-SOURCES = ["oai4g_host.cpp", "oai4g_encode.hip", "oai4g_ofdm.hip", "oai4g_decode.hip", "oai4g_decode8.hip", "oai4g_fep.hip", "oai4g_ctrl.hip", "oai4g_ctrl_rx.hip", "oai4g_pdcch_front.hip", "oai4g_pbch_front.hip", "oai4g_sync_rx.hip", "oai4g_rx.hip", "oai4g_chest.hip", "oai4g_channel.hip", "oai4g_dist.cpp"]
+SOURCES = ["oai4g_host.cpp", "oai4g_encode.hip", "oai4g_ofdm.hip", "oai4g_decode.hip", "oai4g_decode8.hip", "oai4g_fep.hip", "oai4g_ctrl.hip", "oai4g_ctrl_rx.hip", "oai4g_pdcch_front.hip", "oai4g_pbch_front.hip", "oai4g_sync_rx.hip", "oai4g_rx.hip", "oai4g_chest.hip", "oai4g_channel.hip", "oai4g_pusch.hip", "oai4g_dist.cpp"]
 EXTRA = [os.path.join(ROOT, "include", "oai4g_qpp.c"), os.path.join(ROOT, "include", "oai4g_tbs.c")]
 # every header a source includes: the library and each object are rebuilt when one of them changes
 HEADERS = tuple(os.path.join(CSRC, h) for h in ("oai4g_internal.h", "oai4g_dft_prims.h", "oai4g_rx_prims.h", "oai4g_front_prims.h", "oai4g_dev_buf.h", "oai4g_rm_geom.h")) + \

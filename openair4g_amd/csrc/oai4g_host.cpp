@@ -6754,3 +6754,326 @@ extern "C" int oai4g_multipath_channel(oai4g_channel_config_t *cfg, double **tx_
     }
   return 0;
 }
+
+/* ------------------------------------------------------------------------------------------
+ * SC-FDMA: the PUSCH DFT sizes (PHY/TOOLS/lte_dfts.c:3510-16087), ulsch_modulation, lte_idft.
+ * ---------------------------------------------------------------------------------------- */
+/* dft<N>: the factor it splits off, the constant of its final mulhi_int16 and whether it calls its sub-transforms with
+ * scale_flag 1, read from the code (dft192 = 4 x 48, dft324 = 3 x 108, dft600 = 2 x 300 ...), not from factorisation
+ * rules.  Norms: dft_norm_table[1..15] for 24..300; entry 14, 16384 or ONE_OVER_SQRT2_Q15 above. */
+namespace {
+struct pusch_size_t {
+  uint16_t N;
+  uint8_t r, sub_scaled;
+  int16_t norm;
+};
+const pusch_size_t k_pusch_sizes[] = {
+    {24, 2, 1, 6689},    {36, 3, 1, 5461},    {48, 4, 1, 4729},    {60, 5, 1, 4230},    {72, 2, 1, 23170},   {96, 2, 0, 3344},
+    {108, 3, 0, 3153},   {120, 2, 0, 2991},   {144, 3, 1, 18918},  {180, 3, 1, 18918},  {192, 4, 1, 16384},  {216, 3, 1, 18918},
+    {240, 4, 1, 16384},  {288, 3, 1, 18918},  {300, 5, 1, 14654},  {324, 3, 1, 18918},  {360, 3, 1, 18918},  {384, 4, 1, 16384},
+    {432, 4, 1, 16384},  {480, 4, 1, 16384},  {540, 3, 1, 18918},  {576, 3, 1, 18918},  {600, 2, 1, 23170},  {648, 3, 1, 18918},
+    {720, 4, 1, 16384},  {864, 3, 1, 18918},  {900, 3, 1, 18918},  {960, 4, 1, 16384},  {972, 3, 1, 18918},  {1080, 3, 1, 18918},
+    {1152, 4, 1, 16384}, {1200, 4, 1, 16384}};
+
+const pusch_size_t *pusch_size(int32_t N)
+{
+  for (const pusch_size_t &e : k_pusch_sizes)
+    if (e.N == N) return &e;
+  return nullptr;
+}
+
+/* the plan of dft<Msc>(x, y, scale_flag) (leaf12: the 9459 product dft_lte and lte_idft put behind dft12) and its twiddles */
+bool pusch_plan(const char *who, int32_t Msc, bool scale_flag, bool leaf12, oai4g_pusch_plan_t &pl, std::vector<int16_t> &tw)
+{
+  memset(&pl, 0, sizeof(pl));
+  tw.clear();
+  if (Msc == 768) { set_err("%s: Msc 768 (64 PRB): the reference has no dft768", who); return false; }
+  if (Msc != 12 && !pusch_size(Msc)) { set_err("%s: Msc %d is not one of the reference's 33 PUSCH DFT sizes", who, Msc); return false; }
+  pl.size = (uint16_t)Msc;
+  pl.leaf_norm = (int16_t)(Msc == 12 && leaf12 ? 9459 : 0);
+  bool scaled = scale_flag;
+  for (int32_t N = Msc; N != 12;) {
+    const pusch_size_t *e = pusch_size(N);
+    const uint32_t l = pl.n_levels++, M = N / e->r;
+    pl.radix[l] = e->r;
+    pl.sub_size[l] = (uint16_t)M;
+    pl.norm[l] = (int16_t)(scaled ? e->norm : 0);
+    pl.tw_offset[l] = (uint32_t)tw.size() / 2;
+    for (uint32_t q = 1; q < e->r; q++)
+      for (uint32_t k = 1; k < M; k++) {
+        const double th = 2.0 * M_PI * q * k / N, c = 32767.0 * cos(th), s = -32767.0 * sin(th);
+        tw.push_back((int16_t)(N <= 300 ? trunc(c) : floor(c)));   /* the tables up to 300 truncate, the later ones floor */
+        tw.push_back((int16_t)(N <= 300 ? trunc(s) : floor(s)));
+      }
+    scaled = e->sub_scaled != 0;
+    N = (int32_t)M;
+  }
+  pl.n_twiddles = (uint32_t)tw.size() / 2;
+  return true;
+}
+
+/* a plan as the kernels read it, with its twiddles on the device */
+struct pusch_engine_t {
+  pusch_plan_t p;
+  dev_buf<uint2> tw;
+};
+uint32_t rcp32(uint32_t d) { return (uint32_t)((0x100000000ull + d - 1) / d); }
+
+bool pusch_engine(const char *who, int32_t Msc, bool scale_flag, bool leaf12, pusch_engine_t &e)
+{
+  oai4g_pusch_plan_t pl;
+  std::vector<int16_t> tw;
+  if (!pusch_plan(who, Msc, scale_flag, leaf12, pl, tw)) return false;
+  pusch_plan_t &p = e.p;
+  memset(&p, 0, sizeof(p));
+  p.N = pl.size;
+  p.n_lvl = pl.n_levels;
+  p.spw = p.N <= 24 ? 16 : p.N <= 48 ? 8 : p.N <= 108 ? 4 : p.N <= 240 ? 2 : 1;
+  p.lds_sym = 2 * p.N + p.N / 12;
+  p.leaf_norm = (uint32_t)pl.leaf_norm;
+  for (uint32_t l = 0; l < p.n_lvl; l++) {
+    p.radix[l] = pl.radix[l];
+    p.M[l] = pl.sub_size[l];
+    p.norm[l] = (uint32_t)pl.norm[l];
+    p.tw_off[l] = pl.tw_offset[l];
+    p.rcp_r[l] = rcp32(p.radix[l]);
+    p.rcp_m1[l] = rcp32(p.M[l] - 1);
+  }
+  std::vector<uint2> dtw(std::max<size_t>(1, pl.n_twiddles));
+  for (uint32_t i = 0; i < pl.n_twiddles; i++) {
+    const uint16_t re = (uint16_t)tw[2 * i], im = (uint16_t)tw[2 * i + 1], nim = (uint16_t)(-(int32_t)tw[2 * i + 1]);
+    dtw[i] = make_uint2((uint32_t)re | (uint32_t)nim << 16, (uint32_t)im | (uint32_t)re << 16);
+  }
+  if (e.tw.upload(dtw) != hipSuccess) { set_err("%s: twiddle upload failed", who); return false; }
+  return true;
+}
+
+void pusch_data_symbols(uint32_t Ncp, bool mapping, uint32_t srs_active, uint32_t row, pusch_grid_t &g)
+{
+  memset(&g, 0, sizeof(g));
+  g.nsymb = Ncp ? 12 : 14;
+  g.row = row;
+  const uint32_t p0 = Ncp ? 2 : 3, p1 = Ncp ? 8 : 10, last = g.nsymb - (mapping ? srs_active : 0);
+  for (uint32_t l = 0; l < last; l++)
+    if (l != p0 && l != p1) g.sym[g.n_data++] = l;
+}
+}  // namespace
+
+extern "C" int oai4g_pusch_dft_plan(int32_t Msc, oai4g_pusch_plan_t *plan, int16_t *twiddles, uint32_t capacity)
+{
+  oai4g_pusch_plan_t pl;
+  std::vector<int16_t> tw;
+  if (!plan) { set_err("pusch_dft_plan: null plan"); return -1; }
+  if (!pusch_plan("pusch_dft_plan", Msc, true, true, pl, tw)) return -1;
+  if (twiddles && capacity < pl.n_twiddles) { set_err("pusch_dft_plan: %u twiddles do not fit %u", pl.n_twiddles, capacity); return -1; }
+  *plan = pl;
+  if (twiddles && !tw.empty()) memcpy(twiddles, tw.data(), tw.size() * sizeof(int16_t));
+  return 0;
+}
+
+struct oai4g_pusch_config {
+  oai4g_frame_parms_t fp;
+  uint32_t Qm, G;
+  pusch_engine_t eng;
+  pusch_grid_t map_grid, idft_grid;
+  pusch_mod_t mod;
+  dev_buf<uint32_t> gold;                 /* [10][1 + (G >> 5)] */
+};
+
+/* what ulsch_modulation itself refuses, nothing written (ulsch_modulation.c:413-429): 1 with the error set */
+static int pusch_ref_refusal(const char *who, uint32_t harq_pid, uint32_t first_rb, uint32_t nb_rb)
+{
+  if (harq_pid > 7) { set_err("%s: Illegal harq_pid %u", who, harq_pid); return 1; }
+  if (nb_rb == 0) { set_err("%s: Illegal nb_rb 0", who); return 1; }
+  if (first_rb > 25) { set_err("%s: Illegal first_rb %u", who, first_rb); return 1; }
+  return 0;
+}
+
+/* everything of a configuration but the device: the checks, shared with the drop-in so that it refuses before it touches anything */
+static bool pusch_config_ok(const char *who, const oai4g_frame_parms_t *fp, uint32_t first_rb, uint32_t nb_rb, uint32_t Qm,
+                            uint32_t srs_active, uint32_t first_subframe, uint32_t subframe_step)
+{
+  if (!fp) { set_err("%s: null frame parameters", who); return false; }
+  if (pusch_ref_refusal(who, 0, first_rb, nb_rb)) return false;
+  oai4g_pusch_plan_t pl;
+  std::vector<int16_t> tw;
+  if (!pusch_plan(who, 12 * (int32_t)nb_rb, true, true, pl, tw)) return false;
+  const uint32_t N = fp->ofdm_symbol_size;
+  if (fp->N_RB_DL == 0 || N < 12u * fp->N_RB_DL || N > 2048 || fp->first_carrier_offset != N - 6u * fp->N_RB_DL || fp->Ncp > 1) {
+    set_err("%s: frame parameters are not initialised (N_RB_DL %u, ofdm_symbol_size %u)", who, fp->N_RB_DL, N);
+    return false;
+  }
+  if (first_rb + nb_rb > fp->N_RB_DL) { set_err("%s: first_rb %u + nb_rb %u leaves the band of %u PRB", who, first_rb, nb_rb, fp->N_RB_DL); return false; }
+  if (Qm != 2 && Qm != 4 && Qm != 6) { set_err("%s: Qm %u", who, Qm); return false; }
+  if (srs_active > 1) { set_err("%s: srs_active %u", who, srs_active); return false; }
+  if (first_subframe > 9 || subframe_step > 9) { set_err("%s: subframe %u step %u", who, first_subframe, subframe_step); return false; }
+  if (fp->first_carrier_offset + 12 * first_rb == N) {
+    set_err("%s: first_carrier_offset + 12 first_rb == ofdm_symbol_size (first_rb %u): the reference's wrap test is '>' and it "
+            "writes past the symbol here", who, first_rb);
+    return false;
+  }
+  return true;
+}
+
+extern "C" oai4g_pusch_config_t *oai4g_pusch_config_create(const oai4g_frame_parms_t *fp, uint16_t first_rb, uint16_t nb_rb, uint8_t Qm,
+                                                           uint8_t srs_active, uint16_t rnti, uint8_t first_subframe,
+                                                           uint8_t subframe_step)
+{
+  const char *who = "pusch_config_create";
+  if (!pusch_config_ok(who, fp, first_rb, nb_rb, Qm, srs_active, first_subframe, subframe_step)) return nullptr;
+  NEED_INIT(nullptr);
+  std::unique_ptr<oai4g_pusch_config_t> cfg(new oai4g_pusch_config_t);
+  cfg->fp = *fp;
+  cfg->Qm = Qm;
+  if (!pusch_engine(who, 12 * nb_rb, true, true, cfg->eng)) return nullptr;
+  const uint32_t N = fp->ofdm_symbol_size;
+  pusch_data_symbols(fp->Ncp, true, srs_active, N, cfg->map_grid);
+  pusch_data_symbols(fp->Ncp, false, 0, 12u * fp->N_RB_DL, cfg->idft_grid);
+  cfg->G = 12u * nb_rb * Qm * cfg->map_grid.n_data;
+  pusch_mod_t &m = cfg->mod;
+  memset(&m, 0, sizeof(m));
+  m.Qm = Qm;
+  m.first_sf = first_subframe;
+  m.sf_step = subframe_step;
+  m.gold_words = 1 + (cfg->G >> 5);
+  m.re_offset = fp->first_carrier_offset + 12u * first_rb;
+  if (m.re_offset > N) m.re_offset -= N;
+  std::vector<uint32_t> gold((size_t)10 * m.gold_words);
+  for (uint32_t sf = 0; sf < 10; sf++) {
+    uint32_t x1 = 0, x2 = ((uint32_t)rnti << 14) + (sf << 9) + fp->Nid_cell;     /* c_init, 36.211 5.3.1 */
+    for (uint32_t w = 0; w < m.gold_words; w++) gold[(size_t)sf * m.gold_words + w] = oai4g_lte_gold_generic(&x1, &x2, w == 0);
+  }
+  HCK(cfg->gold.upload(gold), nullptr);
+  return cfg.release();
+}
+
+extern "C" void oai4g_pusch_config_destroy(oai4g_pusch_config_t *cfg) { delete cfg; }
+
+extern "C" int oai4g_pusch_mod_batch(oai4g_pusch_config_t *cfg, int n_sf, const uint8_t *d_h, size_t h_stride, int16_t amp,
+                                     int32_t *d_txdataF, void *stream)
+{
+  if (!cfg || n_sf < 0 || (n_sf > 0 && (!d_h || !d_txdataF))) { set_err("pusch_mod_batch: bad arguments"); return -1; }
+  if (h_stride < cfg->G || h_stride > 0xFFFFFFFFu) { set_err("pusch_mod_batch: h_stride %zu is less than G = %u", h_stride, cfg->G); return -1; }
+  NEED_INIT(-1);
+  pusch_mod_t m = cfg->mod;
+  m.h_stride = (uint32_t)h_stride;
+  m.amp = amp;
+  m.gain_qpsk = (int16_t)((amp * 23170) >> 15);          /* gain_lin_QPSK = (amp * ONE_OVER_SQRT2_Q15) >> 15 */
+  HCK(oai4g_launch_pusch_mod(cfg->eng.p, cfg->eng.tw.get(), cfg->map_grid, m, d_h, cfg->gold.get(), (uint32_t *)d_txdataF,
+                             (uint32_t)n_sf, (hipStream_t)stream), -1);
+  return 0;
+}
+
+extern "C" int oai4g_pusch_dft_batch(oai4g_pusch_config_t *cfg, int n_sf, const int32_t *d_d, int32_t *d_z, void *stream)
+{
+  if (!cfg || n_sf < 0 || (n_sf > 0 && (!d_d || !d_z))) { set_err("pusch_dft_batch: bad arguments"); return -1; }
+  NEED_INIT(-1);
+  HCK(oai4g_launch_pusch_dft(cfg->eng.p, cfg->eng.tw.get(), (const uint32_t *)d_d, (uint32_t *)d_z,
+                             (uint32_t)n_sf * cfg->map_grid.n_data, (hipStream_t)stream), -1);
+  return 0;
+}
+
+extern "C" int oai4g_pusch_idft_batch(oai4g_pusch_config_t *cfg, int n_sf, int32_t *d_comp, void *stream)
+{
+  if (!cfg || n_sf < 0 || (n_sf > 0 && !d_comp)) { set_err("pusch_idft_batch: bad arguments"); return -1; }
+  NEED_INIT(-1);
+  HCK(oai4g_launch_pusch_idft(cfg->eng.p, cfg->eng.tw.get(), cfg->idft_grid, (uint32_t *)d_comp, (uint32_t)n_sf, (hipStream_t)stream), -1);
+  return 0;
+}
+
+/* n transforms of Msc on host samples through k_pusch_dft */
+static int pusch_dft_host(const char *who, int32_t Msc, bool scale_flag, bool leaf12, const void *x, void *y, uint32_t n)
+{
+  if (!x || !y) { set_err("%s: null buffer", who); return -1; }
+  oai4g_pusch_plan_t pl;
+  std::vector<int16_t> tw;
+  if (!pusch_plan(who, Msc, scale_flag, leaf12, pl, tw)) return -1;       /* refuse before the device is touched */
+  if (n == 0) return 0;
+  NEED_INIT(-1);
+  pusch_engine_t eng;
+  if (!pusch_engine(who, Msc, scale_flag, leaf12, eng)) return -1;
+  const size_t bytes = (size_t)n * Msc * 4;
+  stage_t st(who);
+  const int r_in = st.add(bytes), r_out = st.add(bytes);
+  if (!st.open()) return -1;
+  HCK(st.up(r_in, x, bytes), -1);
+  HCK(oai4g_launch_pusch_dft(eng.p, eng.tw.get(), st.ptr<uint32_t>(r_in), st.ptr<uint32_t>(r_out), n, g_scr.s), -1);
+  HCK(st.down(y, r_out, bytes), -1);
+  HCK(st.sync(), -1);
+  return 0;
+}
+
+extern "C" int oai4g_dft_lte(int32_t *z, const int32_t *d, int32_t Msc_PUSCH, uint8_t Nsymb)
+{
+  if (Nsymb > 12) { set_err("dft_lte: Nsymb %u (at most 12 columns)", Nsymb); return -1; }
+  return pusch_dft_host("dft_lte", Msc_PUSCH, true, true, d, z, Nsymb);
+}
+
+extern "C" int oai4g_pusch_dft(int32_t Msc, const int16_t *x, int16_t *y, uint8_t scale_flag)
+{
+  return pusch_dft_host("pusch_dft", Msc, scale_flag == 1, false, x, y, 1);
+}
+
+extern "C" int oai4g_lte_idft(const oai4g_frame_parms_t *fp, int32_t *z, uint16_t Msc_PUSCH)
+{
+  const char *who = "lte_idft";
+  if (!fp || !z) { set_err("%s: null argument", who); return -1; }
+  oai4g_pusch_plan_t pl;
+  std::vector<int16_t> tw;
+  if (!pusch_plan(who, Msc_PUSCH, true, true, pl, tw)) return -1;
+  if (fp->N_RB_DL == 0 || fp->N_RB_DL > 110 || Msc_PUSCH > 12u * fp->N_RB_DL || fp->Ncp > 1) {
+    set_err("%s: Msc %u does not fit N_RB_DL %u", who, Msc_PUSCH, fp->N_RB_DL);
+    return -1;
+  }
+  NEED_INIT(-1);
+  pusch_engine_t eng;
+  if (!pusch_engine(who, Msc_PUSCH, true, true, eng)) return -1;
+  pusch_grid_t g;
+  pusch_data_symbols(fp->Ncp, false, 0, 12u * fp->N_RB_DL, g);
+  const size_t bytes = (size_t)g.nsymb * g.row * 4;
+  stage_t st(who);
+  const int r = st.add(bytes);
+  if (!st.open()) return -1;
+  HCK(st.up(r, z, bytes), -1);
+  HCK(oai4g_launch_pusch_idft(eng.p, eng.tw.get(), g, st.ptr<uint32_t>(r), 1, g_scr.s), -1);
+  HCK(st.down(z, r, bytes), -1);
+  HCK(st.sync(), -1);
+  return 0;
+}
+
+extern "C" int oai4g_ulsch_modulation(int32_t *const *txdataF, int16_t amp, uint32_t frame, uint32_t subframe,
+                                      const oai4g_frame_parms_t *fp, const oai4g_ue_ulsch_t *ulsch)
+{
+  const char *who = "ulsch_modulation";
+  (void)frame;
+  if (!fp || !ulsch) { set_err("%s: Null ulsch or frame parameters", who); return -1; }
+  if (ulsch->harq_pid > 7) return pusch_ref_refusal(who, ulsch->harq_pid, 0, 1);
+  const oai4g_ul_harq_t *hp = ulsch->harq_processes[ulsch->harq_pid];
+  if (!hp) { set_err("%s: null harq process %u", who, ulsch->harq_pid); return -1; }
+  if (int r = pusch_ref_refusal(who, ulsch->harq_pid, hp->first_rb, hp->nb_rb)) return r;
+  if (ulsch->cooperation_flag == 2) { set_err("%s: cooperation_flag 2 (distributed Alamouti) is not supported", who); return -1; }
+  if (subframe > 9) { set_err("%s: subframe %u", who, subframe); return -1; }
+  const uint8_t Qm = oai4g_get_Qm_ul(hp->mcs);
+  if (!pusch_config_ok(who, fp, hp->first_rb, hp->nb_rb, Qm, ulsch->srs_active, subframe, 0)) return -1;
+  const uint32_t nsymb = fp->Ncp ? 12 : 14;
+  if (ulsch->Nsymb_pusch != nsymb - 2 - ulsch->srs_active) {
+    set_err("%s: Nsymb_pusch %u, but the mapping takes %u symbols", who, ulsch->Nsymb_pusch, nsymb - 2 - ulsch->srs_active);
+    return -1;
+  }
+  if (!txdataF || !txdataF[0] || !ulsch->h) { set_err("%s: null txdataF or h", who); return -1; }
+  std::unique_ptr<oai4g_pusch_config_t, void (*)(oai4g_pusch_config_t *)> cfg(
+      oai4g_pusch_config_create(fp, hp->first_rb, hp->nb_rb, Qm, ulsch->srs_active, ulsch->rnti, (uint8_t)subframe, 0),
+      oai4g_pusch_config_destroy);
+  if (!cfg) return -1;
+  const size_t gb = (size_t)nsymb * fp->ofdm_symbol_size * 4;
+  int32_t *sub = txdataF[0] + (size_t)subframe * nsymb * fp->ofdm_symbol_size;
+  stage_t st(who);
+  const int r_h = st.add(cfg->G), r_g = st.add(gb);
+  if (!st.open()) return -1;
+  HCK(st.up(r_h, ulsch->h, cfg->G), -1);
+  HCK(st.up(r_g, sub, gb), -1);
+  if (oai4g_pusch_mod_batch(cfg.get(), 1, st.ptr<uint8_t>(r_h), cfg->G, amp, st.ptr<int32_t>(r_g), g_scr.s) != 0) return -1;
+  HCK(st.down(sub, r_g, gb), -1);
+  HCK(st.sync(), -1);
+  return 0;
+}

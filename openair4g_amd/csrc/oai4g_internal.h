@@ -729,6 +729,33 @@ struct sss_args_t {
 };
 hipError_t oai4g_launch_sss_offsets(const sss_args_t &a, hipStream_t s);
 hipError_t oai4g_launch_sss(const sss_args_t &a, hipStream_t s);
+/* SC-FDMA transform precoding (oai4g_pusch.hip).  The plan of one size as the kernels read it, by value: level 0 is the
+ * outermost; rcp_r / rcp_m1 are ceil(2^32 / radix) and ceil(2^32 / (M - 1)) for the index divisions */
+#define OAI4G_PUSCH_LEVELS 4
+struct pusch_plan_t {
+  uint32_t N, n_lvl;
+  uint32_t spw;                /* symbols per workgroup of 256 threads: 1, 2, 4, 8 or 16 */
+  uint32_t lds_sym;            /* LDS words per symbol: N (natural order) + N + N / 12 (blocks, padded) */
+  uint32_t leaf_norm;          /* 9459 behind dft12 in dft_lte / lte_idft, else 0 */
+  uint32_t radix[OAI4G_PUSCH_LEVELS], M[OAI4G_PUSCH_LEVELS], norm[OAI4G_PUSCH_LEVELS], tw_off[OAI4G_PUSCH_LEVELS];
+  uint32_t rcp_r[OAI4G_PUSCH_LEVELS], rcp_m1[OAI4G_PUSCH_LEVELS];
+};
+struct pusch_grid_t {          /* the data symbols of a subframe's grid */
+  uint32_t n_data, nsymb, row; /* data symbols per subframe, symbols per subframe, words per symbol row */
+  uint32_t sym[12];
+};
+struct pusch_mod_t {
+  uint32_t Qm, h_stride, first_sf, sf_step, gold_words;
+  uint32_t re_offset;          /* first RE of the allocation, < ofdm_symbol_size */
+  int amp, gain_qpsk;
+};
+/* d_tw: per twiddle (t.re, -t.im) and (t.im, t.re) as packed int16 pairs */
+hipError_t oai4g_launch_pusch_dft(const pusch_plan_t &p, const uint2 *d_tw, const uint32_t *d_in, uint32_t *d_out, uint32_t n_sym,
+                                  hipStream_t s);
+hipError_t oai4g_launch_pusch_idft(const pusch_plan_t &p, const uint2 *d_tw, const pusch_grid_t &g, uint32_t *d_comp, uint32_t n_sf,
+                                   hipStream_t s);
+hipError_t oai4g_launch_pusch_mod(const pusch_plan_t &p, const uint2 *d_tw, const pusch_grid_t &g, const pusch_mod_t &m,
+                                  const uint8_t *d_h, const uint32_t *d_gold, uint32_t *d_txF, uint32_t n_sf, hipStream_t s);
 void oai4g_set_error(const char *fmt, ...);
 /* binds the calling thread to the device the library was initialised on (hipSetDevice is per thread) */
 int oai4g_bind_thread(void);
